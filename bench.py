@@ -18,13 +18,26 @@ torch.distributed.run with N ranks; it refuses to run if the node has fewer than
 WORLD_SIZE disagrees with --gpus.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (usv_qp_rti), timed with HIP
-events on the stream the kernels run on; `cpu_baseline` times the CPU oracle (a port, not the
-reference) on a bounded sample of the same workload.
+events on the stream the kernels run on.
+
+A plain run sets up, warms up, times the --steps steps and prints the line; nothing else.  `--full` adds what
+goes beyond the headline figure: the closed-loop parity check against the CPU oracle during the warm-up
+(`parity`, exit status 4 when its rule is violated), `cpu_baseline` (the CPU oracle, a port, not the reference,
+timed on a bounded sample of the same workload), the extra timed regions `survey_verbatim` and
+`configs4_condensed`, and under a launcher the un-timed all-gather of the results (`allgather`).  In a plain
+run those keys are null.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed - the arrays a caller of
+the solve + hand-over receives - as DIR/<name>.npy (float64, rank 0's instances): x [S, N+1, nx], u [S, N, nu],
+x0 [S, nx] (the hand-over's next initial state), status, qp_status, qp_iter [S].  S is the whole batch when it
+fits in 48 MiB, otherwise a fixed seeded sample (numpy default_rng(0), sorted instance indices; written as
+instance_index.npy).  The inputs depend only on the arguments, so two builds can be compared file by file.
 """
 import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -226,7 +239,7 @@ def survey_verbatim_leg(args, name, N, K, B, device, parity_sample):
 
 
 def configs4_condensed_leg(args, device):
-    """A third short region of the default line: BASELINE configs[4] ("+ partial condensing") at its per-GPU share - usv_model_pf_ca, N = 80, 20 MOVING
+    """A third short region of the --full line: BASELINE configs[4] ("+ partial condensing") at its per-GPU share - usv_model_pf_ca, N = 80, 20 MOVING
     obstacles, 8192 instances - solved with qp_solver_cond_N = 10 (usv_qp_cond: condense on the device, IPM on the ten dense stages, expand) and, on the
     same inputs, uncondensed (usv_qp_rti, the default formulation).  Tick 0 (both cold starts coincide) compares the two solutions; then 2 warm-up +
     4 timed closed-loop ticks each.  Returns the `configs4_condensed` object of the line."""
@@ -275,8 +288,28 @@ def configs4_condensed_leg(args, device):
     return out
 
 
+DUMP_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, solver, status, qp_status, qp_iter):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files; a fixed seeded sample of the instances when
+    the whole batch would exceed DUMP_BYTES."""
+    B, N, nx, nu = solver.B, solver.N, solver.nx, solver.nu
+    per_instance = 8 * ((N + 1) * nx + N * nu + nx + 3)
+    S = min(B, max(1, DUMP_BYTES // per_instance))
+    idx = np.arange(B) if S == B else np.sort(np.random.default_rng(0).choice(B, S, replace=False))
+    arrays = {"x": solver.get_all("x")[idx], "u": solver.get_all("u")[idx], "x0": solver.get("x0", 0)[idx],
+              "status": status[idx], "qp_status": qp_status[idx], "qp_iter": qp_iter[idx]}
+    if S < B:
+        arrays["instance_index"] = idx
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    sys.stderr.write("bench.py: wrote %s (%d of %d instances) to %s\n" % (", ".join(sorted(arrays)), S, B, out_dir))
+
+
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: become N ranks under torch.distributed.run."""
+    """`python bench.py --gpus N` without a launcher: run N ranks under torch.distributed.run and exit with its status."""
     import torch
     have = torch.cuda.device_count()
     if have < args.gpus:
@@ -289,7 +322,7 @@ def self_launch(args):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))   # (a fresh process: this one has already asked the runtime for its devices)
 
 
 def main():
@@ -312,7 +345,13 @@ def main():
     ap.add_argument("--sigma", type=float, default=None,
                     help="std of the Gaussian disturbance added at the hand-over (default: 1e-3 for survey, 0 for r01)")
     ap.add_argument("--cond-N", type=int, default=0, help="qp_solver_cond_N (0: acados default = N, no condensing)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="instances timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what goes beyond the headline figure: parity check against the CPU oracle in the warm-up, CPU baseline, the "
+                         "survey_verbatim and configs4_condensed timed regions, the all-gather under a launcher (off: those keys are null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (x, u, x0, status, qp_status, qp_iter of rank 0's "
+                         "instances, float64; a fixed seeded sample of them if they exceed 48 MiB) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="instances timed on the CPU oracle (0 = skip; with --full)")
     ap.add_argument("--oracle-opt", action="append", default=[], metavar="NAME=VALUE",
                     help="option of the CPU oracle in the un-timed parity leg (oracle/usv_oracle.h usv_opts), e.g. itref_corr_max=2 or "
                          "cond_pred_corr=1: HPIPM options the restatement leaves off by default; may be repeated")
@@ -321,7 +360,7 @@ def main():
     ap.add_argument("--spread-mode", default="R04", choices=["BALANCE", "SPEED", "ROBUST", "R04", "none"],
                     help="second profile for parity.profile_spread: the device under --hpipm-mode against the device under this profile on the parity sample")
     ap.add_argument("--no-survey-verbatim", action="store_true",
-                    help="skip the extra timed regions of the default line: SURVEY 8(d)'s generator to the letter (`survey_verbatim`) and BASELINE configs[4] with "
+                    help="with --full: skip its extra timed regions: SURVEY 8(d)'s generator to the letter (`survey_verbatim`) and BASELINE configs[4] with "
                          "qp_solver_cond_N = 10 against its uncondensed default (`configs4_condensed`)")
     ap.add_argument("--bind-numa", default="auto", choices=["auto", "on", "off"],
                     help="pin each rank's host threads to its GPU's NUMA node (auto: under a multi-rank launch)")
@@ -330,6 +369,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)  # does not return
 
@@ -391,8 +432,8 @@ def main():
             torch.cuda.synchronize()
 
     # ---- warmup (un-timed).  On a single GPU it doubles as a closed-loop parity check: the first S1 instances are
-    # replayed tick by tick on the CPU oracle, fed the x0 the device's hand-over produced (disturbance included)
-    check = rank == 0 and args.gpus == 1 and args.cpu_sample != 0
+    # replayed tick by tick on the CPU oracle, fed the x0 the device's hand-over produced (disturbance included) - with --full
+    check = args.full and rank == 0 and args.gpus == 1 and args.cpu_sample != 0
     parity = cpu_baseline = None
     if check:
         from oracle import binding as ob
@@ -549,11 +590,13 @@ def main():
     qi = solver.get_int("qp_iter")
     qs = solver.get_int("qp_status")
     tmin = solver.get("obs_tmin", 0) if K > 0 else np.full(B, 1e300)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver, st, qs, qi)
 
     # ---- optional exchange (north_star): all-gather of the optimal trajectories over RCCL, un-timed, on the solver's
-    # own device buffers (zero-copy views)
+    # own device buffers (zero-copy views) - with --full
     gather = None
-    if dist is not None:
+    if dist is not None and args.full:
         g = {}
         for what in ("u0", "x1", "trajectory"):
             torch.cuda.synchronize()
@@ -644,7 +687,7 @@ def main():
 
     # ---- the survey's generator to the letter, as a second short timed region of the same run (single-GPU default-workload lines)
     survey_verbatim = None
-    if rank == 0 and args.gpus == 1 and args.workload == "survey" and not args.no_survey_verbatim and not cond_applied and not args.moving and K > 0:
+    if args.full and rank == 0 and args.gpus == 1 and args.workload == "survey" and not args.no_survey_verbatim and not cond_applied and not args.moving and K > 0:
         solver.sync()
         survey_verbatim = survey_verbatim_leg(args, name, N, K, B, local_rank, min(S1, 128) if check else 0)
 

@@ -1,7 +1,10 @@
 """bench.py's contract, checked without a GPU: the algorithmic byte counts of SURVEY 8(d), the CPU-core detection,
-and the shape of the JSON line (on the line committed next to the profiles of the same build)."""
+and the shape of the JSON line (on the line committed next to the profiles of the same build); --dump-outputs on a stand-in
+solver.  One `-m gpu` test runs a plain line with --dump-outputs."""
 import json
 import os
+
+import pytest
 
 import bench
 
@@ -237,3 +240,77 @@ def test_default_line_carries_configs4_with_its_condensing_applied():
     assert t["rel_err_per_instance"]["p50"] <= 1e-9 and t["rel_err_per_instance"]["p99"] <= 1e-5 and t["rel_err_per_instance"]["max"] <= 1e-3
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "def configs4_condensed_leg" in src and '"configs4_condensed": configs4_condensed' in src
+
+
+class _FakeSolver:
+    """The slice of BatchOcpSolver that bench.dump_outputs reads."""
+
+    def __init__(self, B, N, nx, nu):
+        self.B, self.N, self.nx, self.nu = B, N, nx, nu
+
+    def get_all(self, field):
+        import numpy as np
+        n, ns = {"x": (self.nx, self.N + 1), "u": (self.nu, self.N)}[field]
+        return np.arange(self.B * ns * n, dtype=np.float64).reshape(self.B, ns, n)
+
+    def get(self, field, stage):
+        import numpy as np
+        assert field == "x0" and stage == 0
+        return np.arange(self.B * self.nx, dtype=np.float64).reshape(self.B, self.nx) + 0.5
+
+
+def test_dump_outputs_writes_float64_within_the_budget(tmp_path):
+    """--dump-outputs: x, u, x0 and the per-instance status arrays of the last step as float64 .npy; the whole batch when it fits,
+    otherwise the same seeded sample of instances on every run, and at most 64 MB in all."""
+    import numpy as np
+    small = _FakeSolver(16, 40, 14, 2)
+    st, qs, qi = np.arange(16, dtype=np.int32), np.zeros(16, dtype=np.int32), np.full(16, 7, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), small, st, qs, qi)
+    names = {f[:-4] for f in os.listdir(tmp_path / "a")}
+    assert names == {"x", "u", "x0", "status", "qp_status", "qp_iter"}
+    for n in names:
+        assert np.load(tmp_path / "a" / (n + ".npy")).dtype == np.float64, n
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), small.get_all("x"))
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), st)
+
+    big = _FakeSolver(65536, 40, 14, 2)
+    z = np.zeros(65536, dtype=np.int32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, z, z, z)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert "instance_index.npy" in files and sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64e6
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
+    idx = np.load(tmp_path / "b" / "instance_index.npy").astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(np.load(tmp_path / "b" / "u.npy"), big.get_all("u")[idx])
+
+
+def test_plain_and_full_options_are_declared():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline line without the extra regions or checks, with the steps asked for, and
+    --dump-outputs writes the last step's outputs; the same arguments give the same inputs, hence the same outputs."""
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1024",
+                            "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "solves/s"
+        for k in ("parity", "cpu_baseline", "survey_verbatim", "configs4_condensed", "allgather"):
+            assert line[k] is None, k
+        outs.append({n: np.load(tmp_path / d / (n + ".npy")) for n in ("x", "u", "x0", "status", "qp_status", "qp_iter")})
+    x, u = outs[0]["x"], outs[0]["u"]
+    assert x.shape == (1024, 41, 14) and u.shape == (1024, 40, 2) and x.dtype == np.float64 and np.isfinite(x).all()
+    for n in outs[0]:
+        assert np.array_equal(outs[0][n], outs[1][n]), n   # (the kernels are bit-reproducible: tests/test_gpu_api.py)

@@ -38,7 +38,7 @@ def test_bench_distributed_branch_under_the_launcher():
     env = _env()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "2048", "--cpu-sample", "0", "--bind-numa", "on"]
+           "--batch", "2048", "--cpu-sample", "0", "--bind-numa", "on", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -22,9 +22,9 @@ echo "GPUs visible: $have, running up to $max" | tee "$out/scale_run.log"
 for n in 1 2 4 8; do
   [ "$n" -gt "$max" ] && break
   extra=""; [ "$n" -gt 1 ] && extra="--cpu-sample 0"
-  python bench.py --gpus $n $extra > "$out/weak_n$n.json" 2> "$out/weak_n$n.err"; echo "weak n=$n rc $?" | tee -a "$out/scale_run.log"
-  python bench.py --gpus $n --global-batch 262144 --cpu-sample 0 > "$out/cfg3_n$n.json" 2> "$out/cfg3_n$n.err"; echo "cfg3 n=$n rc $?" | tee -a "$out/scale_run.log"
-  python bench.py --gpus $n --global-batch 65536 --horizon 80 --obstacles 20 --moving --cpu-sample 0 > "$out/cfg4_n$n.json" 2> "$out/cfg4_n$n.err"; echo "cfg4 n=$n rc $?" | tee -a "$out/scale_run.log"
+  python bench.py --full --gpus $n $extra > "$out/weak_n$n.json" 2> "$out/weak_n$n.err"; echo "weak n=$n rc $?" | tee -a "$out/scale_run.log"
+  python bench.py --full --gpus $n --global-batch 262144 --cpu-sample 0 > "$out/cfg3_n$n.json" 2> "$out/cfg3_n$n.err"; echo "cfg3 n=$n rc $?" | tee -a "$out/scale_run.log"
+  python bench.py --full --gpus $n --global-batch 65536 --horizon 80 --obstacles 20 --moving --cpu-sample 0 > "$out/cfg4_n$n.json" 2> "$out/cfg4_n$n.err"; echo "cfg4 n=$n rc $?" | tee -a "$out/scale_run.log"
 done
 python - "$out" <<'PY'
 import glob, json, os, sys
