@@ -62,8 +62,7 @@ int occupancy_of(const DevSpec &S, int N2, CondDims &D, size_t &lds, int &nb)
     if (!cond_dims(S, M::NX, M::NU, M::IPX, M::IPY, N2, NT, SOFT, D)) return USVMPC_E_ARG;
     lds = (size_t)D.lds_doubles * sizeof(double);
     if (lds > 160u * 1024u) return 0; // (nb = 0: does not fit)
-    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, NT, lds) != hipSuccess)
+    if (set_dynamic_lds((const void *)kern, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, NT, lds) != hipSuccess)
         return USVMPC_E_HIP;
     return 0;
 }
@@ -85,13 +84,14 @@ int prepare_for(const DevSpec &S, int N2, CondDims &D, size_t &lds, int &nb, std
 }
 
 template <class M, int KCH, bool SOFT>
-int run_for(const CondDims &Dh, hipStream_t st, long teams, size_t lds, const DevPtrs &P, const CondDims *dD, double *scratch, int B)
+int run_for(const CondDims &Dh, hipStream_t st, long teams, size_t lds, const DevPtrs &P, const CondDims *dD, double *scratch, int B, std::string &err)
 {
     const int nt = Dh.nt;
     if (nt == 64) hipLaunchKernelGGL((usv_qp_cond<M, KCH, SOFT, 64, 0, 0>), dim3((unsigned)teams), dim3(64), lds, st, P, dD, scratch, B, (int)teams);
     else if (CondFixed<M, SOFT>::MB > 0 && Dh.Mb == CondFixed<M, SOFT>::MB && Dh.nxr == CondFixed<M, SOFT>::NXR) {
         auto kern = &usv_qp_cond<M, KCH, SOFT, 256, CondFixed<M, SOFT>::MB, CondFixed<M, SOFT>::NXR>;
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+        const hipError_t e = set_dynamic_lds((const void *)kern, lds);
+        if (e != hipSuccess) { err = std::string("partial condensing: set_dynamic_lds: ") + hipGetErrorString(e); return USVMPC_E_HIP; }
         hipLaunchKernelGGL(kern, dim3((unsigned)teams), dim3(256), lds, st, P, dD, scratch, B, (int)teams);
     } else hipLaunchKernelGGL((usv_qp_cond<M, KCH, SOFT, 256, 0, 0>), dim3((unsigned)teams), dim3(256), lds, st, P, dD, scratch, B, (int)teams);
     return 0;
@@ -131,12 +131,14 @@ int cond_prepare(int model, int kch, const DevSpec &S, int N2, CondDims &D, size
     return USVMPC_E_ARG;
 }
 
-int cond_run(int model, int kch, const CondDims &Dh, hipStream_t st, long teams, size_t lds_bytes, const DevPtrs &P, const CondDims *dD, double *scratch, int B)
+int cond_run(int model, int kch, const CondDims &Dh, hipStream_t st, long teams, size_t lds_bytes, const DevPtrs &P, const CondDims *dD, double *scratch, int B,
+             std::string &err)
 {
-#define USV_COND_RUN(M, K, SF) run_for<M, K, SF>(Dh, st, teams, lds_bytes, P, dD, scratch, B)
+#define USV_COND_RUN(M, K, SF) run_for<M, K, SF>(Dh, st, teams, lds_bytes, P, dD, scratch, B, err)
     USV_COND_DISPATCH(USV_COND_RUN)
 #undef USV_COND_RUN
-    return -1;
+    err = "partial condensing: no kernel for this model in this library";
+    return USVMPC_E_ARG;
 }
 
 } // namespace usv

@@ -10,9 +10,9 @@
 //
 // Build parts.  The QP kernel templates are what takes minutes to compile, and one (model, obstacle chunks) pair has nothing in common
 // with another: __graft_entry__.build() therefore compiles THIS file several times in parallel, -DUSV_PART=0 for the C ABI, the handle
-// bookkeeping and the small kernels, -DUSV_PART=1 .. 5 for one launch_pair / export_pair instantiation each (explicit instantiation
-// there, extern template everywhere else), and links the objects.  Without USV_PART everything is one translation unit (the generated-
-// model libraries of genbuild.py, tools/dev_build.sh).
+// bookkeeping, the launch policy and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
+// kernels_for<M, KCH, SOFT> (explicit instantiation in its part, extern template in part 0, which calls it) - and links the objects.
+// Without USV_PART everything is one translation unit (the generated-model libraries of genbuild.py).
 #ifndef USV_PART
 #define USV_PART -1
 #endif
@@ -34,7 +34,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 using namespace usv;
@@ -179,22 +181,40 @@ constexpr qp_resume_co_t resume_co_kernel()
     if constexpr (KCH == 1 || (KCH == 0 && !MERGE)) return &usv_qp_resume_co<M, KCH, SOFT, MERGE>;
     else return nullptr;
 }
-// the wide kernels of one layout: [planes in LDS, planes in HBM] x [one wave, four waves per instance], and the follow-up kernel
-// (nplw: planes per stage an instance keeps in LDS; ex_lds / ex_hbm: planes of the exchange area - qp_ipm.hpp NPLW, EX_N)
 using qp_kernel_t = void (*)(DevPtrs, long, int, int, int);
-struct WideSet { qp_kernel_t lds1, hbm1, lds4, hbm4; qp_resume_t resume, resume_lds; qp_resume_co_t resume_co; int nplw, ex_lds, ex_hbm; };
-constexpr WideSet NO_WIDE = WideSet{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+using group_kernel_t = void (*)(DevPtrs, long); // (the lineariser, the multiplier read-back)
+
+// The kernels of one (model, obstacle chunks) pair for the handle's current row layout (kernels_for), and what the launch policy needs to
+// know about them.  A null kernel: that mapping does not exist for the layout.
+struct Kernels {
+    qp_kernel_t qp, qp_lds, qp_aux;              // four instances per wave: planes in HBM / the workspace in LDS / the aux plane in LDS
+    qp_kernel_t wide_lds1, wide_hbm1, wide_lds4, wide_hbm4; // the latency mapping: [planes in LDS, in HBM] x [one wave, four waves per instance]
+    qp_resume_t resume, resume_lds;              // the follow-up launch of a hand-over: over the planes in HBM / after copying them into LDS
+    qp_resume_co_t resume_co;                    // ... and its co-resident form (usv_qp_resume_co)
+    int nplw, ex_lds, ex_hbm;                    // planes per stage an instance keeps in LDS; planes of the exchange area (qp_ipm.hpp NPLW, EX_N)
+    group_kernel_t lin[2][3];                    // usv_linearize [MULTI][MODE]
+    group_kernel_t qp_export;                    // usv_qp_export
+    int npt_hard, npt_soft;                      // WsLayout::NPT without / with soft state bounds
+    int kch;                                     // the instantiation's KCH and SOFT (h->kch / h->soft may differ: usv_model with "soft" set)
+    bool soft;
+};
+
 template <class M, int KCH, bool SOFT, bool MERGE, bool SOFTBOX = false, bool UNPACKED = false>
-constexpr WideSet wide_set()
+void set_wide(Kernels &k)
 {
     using WL = WsLayout<M, KCH, SOFT, SOFTBOX>;
     constexpr bool packed = KCH > 0 && !SOFTBOX && !UNPACKED; // (the packed layouts leave the four box planes out of the LDS map)
-    return WideSet{wide_kernel<M, KCH, SOFT, MERGE, true, 1, SOFTBOX, UNPACKED>(), wide_kernel<M, KCH, SOFT, MERGE, false, 1, SOFTBOX, UNPACKED>(),
-                   wide_kernel<M, KCH, SOFT, MERGE, true, 4, SOFTBOX, UNPACKED>(), wide_kernel<M, KCH, SOFT, MERGE, false, 4, SOFTBOX, UNPACKED>(),
-                   (SOFTBOX || (UNPACKED && KCH > 0)) ? nullptr : resume_kernel<M, KCH, SOFT, MERGE>(),
-                   (SOFTBOX || (UNPACKED && KCH > 0)) ? nullptr : resume_kernel<M, KCH, SOFT, MERGE, true>(),
-                   (SOFTBOX || (UNPACKED && KCH > 0)) ? nullptr : resume_co_kernel<M, KCH, SOFT, MERGE>(),
-                   WL::P_RB0 - (packed ? 4 : 0) + (SOFTBOX ? 6 : 0), wide_ex_planes(KCH, SOFTBOX), wide_ex_planes_hbm(KCH, SOFTBOX)};
+    constexpr bool resumes = !(SOFTBOX || (UNPACKED && KCH > 0));
+    k.wide_lds1 = wide_kernel<M, KCH, SOFT, MERGE, true, 1, SOFTBOX, UNPACKED>();
+    k.wide_hbm1 = wide_kernel<M, KCH, SOFT, MERGE, false, 1, SOFTBOX, UNPACKED>();
+    k.wide_lds4 = wide_kernel<M, KCH, SOFT, MERGE, true, 4, SOFTBOX, UNPACKED>();
+    k.wide_hbm4 = wide_kernel<M, KCH, SOFT, MERGE, false, 4, SOFTBOX, UNPACKED>();
+    k.resume = resumes ? resume_kernel<M, KCH, SOFT, MERGE>() : nullptr;
+    k.resume_lds = resumes ? resume_kernel<M, KCH, SOFT, MERGE, true>() : nullptr;
+    k.resume_co = resumes ? resume_co_kernel<M, KCH, SOFT, MERGE>() : nullptr;
+    k.nplw = WL::P_RB0 - (packed ? 4 : 0) + (SOFTBOX ? 6 : 0);
+    k.ex_lds = wide_ex_planes(KCH, SOFTBOX);
+    k.ex_hbm = wide_ex_planes_hbm(KCH, SOFTBOX);
 }
 
 // Multiplier read-back (usvmpc_get "lam" / "t"): the inequality multipliers and slacks of every instance's last QP, from the
@@ -409,7 +429,8 @@ struct usvmpc_handle {
     int handover_co;
     int co_spin_limit;        // polls of ~1 us a co-resident workgroup waits for its entry before it gives up (option "handover_co_spin")
     long co_wgs;              // workgroups of the co-resident launch (option "handover_co_wgs"; 0: one per CU - launch_qp says why)
-    hipStream_t co_stream;    // nullptr until first used
+    bool co_ready;            // co_stream, ev_co_pre / ev_co_end and d_co_ctl exist (made together on first use: co_prepare)
+    hipStream_t co_stream;
     hipEvent_t ev_co_pre, ev_co_end;
     int *d_co_ctl;            // [RING][8] DevPtrs::co_ctl of the last launches
     bool ev3_set[RING];       // ev[.][3] was recorded for that solve
@@ -473,6 +494,91 @@ struct usvmpc_handle {
     std::vector<void *> allocs;
 };
 
+// The kernel table of one (model, obstacle chunks) pair for the handle's current row layout.  (External linkage: a split build defines
+// each instantiation in a translation unit of its own - see "Build parts" at the top.)
+template <class M, int KCH, bool SOFT>
+Kernels kernels_for(const usvmpc_handle *h)
+{
+    constexpr bool CANPACK = KCH > 0;
+    const DevSpec &S = h->spec;
+    const bool pack = CANPACK && S.boxpack != 0;
+    Kernels k = {};
+    k.lin[0][0] = &usv_linearize<M, KCH, SOFT, false, 0>; k.lin[0][1] = &usv_linearize<M, KCH, SOFT, false, 1>; k.lin[0][2] = &usv_linearize<M, KCH, SOFT, false, 2>;
+    k.lin[1][0] = &usv_linearize<M, KCH, SOFT, true, 0>; k.lin[1][1] = &usv_linearize<M, KCH, SOFT, true, 1>; k.lin[1][2] = &usv_linearize<M, KCH, SOFT, true, 2>;
+    k.qp_export = S.any_bsoft ? &usv_qp_export<M, KCH, SOFT, false, true>
+                              : pack ? &usv_qp_export<M, KCH, SOFT, CANPACK, false> : &usv_qp_export<M, KCH, SOFT, false, false>;
+    k.npt_hard = WsLayout<M, KCH, SOFT, false>::NPT; k.npt_soft = WsLayout<M, KCH, SOFT, true>::NPT;
+    k.kch = KCH; k.soft = SOFT;
+    auto qp = [&k](qp_kernel_t q, qp_kernel_t q_lds = nullptr, qp_kernel_t q_aux = nullptr) { k.qp = q; k.qp_lds = q_lds; k.qp_aux = q_aux; };
+    // (one row pass when every box row rides in a slot lane: qp_ipm.hpp, MERGE)
+    const bool merge = pack && h->merge_rows && !S.box_dense;
+#ifdef USV_BENCH_ONLY // development builds (tools/dev_build.sh): only the instantiation the bench workload runs (k.qp null for any other layout)
+    if (!(S.hdiag && pack && !S.any_bsoft)) return k;
+    if (merge) {
+        qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true, CANPACK>,
+           &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK, true>);
+        set_wide<M, KCH, SOFT, CANPACK>(k);
+    } else {
+        qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true>,
+           &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, false, true>);
+    }
+#else
+    if (S.any_bsoft) { // soft state bounds: rows with slacks, ten planes of their own
+        if (S.hdiag) { qp(&usv_qp_rti<M, KCH, SOFT, true, false, true>); set_wide<M, KCH, SOFT, false, true>(k); }
+        else qp(&usv_qp_rti<M, KCH, SOFT, false, false, true>);
+    } else if (S.hdiag) { // (every OCP of the reference: the only instantiations that also come with the workspace in LDS)
+        // (the packed layouts - every OCP of the reference, the bench workloads - also come with the aux plane in LDS)
+        if (merge) {
+            qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true, CANPACK>,
+               &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK, true>);
+            set_wide<M, KCH, SOFT, CANPACK>(k);
+        } else if (pack) {
+            qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true>,
+               &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, false, true>);
+            set_wide<M, KCH, SOFT, false>(k);
+        } else { // (box rows in planes of their own)
+            qp(&usv_qp_rti<M, KCH, SOFT, true, false, false>, &usv_qp_rti<M, KCH, SOFT, true, false, false, true>);
+            set_wide<M, KCH, SOFT, false, false, true>(k);
+        }
+    } else {
+        qp(pack ? &usv_qp_rti<M, KCH, SOFT, false, CANPACK, false> : &usv_qp_rti<M, KCH, SOFT, false, false, false>);
+    }
+#endif
+    return k;
+}
+
+// The instantiations of the stock library: USV_KERNELS(PART, ...) names the pair build part PART compiles; every part declares all of them
+// (extern template) and part PART then defines its own.
+template <int PART> struct PartPair;
+#define USV_KERNELS(PART, M, KCH, SOFT)                                                              \
+    template <> struct PartPair<PART> { using Model = M; static constexpr int kch = KCH; static constexpr bool soft = SOFT; }; \
+    extern template Kernels kernels_for<M, KCH, SOFT>(const usvmpc_handle *);
+#if USV_PART >= 0 && !defined(USV_GEN_ONLY)
+USV_KERNELS(1, ModelM0, 0, false)
+USV_KERNELS(2, ModelM1, 1, true)
+USV_KERNELS(3, ModelM1, 2, true)
+USV_KERNELS(4, ModelM2, 1, false)
+USV_KERNELS(5, ModelM2, 2, false)
+#if USV_PART > 0
+template Kernels kernels_for<PartPair<USV_PART>::Model, PartPair<USV_PART>::kch, PartPair<USV_PART>::soft>(const usvmpc_handle *);
+#endif
+#endif
+
+#if USV_MAIN
+// A kernel's dynamic-LDS limit belongs to the process, not to a handle: it is kept at the largest size any handle has launched the kernel
+// with (a handle with a shorter horizon created later must not lower it under what an older one uses)
+hipError_t usv::set_dynamic_lds(const void *kern, size_t bytes)
+{
+    static std::mutex mu;
+    static std::unordered_map<const void *, size_t> largest;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &cur = largest[kern];
+    if (bytes <= cur) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) cur = bytes;
+    return e;
+}
+
 namespace {
 
 thread_local std::string g_create_err;
@@ -510,14 +616,13 @@ void dev_free(usvmpc_handle *h, void *p, size_t nbytes)
 }
 
 // Forget what the occupancy queries said about the QP kernels: whatever changes WHICH kernel a launch takes (row layout, mapping,
-// wave cap, workspace placement) makes launch_qp ask again - for every instantiation, with its dynamic LDS size set afresh.
+// wave cap, workspace placement) makes launch_qp ask again - for every kernel of the handle's table.
 void reset_caps(usvmpc_handle *h)
 {
     h->qp_cap = 0; h->lds_cap = 0; h->aux_cap = 0;
     h->wide_cap = 0; h->wide_hbm_cap = 0; h->wide4_cap = 0; h->wide4_hbm_cap = 0; h->resume_cap = 0;
 }
 
-#if USV_MAIN
 struct Field {
     double *base;   // device pointer
     int n;          // per-stage length
@@ -595,8 +700,6 @@ int mirror_quiesce(usvmpc_handle *h)
     return 0;
 }
 
-#endif // USV_MAIN
-
 // upload what the mirror holds newer than the device: consecutive dirty fields go as one copy
 int mirror_flush(usvmpc_handle *h)
 {
@@ -636,7 +739,6 @@ int mirror_flush(usvmpc_handle *h)
     return 0;
 }
 
-#if USV_MAIN
 int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, size_t n, bool set)
 {
     if (!h) return USVMPC_E_ARG;
@@ -737,8 +839,6 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
     return 0;
 }
 
-#endif // USV_MAIN
-
 // the condensed QP solve of an RTI iteration (after the lineariser): buffers on first use; the kernels live in cond_kernels.hip
 int launch_cond(usvmpc_handle *h)
 {
@@ -764,10 +864,8 @@ int launch_cond(usvmpc_handle *h)
         HIP_TRY(h, hipMemsetAsync(h->ptrs.t_out, 0, nbytes, h->stream));
         h->export_at = h->nsolves + 1;
     }
-    if (cond_run(h->desc.model, h->kch, h->cond_dims, h->stream, h->cond_teams, h->cond_lds, h->ptrs, h->d_cond_dims, h->d_cond_scratch, h->B)) {
-        h->err = "partial condensing: no kernel for this model in this library";
-        return USVMPC_E_ARG;
-    }
+    const int rcr = cond_run(h->desc.model, h->kch, h->cond_dims, h->stream, h->cond_teams, h->cond_lds, h->ptrs, h->d_cond_dims, h->d_cond_scratch, h->B, h->err);
+    if (rcr) return rcr;
     h->map_changed = true; // (the group-indexed workspace holds no multipliers of this QP: a later full SQP starts afresh)
     return 0;
 }
@@ -779,19 +877,272 @@ void cond_release(usvmpc_handle *h)
     h->d_cond_scratch = nullptr; h->d_cond_dims = nullptr; h->cond_teams = 0;
 }
 
-} // namespace
+// Workgroups of `block` threads a CU holds of `kern` with `dyn` bytes of dynamic LDS (the kernel's limit raised to that first); 0: it does
+// not fit - static and dynamic LDS over a CU's 160 KB - or a call failed
+template <class F>
+int blocks_per_cu(F kern, int block, size_t dyn)
+{
+    const void *f = (const void *)kern;
+    hipFuncAttributes fa;
+    int nb = 0;
+    if (f == nullptr || hipFuncGetAttributes(&fa, f) != hipSuccess || fa.sharedSizeBytes + dyn > 160u * 1024u || set_dynamic_lds(f, dyn) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, block, dyn) != hipSuccess)
+        return 0;
+    return nb;
+}
 
-// (external linkage: a split build defines each instantiation in a translation unit of its own - see "Build parts" at the top)
-template <class M, int KCH, bool SOFT>
-int launch_pair(usvmpc_handle *h, int phase)
+// The co-resident follow-up kernel's stream, events and control ring: made together on first use, co_ready set last.  When one of them
+// cannot be made, what was made is released and the handle's hand-overs go to the follow-up launch behind the main one only.
+void co_release(usvmpc_handle *h)
+{
+    if (h->co_stream) { (void)hipStreamSynchronize(h->co_stream); (void)hipStreamDestroy(h->co_stream); }
+    if (h->ev_co_pre) (void)hipEventDestroy(h->ev_co_pre);
+    if (h->ev_co_end) (void)hipEventDestroy(h->ev_co_end);
+    dev_free(h, h->d_co_ctl, (size_t)usvmpc_handle::RING * 8 * sizeof(int));
+    h->co_stream = nullptr; h->ev_co_pre = nullptr; h->ev_co_end = nullptr; h->d_co_ctl = nullptr;
+    h->co_ready = false;
+}
+
+bool co_prepare(usvmpc_handle *h)
+{
+    if (h->co_ready) return true;
+    int prio_least = 0, prio_greatest = 0;
+    const bool ok = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess &&
+                    hipStreamCreateWithPriority(&h->co_stream, hipStreamNonBlocking, prio_least) == hipSuccess &&
+                    hipEventCreateWithFlags(&h->ev_co_pre, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&h->ev_co_end, hipEventDisableTiming) == hipSuccess &&
+                    dev_alloc(h, &h->d_co_ctl, (size_t)usvmpc_handle::RING * 8, true) == 0;
+    if (ok) h->co_ready = true;
+    else { co_release(h); h->handover_co = 0; (void)hipGetLastError(); } // (handled here: the launch's own error check must not report it)
+    return ok;
+}
+
+// An RTI solve is ONE launch of as many waves as the device holds at once; their rows start on the first groups and
+// pull the remaining ones from a queue as they finish (qp_ipm.hpp).  The full SQP keeps one group per row: its later
+// iterations find their multipliers in the group's part of the workspace.
+// Small batches: the planes of every instance in flight fit in LDS (160 KB per CU), and a solve whose sweeps wait for
+// HBM at every stage - nothing else runs on the CU to hide it - becomes a solve on LDS.  rows_lds instances per wave
+// (as many whole horizons as fit), one wave per CU at a time; further instances come through the same queue.
+int launch_qp(usvmpc_handle *h, const Kernels &k, int phase)
+{
+    const int qp_block = 64;
+    const long qp_groups = h->Bp;
+    hipEvent_t *ev = h->ev[h->nsolves % usvmpc_handle::RING];
+    const long lds_inst = (long)(h->N + 1) * h->spec.npt * 128;
+    h->last_wide = 0;
+    h->ptrs.susp_count = nullptr; h->ptrs.susp_list = nullptr; h->ptrs.susp_rec = nullptr; h->ptrs.handover_iter = 0; h->ptrs.co_ctl = nullptr; // (set by the path that hands over)
+    // Four waves per instance (qp_ipm.hpp, WW): a workgroup = a whole CU shares out the row work of 16 consecutive stages - for the
+    // single instance and batches of at most one instance per CU.
+    if (k.wide_lds4 != nullptr && phase == 0 && h->wide_mode != 0 && h->wide_waves != 1 && h->ncu > 0) {
+        const size_t pl = (size_t)(h->N + 1) * (size_t)k.nplw * 128;
+        const size_t b4 = pl + (size_t)16 * k.ex_lds * 128 + 128, x4 = (size_t)16 * k.ex_hbm * 128 + 128;
+        const long win_bytes = (long)std::min(h->N + 1, 16) * h->Bp * h->spec.npt * 128; // (the window of a block of 16 stages: 32-bit offsets)
+        if (h->wide4_cap == 0) h->wide4_cap = blocks_per_cu(k.wide_lds4, 4 * qp_block, b4) > 0 ? (long)h->ncu : -1;
+        if (h->wide4_cap < 0 && h->wide4_hbm_cap == 0)
+            h->wide4_hbm_cap = (win_bytes < (1L << 32) && blocks_per_cu(k.wide_hbm4, 4 * qp_block, x4) > 0) ? (long)h->ncu : -1;
+        const bool lds = h->wide4_cap > 0;
+        long cap = lds ? h->wide4_cap : h->wide4_hbm_cap;
+        if (cap > 0 && h->max_waves > 0) cap = std::max<long>(1, std::min(cap, h->max_waves / 4)); // option "max_waves" counts wavefronts
+        // default: where the row work is the larger share - the soft-row OCPs and two obstacle chunks (measured, one instance / 256 instances
+        // per tick: usv_model_guidance_ca1 N = 100 / K = 8 1.78 -> 1.59 / 5.6 -> 5.0 ms, N = 40 / K = 10 0.94 -> 0.86 / 2.05 -> 1.87, N = 80 / K = 20
+        // 4.00 -> 3.00 / 8.1 -> 6.2; usv_model_pf_ca N = 80 / K = 20 6.95 -> 6.22 / 10.4 -> 9.6, with ONE chunk of hard rows 0 - 7 % SLOWER: there
+        // the recursion dominates and pays the barriers)
+        // Up to one instance per CU; with the queue and a horizon of 40 or more up to two (tools/latency_probe.py over 13 shapes x 7 batch sizes,
+        // profiles/r05_f_policy_audit.txt: 512 instances 6 - 8 % under one wave each; at N = 20 the second round costs more than the row work saves)
+        const long reach = (h->dynamic_rows && h->N >= 40) ? 2 * cap : cap;
+        // (round 6, profiles/r06_b_policy_audit.txt: ONE chunk of hard rows also gains 2 - 4 % from four waves when the rows are many and the
+        // horizon long - usv_model_pf_ca N = 40 / K = 10: one instance 2.50 -> 2.40 ms, 64: 5.84 -> 5.63, 256: 4.03 -> 3.94; N = 100 / K = 8,
+        // 64: 9.62 -> 9.34; with K = 3 or 4 it loses - up to one instance per CU)
+        const bool hard_many = !k.soft && k.kch == 1 && h->K >= 8 && h->N >= 40 && (long)h->B <= cap;
+        if (cap > 0 && (h->wide_waves == 4 || ((k.soft || k.kch == 2) && (long)h->B <= reach) || hard_many)) {
+            long nw = (long)h->B;
+            int q0 = -1;
+            if (h->dynamic_rows && nw > cap) { nw = cap; q0 = (int)nw; }
+            if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
+            hipLaunchKernelGGL(lds ? k.wide_lds4 : k.wide_hbm4, dim3((unsigned)nw), dim3(4 * qp_block), lds ? b4 : x4, h->stream, h->ptrs, nw, phase, q0, 1);
+            h->last_wide = 4;
+            return 0;
+        }
+    }
+    // The latency mapping: ONE instance per wave (qp_ipm.hpp, WIDE) - planes in LDS, the four rows share out the stage-local row
+    // work.  A wave then finishes an instance 1.4x (hard rows) to 1.8x (soft rows) sooner and the device holds a quarter of the instances at once: it pays while
+    // the batch leaves SIMDs idle anyway (a solve of the batch then lasts as long as its hardest instance on a lone wave).
+    if (k.wide_lds1 != nullptr && h->wide_mode != 0 && h->ncu > 0) {
+        if (phase == 0) { // (the launches of a full SQP find their multipliers in the group's planes in HBM: the variant over planes in HBM below)
+            // (in LDS: the planes the solve writes - WsLayout's up to L_zu less the four box planes the packed layouts leave unused)
+            const size_t bytes = (size_t)(h->N + 1) * (size_t)k.nplw * 128 + (size_t)4 * k.ex_lds * 128;
+            if (h->wide_cap == 0) {
+                const int nb = blocks_per_cu(k.wide_lds1, qp_block, bytes);
+                h->wide_cap = nb > 0 ? (long)std::min(nb, 4) * h->ncu : -1; // (one wave per SIMD at most: the point is a lone wave's issue rate)
+                if (h->wide_cap > 0 && h->max_waves > 0) h->wide_cap = std::min(h->wide_cap, h->max_waves); // option "max_waves"
+            }
+            // default: while the batch fits the SIMDs twice over (the queue hands the second half to the waves that finish first)
+            if (h->wide_cap > 0 && (h->wide_mode > 0 || (long)h->B <= 2 * h->wide_cap)) {
+                // (without the queue every instance needs its wave at launch: still correct, later workgroups wait)
+                long nw = (long)h->B;
+                int q0 = -1;
+                if (h->dynamic_rows && nw > h->wide_cap) { nw = h->wide_cap; q0 = (int)nw; }
+                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
+                hipLaunchKernelGGL(k.wide_lds1, dim3((unsigned)nw), dim3(qp_block), bytes, h->stream, h->ptrs, nw, phase, q0, 1);
+                h->last_wide = 1;
+                return 0;
+            }
+        }
+        // The horizon's planes do not fit a CU's LDS (the reference node's own N = 100: nmpc_guidance_ca1.cpp:64), or the launch belongs to a
+        // full SQP: the same sweeps over the planes in HBM / L2 - the four rows of a wave address the four stages of a block through one
+        // window, the next block's row planes and the next stage's recursion planes are in flight ahead of their use.
+        const long win_bytes = (long)std::min(h->N + 1, 4) * h->Bp * h->spec.npt * 128; // (the window of a block of four stages: 32-bit offsets)
+        if ((h->wide_cap < 0 || phase != 0) && k.wide_hbm1 != nullptr && win_bytes < (1L << 32)) {
+            const size_t xbytes = (size_t)4 * k.ex_hbm * 128;
+            if (h->wide_hbm_cap == 0) {
+                const int nb = blocks_per_cu(k.wide_hbm1, qp_block, xbytes);
+                h->wide_hbm_cap = nb > 0 ? (long)std::min(nb, 4) * h->ncu : -1;
+                if (h->wide_hbm_cap > 0 && h->max_waves > 0) h->wide_hbm_cap = std::min(h->wide_hbm_cap, h->max_waves);
+            }
+            // default: an RTI solve while the batch fits the resident waves twice over, as with the planes in LDS (measured at 2 048 instances, N = 80 / 100:
+            // 1.2 - 1.3x the throughput mapping; at 4 096 the throughput mapping is ahead); the launches of a full SQP once (no queue there)
+            const long reach = (phase == 0 && h->dynamic_rows) ? 2 * h->wide_hbm_cap : h->wide_hbm_cap;
+            if (h->wide_hbm_cap > 0 && (h->wide_mode > 0 || (long)h->B <= reach)) {
+                long nw = (long)h->B;
+                int q0 = -1;
+                // (full SQP: one group per workgroup for the whole call - its multipliers persist in the group's planes)
+                if (h->dynamic_rows && phase == 0 && nw > h->wide_hbm_cap) { nw = h->wide_hbm_cap; q0 = (int)nw; }
+                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
+                hipLaunchKernelGGL(k.wide_hbm1, dim3((unsigned)nw), dim3(qp_block), xbytes, h->stream, h->ptrs, nw, phase, q0, 1);
+                h->last_wide = 1;
+                return 0;
+            }
+        }
+    }
+    // (the kernel's own static LDS - exchange area, parked constants - comes out of the same 160 KB)
+    long lds_static = 0;
+    if (k.qp_lds != nullptr) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, (const void *)k.qp_lds) == hipSuccess) lds_static = (long)fa.sharedSizeBytes;
+    }
+    const int rows_lds = (int)std::min<long>(4, (160L * 1024 - lds_static) / lds_inst);
+    bool use_lds = phase == 0 && h->lds_mode != 0 && k.qp_lds != nullptr && rows_lds >= 1 && h->ncu > 0;
+    // by default only while one round of workgroups covers the batch: measured on usv_model_pf_ca, N = 20 / K = 3, the solve
+    // of 512 instances takes 5.9 ms with the planes in LDS against 6.5 ms in HBM, at 1024 (two rounds) 7.5 against 7.1
+    if (use_lds && h->lds_mode < 0) use_lds = (long)h->B <= (long)rows_lds * h->ncu;
+    if (use_lds) {
+        const size_t bytes = (size_t)rows_lds * lds_inst;
+        if (h->lds_cap == 0) {
+            const int nb = blocks_per_cu(k.qp_lds, qp_block, bytes);
+            h->lds_cap = nb > 0 ? (long)nb * h->ncu : -1;
+        }
+        if (h->lds_cap > 0) {
+            long nw = ((long)h->B + rows_lds - 1) / rows_lds;
+            int q0 = -1;
+            if (h->dynamic_rows && nw > h->lds_cap) { nw = h->lds_cap; q0 = (int)(nw * rows_lds); }
+            if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
+            hipLaunchKernelGGL(k.qp_lds, dim3((unsigned)nw), dim3(qp_block), bytes, h->stream, h->ptrs, nw * rows_lds, phase, q0, rows_lds);
+            return 0;
+        }
+    }
+    long ng = qp_groups;
+    int q0 = -1;
+    if (h->dynamic_rows && phase == 0 && h->qp_cap == 0) {
+        const int nb = blocks_per_cu(k.qp, qp_block, 0);
+        h->qp_cap = (nb > 0 && h->ncu > 0) ? 4L * nb * h->ncu : -1;
+    }
+    // The aux plane in LDS (qp_ipm.hpp, AUXLDS): 4 rows x (N + 1) stages x at most ten values beside the kernel's static LDS - taken
+    // when it does not cost a resident wave (usv_model_pf_ca at N = 40, K = 10: 13.1 KB + 6.7 KB of the 20 KB a wave may have)
+    size_t aux_bytes = 0;
+    if (phase == 0 && k.qp_aux != nullptr && h->aux_lds && h->dynamic_rows && h->qp_cap > 0) {
+        aux_bytes = (size_t)4 * (h->N + 1) * (size_t)(h->spec.aux_dense4 + (h->kch > 0 ? 2 : 0) + 2 * h->nu) * sizeof(double);
+        if (h->aux_cap == 0) {
+            const long cap = 4L * blocks_per_cu(k.qp_aux, qp_block, aux_bytes) * h->ncu;
+            h->aux_cap = cap >= h->qp_cap ? cap : -1;
+        }
+        if (h->aux_cap < 0) aux_bytes = 0;
+    }
+    const qp_kernel_t kern = aux_bytes ? k.qp_aux : k.qp;
+    if (h->dynamic_rows && phase == 0) {
+        long cap = aux_bytes ? std::min(h->aux_cap, h->qp_cap) : h->qp_cap;
+        if (h->max_waves > 0 && 4L * h->max_waves < cap) cap = 4L * h->max_waves; // option "max_waves": fewer resident waves
+        if (cap > 0 && cap < qp_groups) { ng = cap; q0 = (int)ng; }
+    }
+    if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
+    // Hand-over of long runners (qp_ipm.hpp, QpIpm::suspend): a launch that refills from the queue ends with a few rows finishing
+    // instances of 30 - 50 iterations on an idling device; past "handover_iter" iterations those go to a follow-up launch on the
+    // latency mapping (one instance per wave over the same planes: 1.6x per pass for usv_model_pf_ca at N = 40).  Scheduling only.
+    bool hand = false;
+    size_t xbytes = (size_t)4 * k.ex_hbm * 128;
+    qp_resume_t kern_resume = k.resume;
+    int hand_it = 0;
+    if (phase == 0 && h->handover_iter != 0 && k.resume != nullptr && (long)std::min(h->N + 1, 4) * h->Bp * h->spec.npt * 128 < (1L << 32)) {
+        const size_t lbytes = (size_t)(h->N + 1) * (size_t)k.nplw * 128 + (size_t)4 * k.ex_lds * 128;
+        if (h->resume_cap == 0) {
+            // (planes in LDS when the horizon fits - option "handover_lds", default on -, else over the planes in HBM)
+            const int nb_lds = (h->handover_lds && h->ncu > 0) ? blocks_per_cu(k.resume_lds, qp_block, lbytes) : 0;
+            const int nb = nb_lds > 0 ? nb_lds : blocks_per_cu(k.resume, qp_block, xbytes);
+            h->resume_lds = nb_lds > 0;
+            h->resume_cap = (nb > 0 && h->ncu > 0) ? (long)std::min(nb, 4) * h->ncu : -1;
+        }
+        if (h->resume_lds) { kern_resume = k.resume_lds; xbytes = lbytes; }
+        if (h->resume_cap > 0 && !h->d_susp_list) {
+            if (dev_alloc(h, &h->d_susp_count, (size_t)usvmpc_handle::RING, true) || dev_alloc(h, &h->d_susp_list, (size_t)h->B, false) ||
+                dev_alloc(h, &h->d_susp_rec, (size_t)h->B * 4, false))
+                return USVMPC_E_HIP;
+        }
+        // default (-1): past 20 iterations when the follow-up works in LDS AND the batch is at most three times what the device holds at once
+        // (re-measured in round 6 under the default QP solver profile, whose solves are shorter - profiles/r06_handover_co.txt: with the
+        // follow-up kernel beside the launch -18 % per tick at 4 096 instances, -13 % at 8 192, -4 % at 16 384, 0 at 32 768, +1 % at
+        // 65 536; with it only behind the launch nothing is gained any more at any size), never when it would run over the planes in HBM (a
+        // loss: profiles/r05_handover.txt)
+        const bool small = h->qp_cap > 0 && (long)h->B <= 3 * h->qp_cap;
+        hand_it = h->handover_iter > 0 ? h->handover_iter : ((h->resume_lds && small) ? 20 : 0);
+        hand = h->resume_cap > 0 && hand_it > 0;
+    }
+    h->ptrs.susp_count = hand ? h->d_susp_count + h->nsolves % usvmpc_handle::RING : nullptr;
+    h->ptrs.susp_list = hand ? h->d_susp_list : nullptr;
+    h->ptrs.susp_rec = hand ? h->d_susp_rec : nullptr;
+    h->ptrs.handover_iter = hand ? hand_it : 0;
+    const dim3 qg((unsigned)((ng * LANES + qp_block - 1) / qp_block)), qb(qp_block);
+    // The follow-up kernel BESIDE the draining launch (usv_qp_resume_co): on a stream of its own, eligible together with the main launch;
+    // what it does not get to is done by the follow-up launch behind the main one.  With the planes copied into LDS only (the form that pays).
+    const bool co = hand && h->handover_co != 0 && h->resume_lds && k.resume_co != nullptr && h->own_stream && co_prepare(h);
+    if (co) {
+        HIP_TRY(h, set_dynamic_lds((const void *)k.resume_co, xbytes));
+        h->ptrs.co_ctl = h->d_co_ctl + 8 * (h->nsolves % usvmpc_handle::RING);
+        HIP_TRY(h, hipMemsetAsync(h->ptrs.co_ctl, 0, 8 * sizeof(int), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->d_susp_list, 0xff, (size_t)h->B * sizeof(int), h->stream)); // (-1: no entry yet)
+        HIP_TRY(h, hipEventRecord(h->ev_co_pre, h->stream));
+    }
+    hipLaunchKernelGGL(kern, qg, qb, aux_bytes, h->stream, h->ptrs, ng, phase, q0, 4);
+    if (co) {
+        hipLaunchKernelGGL(usv_co_done, dim3(1), dim3(1), 0, h->stream, h->ptrs.co_ctl);
+        HIP_TRY(h, hipStreamWaitEvent(h->co_stream, h->ev_co_pre, 0));
+        // One follow-up workgroup per CU unless the caller asks otherwise (option "handover_co_wgs"): what finds room BESIDE the main launch's
+        // workgroups at once (75 KB of LDS next to their eight times 10 KB).  With two per CU - what fits once the main launch has left - some
+        // of them wait to be placed while the main launch runs, and about one tick in 1 500 then stalled until their waits ran out: the main
+        // launch took 410 ms instead of 9 (tools/co_soak.py, docs/rounds/r06.md section 8: 0 stalls in 16 000 ticks with one per CU, same pace).
+        long nco = std::min<long>(h->resume_cap, (long)h->B);
+        nco = std::min<long>(nco, h->co_wgs > 0 ? (long)h->co_wgs : (long)std::max(h->ncu, 1));
+        hipLaunchKernelGGL(k.resume_co, dim3((unsigned)nco), dim3(qp_block), xbytes, h->co_stream, h->ptrs, (int)qg.x, (int)h->B, h->co_spin_limit);
+        HIP_TRY(h, hipEventRecord(h->ev_co_end, h->co_stream));
+    }
+    if (hand) {
+        HIP_TRY(h, hipEventRecord(ev[3], h->stream));
+        h->ev3_set[h->nsolves % usvmpc_handle::RING] = true;
+        const long nwg = std::min<long>(h->resume_cap, (long)h->B);
+        hipLaunchKernelGGL(kern_resume, dim3((unsigned)nwg), dim3(qp_block), xbytes, h->stream, h->ptrs);
+    }
+    if (co) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_co_end, 0)); // (the tick's QPs are solved when both kernels are through)
+    return 0;
+}
+
+// One solve's launches on the handle's stream: sort, lineariser (pipelined: see usvmpc_handle), the QP (launch_qp, or the partially
+// condensed QP: launch_cond), the count of unconverged QPs and the copy of the results into the host mirror.
+int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
 {
     {   // pending host writes go up first; the results come back below
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
     }
     const long lin_groups = (long)(h->N + 1) * h->Bp;
-    const long qp_groups = h->Bp;
-    const int lin_block = 256, qp_block = 64;
+    const int lin_block = 256;
     const long lin_grid = (lin_groups * LANES + lin_block - 1) / lin_block;
     hipEvent_t *ev = h->ev[h->nsolves % usvmpc_handle::RING];
     const int B = h->B;
@@ -802,13 +1153,7 @@ int launch_pair(usvmpc_handle *h, int phase)
         hipLaunchKernelGGL(usv_sort_scan, dim3(1), dim3(64), 0, h->stream, h->d_hist, h->d_cursor);
         hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst);
     };
-    auto lin_launch = [&](auto mode, hipStream_t st, const DevPtrs &P) {
-        constexpr int MODE = decltype(mode)::value;
-        if (h->spec.sim_steps > 1)
-            hipLaunchKernelGGL((usv_linearize<M, KCH, SOFT, true, MODE>), dim3((unsigned)lin_grid), dim3(lin_block), 0, st, P, lin_groups);
-        else
-            hipLaunchKernelGGL((usv_linearize<M, KCH, SOFT, false, MODE>), dim3((unsigned)lin_grid), dim3(lin_block), 0, st, P, lin_groups);
-    };
+    const group_kernel_t *lin = k.lin[h->spec.sim_steps > 1 ? 1 : 0]; // [MODE]
     // Pipelined lineariser (see usvmpc_handle): RTI solves of large handles
     const bool cond = phase == 0 && h->cond_N2 > 0; // RTI solve on the partially condensed QP (cond_ipm.hpp)
     const bool pipe = phase == 0 && h->pipeline && !h->mirror && !h->extern_access && h->dynamic_rows && h->B >= 16384 && !cond;
@@ -857,8 +1202,8 @@ int launch_pair(usvmpc_handle *h, int phase)
     h->ptrs.tick = (int)h->nsolves;
     h->ev3_set[h->nsolves % usvmpc_handle::RING] = false;
     HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    if (use_spec) lin_launch(std::integral_constant<int, 2>{}, h->stream, h->ptrs); // only what the speculative pass had to skip
-    else lin_launch(std::integral_constant<int, 0>{}, h->stream, h->ptrs);
+    // (MODE 2: only what the speculative pass had to skip)
+    hipLaunchKernelGGL(lin[use_spec ? 2 : 0], dim3((unsigned)lin_grid), dim3(lin_block), 0, h->stream, h->ptrs, lin_groups);
     HIP_TRY(h, hipGetLastError());
     if (pipe) HIP_TRY(h, hipMemsetAsync(h->d_redo, 0, (size_t)B * ((h->N + 32) / 32) * sizeof(int), h->stream));
     HIP_TRY(h, hipEventRecord(ev[1], h->stream));
@@ -881,307 +1226,12 @@ int launch_pair(usvmpc_handle *h, int phase)
     // the pair (qp_iter, d_iter_prev), the pipelined map's included, and before the QP launch overwrites qp_iter)
     if (h->sort_enabled && h->sort_two && phase == 0)
         HIP_TRY(h, hipMemcpyAsync(h->d_iter_prev, h->ptrs.qp_iter, (size_t)h->B * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    constexpr bool CANPACK = KCH > 0;
-    const bool pack = CANPACK && h->spec.boxpack != 0;
-    if (h->spec.npt != (h->spec.any_bsoft ? WsLayout<M, KCH, SOFT, true>::NPT : WsLayout<M, KCH, SOFT, false>::NPT)) {
+    if (h->spec.npt != (h->spec.any_bsoft ? k.npt_soft : k.npt_hard)) {
         h->err = "workspace layout mismatch between host and kernels";
         return USVMPC_E_ARG;
     }
-    // An RTI solve is ONE launch of as many waves as the device holds at once; their rows start on the first groups and
-    // pull the remaining ones from a queue as they finish (qp_ipm.hpp).  The full SQP keeps one group per row: its later
-    // iterations find their multipliers in the group's part of the workspace.
-    // Small batches: the planes of every instance in flight fit in LDS (160 KB per CU), and a solve whose sweeps wait for
-    // HBM at every stage - nothing else runs on the CU to hide it - becomes a solve on LDS.  rows_lds instances per wave
-    // (as many whole horizons as fit), one wave per CU at a time; further instances come through the same queue.
-    auto launch_qp = [&](auto kern, decltype(kern) kern_lds, decltype(kern) kern_aux = nullptr, WideSet wide = NO_WIDE) -> int {
-        const long lds_inst = (long)(h->N + 1) * h->spec.npt * 128;
-        h->last_wide = 0;
-        h->ptrs.susp_count = nullptr; h->ptrs.susp_list = nullptr; h->ptrs.susp_rec = nullptr; h->ptrs.handover_iter = 0; h->ptrs.co_ctl = nullptr; // (set by the path that hands over)
-        const qp_kernel_t kern_wide = wide.lds1, kern_wide_hbm = wide.hbm1;
-        // Four waves per instance (qp_ipm.hpp, WW): a workgroup = a whole CU shares out the row work of 16 consecutive stages - for the
-        // single instance and batches of at most one instance per CU.
-        if (wide.lds4 != nullptr && phase == 0 && h->wide_mode != 0 && h->wide_waves != 1 && h->ncu > 0) {
-            const size_t pl = (size_t)(h->N + 1) * (size_t)wide.nplw * 128;
-            const size_t b4 = pl + (size_t)16 * wide.ex_lds * 128 + 128, x4 = (size_t)16 * wide.ex_hbm * 128 + 128;
-            const long win_bytes = (long)std::min(h->N + 1, 16) * h->Bp * h->spec.npt * 128; // (the window of a block of 16 stages: 32-bit offsets)
-            if (h->wide4_cap == 0) {
-                int nb = 0;
-                hipFuncAttributes fa;
-                if (b4 <= 160u * 1024u && hipFuncGetAttributes(&fa, (const void *)wide.lds4) == hipSuccess && fa.sharedSizeBytes + b4 <= 160u * 1024u &&
-                    hipFuncSetAttribute((const void *)wide.lds4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b4) == hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wide.lds4, 4 * qp_block, b4) == hipSuccess && nb > 0)
-                    h->wide4_cap = (long)h->ncu;
-                else
-                    h->wide4_cap = -1;
-            }
-            if (h->wide4_cap < 0 && h->wide4_hbm_cap == 0) {
-                int nb = 0;
-                h->wide4_hbm_cap = (wide.hbm4 != nullptr && win_bytes < (1L << 32) &&
-                                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wide.hbm4, 4 * qp_block, x4) == hipSuccess && nb > 0) ? (long)h->ncu : -1;
-            }
-            const bool lds = h->wide4_cap > 0;
-            long cap = lds ? h->wide4_cap : h->wide4_hbm_cap;
-            if (cap > 0 && h->max_waves > 0) cap = std::max<long>(1, std::min(cap, h->max_waves / 4)); // option "max_waves" counts wavefronts
-            // default: where the row work is the larger share - the soft-row OCPs and two obstacle chunks (measured, one instance / 256 instances
-            // per tick: usv_model_guidance_ca1 N = 100 / K = 8 1.78 -> 1.59 / 5.6 -> 5.0 ms, N = 40 / K = 10 0.94 -> 0.86 / 2.05 -> 1.87, N = 80 / K = 20
-            // 4.00 -> 3.00 / 8.1 -> 6.2; usv_model_pf_ca N = 80 / K = 20 6.95 -> 6.22 / 10.4 -> 9.6, with ONE chunk of hard rows 0 - 7 % SLOWER: there
-            // the recursion dominates and pays the barriers)
-            // Up to one instance per CU; with the queue and a horizon of 40 or more up to two (tools/latency_probe.py over 13 shapes x 7 batch sizes,
-            // profiles/r05_f_policy_audit.txt: 512 instances 6 - 8 % under one wave each; at N = 20 the second round costs more than the row work saves)
-            const long reach = (h->dynamic_rows && h->N >= 40) ? 2 * cap : cap;
-            // (round 6, profiles/r06_b_policy_audit.txt: ONE chunk of hard rows also gains 2 - 4 % from four waves when the rows are many and the
-            // horizon long - usv_model_pf_ca N = 40 / K = 10: one instance 2.50 -> 2.40 ms, 64: 5.84 -> 5.63, 256: 4.03 -> 3.94; N = 100 / K = 8,
-            // 64: 9.62 -> 9.34; with K = 3 or 4 it loses - up to one instance per CU)
-            const bool hard_many = !SOFT && KCH == 1 && h->K >= 8 && h->N >= 40 && (long)h->B <= cap;
-            if (cap > 0 && (h->wide_waves == 4 || ((SOFT || KCH == 2) && (long)h->B <= reach) || hard_many)) {
-                long nw = (long)h->B;
-                int q0 = -1;
-                if (h->dynamic_rows && nw > cap) { nw = cap; q0 = (int)nw; }
-                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-                hipLaunchKernelGGL(lds ? wide.lds4 : wide.hbm4, dim3((unsigned)nw), dim3(4 * qp_block), lds ? b4 : x4, h->stream, h->ptrs, nw, phase, q0, 1);
-                h->last_wide = 4;
-                return 0;
-            }
-        }
-        // The latency mapping: ONE instance per wave (qp_ipm.hpp, WIDE) - planes in LDS, the four rows share out the stage-local row
-        // work.  A wave then finishes an instance 1.4x (hard rows) to 1.8x (soft rows) sooner and the device holds a quarter of the instances at once: it pays while
-        // the batch leaves SIMDs idle anyway (a solve of the batch then lasts as long as its hardest instance on a lone wave).
-        if (kern_wide != nullptr && h->wide_mode != 0 && h->ncu > 0) {
-          if (phase == 0) { // (the launches of a full SQP find their multipliers in the group's planes in HBM: the variant over planes in HBM below)
-            // (in LDS: the planes the solve writes - WsLayout's up to L_zu less the four box planes the packed layouts leave unused)
-            const size_t bytes = (size_t)(h->N + 1) * (size_t)wide.nplw * 128 + (size_t)4 * wide.ex_lds * 128;
-            if (h->wide_cap == 0) {
-                int nb = 0;
-                hipFuncAttributes fa;
-                if (bytes <= 160u * 1024u && hipFuncGetAttributes(&fa, (const void *)kern_wide) == hipSuccess && fa.sharedSizeBytes + bytes <= 160u * 1024u &&
-                    hipFuncSetAttribute((const void *)kern_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern_wide, qp_block, bytes) == hipSuccess && nb > 0)
-                    h->wide_cap = (long)std::min(nb, 4) * h->ncu;   // (one wave per SIMD at most: the point is a lone wave's issue rate)
-                else
-                    h->wide_cap = -1;
-                if (h->wide_cap > 0 && h->max_waves > 0) h->wide_cap = std::min(h->wide_cap, h->max_waves); // option "max_waves"
-            }
-            // default: while the batch fits the SIMDs twice over (the queue hands the second half to the waves that finish first)
-            const bool take = h->wide_cap > 0 && (h->wide_mode > 0 || (long)h->B <= 2 * h->wide_cap);
-            if (take) {
-                long nw = (long)h->B;
-                int q0 = -1;
-                if (h->dynamic_rows && nw > h->wide_cap) { nw = h->wide_cap; q0 = (int)nw; }
-                if (!h->dynamic_rows && nw > h->wide_cap) { /* without the queue every instance needs its wave at launch: still correct, later workgroups wait */ }
-                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-                hipLaunchKernelGGL(kern_wide, dim3((unsigned)nw), dim3(qp_block), bytes, h->stream, h->ptrs, nw, phase, q0, 1);
-                h->last_wide = 1;
-                return 0;
-            }
-          }
-            // The horizon's planes do not fit a CU's LDS (the reference node's own N = 100: nmpc_guidance_ca1.cpp:64), or the launch belongs to a
-            // full SQP: the same sweeps over the planes in HBM / L2 - the four rows of a wave address the four stages of a block through one
-            // window, the next block's row planes and the next stage's recursion planes are in flight ahead of their use.
-            const long win_bytes = (long)std::min(h->N + 1, 4) * h->Bp * h->spec.npt * 128; // (the window of a block of four stages: 32-bit offsets)
-            if ((h->wide_cap < 0 || phase != 0) && kern_wide_hbm != nullptr && win_bytes < (1L << 32)) {
-                const size_t xbytes = (size_t)4 * wide.ex_hbm * 128;
-                if (h->wide_hbm_cap == 0) {
-                    int nb = 0;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern_wide_hbm, qp_block, xbytes) == hipSuccess && nb > 0)
-                        h->wide_hbm_cap = (long)std::min(nb, 4) * h->ncu;
-                    else
-                        h->wide_hbm_cap = -1;
-                    if (h->wide_hbm_cap > 0 && h->max_waves > 0) h->wide_hbm_cap = std::min(h->wide_hbm_cap, h->max_waves);
-                }
-                // default: an RTI solve while the batch fits the resident waves twice over, as with the planes in LDS (measured at 2 048 instances, N = 80 / 100:
-                // 1.2 - 1.3x the throughput mapping; at 4 096 the throughput mapping is ahead); the launches of a full SQP once (no queue there)
-                const long reach = (phase == 0 && h->dynamic_rows) ? 2 * h->wide_hbm_cap : h->wide_hbm_cap;
-                if (h->wide_hbm_cap > 0 && (h->wide_mode > 0 || (long)h->B <= reach)) {
-                    long nw = (long)h->B;
-                    int q0 = -1;
-                    // (full SQP: one group per workgroup for the whole call - its multipliers persist in the group's planes)
-                    if (h->dynamic_rows && phase == 0 && nw > h->wide_hbm_cap) { nw = h->wide_hbm_cap; q0 = (int)nw; }
-                    if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-                    hipLaunchKernelGGL(kern_wide_hbm, dim3((unsigned)nw), dim3(qp_block), xbytes, h->stream, h->ptrs, nw, phase, q0, 1);
-                    h->last_wide = 1;
-                    return 0;
-                }
-            }
-        }
-        // (the kernel's own static LDS - exchange area, parked constants - comes out of the same 160 KB)
-        long lds_static = 0;
-        if (kern_lds != nullptr) {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, (const void *)kern_lds) == hipSuccess) lds_static = (long)fa.sharedSizeBytes;
-        }
-        const int rows_lds = (int)std::min<long>(4, (160L * 1024 - lds_static) / lds_inst);
-        bool use_lds = phase == 0 && h->lds_mode != 0 && kern_lds != nullptr && rows_lds >= 1 && h->ncu > 0;
-        // by default only while one round of workgroups covers the batch: measured on usv_model_pf_ca, N = 20 / K = 3, the solve
-        // of 512 instances takes 5.9 ms with the planes in LDS against 6.5 ms in HBM, at 1024 (two rounds) 7.5 against 7.1
-        if (use_lds && h->lds_mode < 0) use_lds = (long)h->B <= (long)rows_lds * h->ncu;
-        if (use_lds) {
-            const size_t bytes = (size_t)rows_lds * lds_inst;
-            if (h->lds_cap == 0) {
-                int nb = 0;
-                if (hipFuncSetAttribute((const void *)kern_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern_lds, qp_block, bytes) == hipSuccess && nb > 0)
-                    h->lds_cap = (long)nb * h->ncu;
-                else
-                    h->lds_cap = -1;
-            }
-            if (h->lds_cap > 0) {
-                long nw = ((long)h->B + rows_lds - 1) / rows_lds;
-                int q0 = -1;
-                if (h->dynamic_rows && nw > h->lds_cap) { nw = h->lds_cap; q0 = (int)(nw * rows_lds); }
-                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-                hipLaunchKernelGGL(kern_lds, dim3((unsigned)nw), dim3(qp_block), bytes, h->stream, h->ptrs, nw * rows_lds, phase, q0, rows_lds);
-                return 0;
-            }
-        }
-        long ng = qp_groups;
-        int q0 = -1;
-        if (h->dynamic_rows && phase == 0 && h->qp_cap == 0) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, qp_block, 0) == hipSuccess && nb > 0 && h->ncu > 0)
-                h->qp_cap = 4L * nb * h->ncu;
-            else
-                h->qp_cap = -1;
-        }
-        // The aux plane in LDS (qp_ipm.hpp, AUXLDS): 4 rows x (N + 1) stages x at most ten values beside the kernel's static LDS - taken
-        // when it does not cost a resident wave (usv_model_pf_ca at N = 40, K = 10: 13.1 KB + 6.7 KB of the 20 KB a wave may have)
-        size_t aux_bytes = 0;
-        if (phase == 0 && kern_aux != nullptr && h->aux_lds && h->dynamic_rows && h->qp_cap > 0) {
-            aux_bytes = (size_t)4 * (h->N + 1) * (size_t)(h->spec.aux_dense4 + (h->kch > 0 ? 2 : 0) + 2 * h->nu) * sizeof(double);
-            if (h->aux_cap == 0) {
-                int nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern_aux, qp_block, aux_bytes) == hipSuccess && 4L * nb * h->ncu >= h->qp_cap)
-                    h->aux_cap = 4L * nb * h->ncu;
-                else
-                    h->aux_cap = -1;
-            }
-            if (h->aux_cap < 0) aux_bytes = 0;
-        }
-        if (aux_bytes) kern = kern_aux;
-        if (h->dynamic_rows && phase == 0) {
-            long cap = aux_bytes ? std::min(h->aux_cap, h->qp_cap) : h->qp_cap;
-            if (h->max_waves > 0 && 4L * h->max_waves < cap) cap = 4L * h->max_waves; // option "max_waves": fewer resident waves
-            if (cap > 0 && cap < qp_groups) { ng = cap; q0 = (int)ng; }
-        }
-        if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-        // Hand-over of long runners (qp_ipm.hpp, QpIpm::suspend): a launch that refills from the queue ends with a few rows finishing
-        // instances of 30 - 50 iterations on an idling device; past "handover_iter" iterations those go to a follow-up launch on the
-        // latency mapping (one instance per wave over the same planes: 1.6x per pass for usv_model_pf_ca at N = 40).  Scheduling only.
-        bool hand = false;
-        size_t xbytes = (size_t)4 * wide.ex_hbm * 128;
-        qp_resume_t kern_resume = wide.resume;
-        int hand_it = 0;
-        if (phase == 0 && h->handover_iter != 0 && wide.resume != nullptr && (long)std::min(h->N + 1, 4) * h->Bp * h->spec.npt * 128 < (1L << 32)) {
-            if (h->resume_cap == 0) {
-                // (planes in LDS when the horizon fits - option "handover_lds", default on -, else over the planes in HBM)
-                int nb = 0;
-                hipFuncAttributes fa;
-                const size_t lbytes = (size_t)(h->N + 1) * (size_t)wide.nplw * 128 + (size_t)4 * wide.ex_lds * 128;
-                h->resume_lds = false;
-                if (h->handover_lds && wide.resume_lds != nullptr && lbytes <= 160u * 1024u && hipFuncGetAttributes(&fa, (const void *)wide.resume_lds) == hipSuccess &&
-                    fa.sharedSizeBytes + lbytes <= 160u * 1024u &&
-                    hipFuncSetAttribute((const void *)wide.resume_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lbytes) == hipSuccess &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wide.resume_lds, qp_block, lbytes) == hipSuccess && nb > 0 && h->ncu > 0) {
-                    h->resume_cap = (long)std::min(nb, 4) * h->ncu;
-                    h->resume_lds = true;
-                } else {
-                    h->resume_cap = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wide.resume, qp_block, xbytes) == hipSuccess && nb > 0 && h->ncu > 0)
-                                        ? (long)std::min(nb, 4) * h->ncu : -1;
-                }
-            }
-            if (h->resume_lds) { kern_resume = wide.resume_lds; xbytes = (size_t)(h->N + 1) * (size_t)wide.nplw * 128 + (size_t)4 * wide.ex_lds * 128; }
-            if (h->resume_cap > 0 && !h->d_susp_list) {
-                if (dev_alloc(h, &h->d_susp_count, (size_t)usvmpc_handle::RING, true) || dev_alloc(h, &h->d_susp_list, (size_t)h->B, false) ||
-                    dev_alloc(h, &h->d_susp_rec, (size_t)h->B * 4, false))
-                    return USVMPC_E_HIP;
-            }
-            // default (-1): past 20 iterations when the follow-up works in LDS AND the batch is at most three times what the device holds at once
-            // (re-measured in round 6 under the default QP solver profile, whose solves are shorter - profiles/r06_handover_co.txt: with the
-            // follow-up kernel beside the launch -18 % per tick at 4 096 instances, -13 % at 8 192, -4 % at 16 384, 0 at 32 768, +1 % at
-            // 65 536; with it only behind the launch nothing is gained any more at any size), never when it would run over the planes in HBM (a
-            // loss: profiles/r05_handover.txt)
-            const bool small = h->qp_cap > 0 && (long)h->B <= 3 * h->qp_cap;
-            hand_it = h->handover_iter > 0 ? h->handover_iter : ((h->resume_lds && small) ? 20 : 0);
-            hand = h->resume_cap > 0 && hand_it > 0;
-        }
-        h->ptrs.susp_count = hand ? h->d_susp_count + h->nsolves % usvmpc_handle::RING : nullptr;
-        h->ptrs.susp_list = hand ? h->d_susp_list : nullptr;
-        h->ptrs.susp_rec = hand ? h->d_susp_rec : nullptr;
-        h->ptrs.handover_iter = hand ? hand_it : 0;
-        const dim3 qg((unsigned)((ng * LANES + qp_block - 1) / qp_block)), qb(qp_block);
-        // The follow-up kernel BESIDE the draining launch (usv_qp_resume_co): on a stream of its own, eligible together with the main launch;
-        // what it does not get to is done by the follow-up launch behind the main one.  With the planes copied into LDS only (the form that pays).
-        const bool co = hand && h->handover_co != 0 && h->resume_lds && wide.resume_co != nullptr && h->own_stream;
-        h->ptrs.co_ctl = nullptr;
-        if (co) {
-            if (!h->co_stream) {
-                int prio_least = 0, prio_greatest = 0;
-                HIP_TRY(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-                HIP_TRY(h, hipStreamCreateWithPriority(&h->co_stream, hipStreamNonBlocking, prio_least));
-                HIP_TRY(h, hipEventCreateWithFlags(&h->ev_co_pre, hipEventDisableTiming));
-                HIP_TRY(h, hipEventCreateWithFlags(&h->ev_co_end, hipEventDisableTiming));
-                if (dev_alloc(h, &h->d_co_ctl, (size_t)usvmpc_handle::RING * 8, true)) return USVMPC_E_HIP;
-            }
-            HIP_TRY(h, hipFuncSetAttribute((const void *)wide.resume_co, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xbytes)); // (per kernel, not per handle: handles differ in horizon)
-            h->ptrs.co_ctl = h->d_co_ctl + 8 * (h->nsolves % usvmpc_handle::RING);
-            HIP_TRY(h, hipMemsetAsync(h->ptrs.co_ctl, 0, 8 * sizeof(int), h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->d_susp_list, 0xff, (size_t)h->B * sizeof(int), h->stream)); // (-1: no entry yet)
-            HIP_TRY(h, hipEventRecord(h->ev_co_pre, h->stream));
-        }
-        hipLaunchKernelGGL(kern, qg, qb, aux_bytes, h->stream, h->ptrs, ng, phase, q0, 4);
-        if (co) {
-            hipLaunchKernelGGL(usv_co_done, dim3(1), dim3(1), 0, h->stream, h->ptrs.co_ctl);
-            HIP_TRY(h, hipStreamWaitEvent(h->co_stream, h->ev_co_pre, 0));
-            // One follow-up workgroup per CU unless the caller asks otherwise (option "handover_co_wgs"): what finds room BESIDE the main launch's
-            // workgroups at once (75 KB of LDS next to their eight times 10 KB).  With two per CU - what fits once the main launch has left - some
-            // of them wait to be placed while the main launch runs, and about one tick in 1 500 then stalled until their waits ran out: the main
-            // launch took 410 ms instead of 9 (tools/co_soak.py, docs/rounds/r06.md section 8: 0 stalls in 16 000 ticks with one per CU, same pace).
-            long nco = std::min<long>(h->resume_cap, (long)h->B);
-            nco = std::min<long>(nco, h->co_wgs > 0 ? (long)h->co_wgs : (long)std::max(h->ncu, 1));
-            hipLaunchKernelGGL(wide.resume_co, dim3((unsigned)nco), dim3(qp_block), xbytes, h->co_stream, h->ptrs, (int)qg.x, (int)h->B, h->co_spin_limit);
-            HIP_TRY(h, hipEventRecord(h->ev_co_end, h->co_stream));
-        }
-        if (hand) {
-            HIP_TRY(h, hipEventRecord(ev[3], h->stream));
-            h->ev3_set[h->nsolves % usvmpc_handle::RING] = true;
-            const long nwg = std::min<long>(h->resume_cap, (long)h->B);
-            hipLaunchKernelGGL(kern_resume, dim3((unsigned)nwg), dim3(qp_block), xbytes, h->stream, h->ptrs);
-        }
-        if (co) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_co_end, 0)); // (the tick's QPs are solved when both kernels are through)
-        return 0;
-    };
-    int rcq = 0;
-    if (cond) {
-        rcq = launch_cond(h);
-    } else {
-#ifdef USV_BENCH_ONLY // development builds (tools/dev_build.sh): only the instantiation the bench workload runs
-    if (!(h->spec.hdiag && pack && !h->spec.any_bsoft)) { h->err = "development build: bench instantiation only"; return USVMPC_E_ARG; }
-    // (one row pass when every box row rides in a slot lane: qp_ipm.hpp, MERGE)
-    if (h->merge_rows && !h->spec.box_dense)
-        rcq = launch_qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true, CANPACK>,
-                        &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK, true>, wide_set<M, KCH, SOFT, CANPACK>());
-    else
-        rcq = launch_qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true>,
-                        &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, false, true>);
-#else
-    if (h->spec.any_bsoft) { // soft state bounds: rows with slacks, ten planes of their own
-        rcq = h->spec.hdiag ? launch_qp(&usv_qp_rti<M, KCH, SOFT, true, false, true>, nullptr, nullptr, wide_set<M, KCH, SOFT, false, true>())
-                            : launch_qp(&usv_qp_rti<M, KCH, SOFT, false, false, true>, nullptr);
-    } else if (h->spec.hdiag) { // (every OCP of the reference: the only instantiations that also come with the workspace in LDS)
-        // (one row pass when every box row rides in a slot lane: qp_ipm.hpp, MERGE)
-        // (the packed layouts - every OCP of the reference, the bench workloads - also come with the aux plane in LDS)
-        if (pack && h->merge_rows && !h->spec.box_dense)
-            rcq = launch_qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true, CANPACK>,
-                            &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK, true>, wide_set<M, KCH, SOFT, CANPACK>());
-        else
-            rcq = pack ? launch_qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true>,
-                                   &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, false, true>, wide_set<M, KCH, SOFT, false>())
-                       : launch_qp(&usv_qp_rti<M, KCH, SOFT, true, false, false>, &usv_qp_rti<M, KCH, SOFT, true, false, false, true>, nullptr,
-                                   wide_set<M, KCH, SOFT, false, false, true>());   // (box rows in planes of their own)
-    } else {
-        rcq = pack ? launch_qp(&usv_qp_rti<M, KCH, SOFT, false, CANPACK, false>, nullptr) : launch_qp(&usv_qp_rti<M, KCH, SOFT, false, false, false>, nullptr);
-    }
-#endif
-    }
+    if (!cond && k.qp == nullptr) { h->err = "development build: bench instantiation only"; return USVMPC_E_ARG; }
+    const int rcq = cond ? launch_cond(h) : launch_qp(h, k, phase);
     if (rcq) return rcq;
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(ev[2], h->stream));
@@ -1198,7 +1248,7 @@ int launch_pair(usvmpc_handle *h, int phase)
         DevPtrs Pn = h->ptrs;
         Pn.perm = next_perm;
         Pn.perm_cur = h->ptrs.perm;
-        lin_launch(std::integral_constant<int, 1>{}, h->aux_stream, Pn);
+        hipLaunchKernelGGL(lin[1], dim3((unsigned)lin_grid), dim3(lin_block), 0, h->aux_stream, Pn, lin_groups);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->ev_spec, h->aux_stream));
         h->spec_for = h->nsolves + 1;
@@ -1217,59 +1267,6 @@ int launch_pair(usvmpc_handle *h, int phase)
     return 0;
 }
 
-// ---- multiplier read-back: buffers on first use, one kernel per solve they are asked for
-template <class M, int KCH, bool SOFT>
-int export_pair(usvmpc_handle *h)
-{
-    constexpr bool CANPACK = KCH > 0;
-    const bool pack = CANPACK && h->spec.boxpack != 0;
-    const dim3 grid((unsigned)((h->Bp + 3) / 4)), block(64);
-    if (h->spec.any_bsoft) hipLaunchKernelGGL((usv_qp_export<M, KCH, SOFT, false, true>), grid, block, 0, h->stream, h->ptrs, (long)h->Bp);
-    else if (pack) hipLaunchKernelGGL((usv_qp_export<M, KCH, SOFT, CANPACK, false>), grid, block, 0, h->stream, h->ptrs, (long)h->Bp);
-    else hipLaunchKernelGGL((usv_qp_export<M, KCH, SOFT, false, false>), grid, block, 0, h->stream, h->ptrs, (long)h->Bp);
-    HIP_TRY(h, hipGetLastError());
-    return 0;
-}
-
-// The instantiations of the stock library, one per build part
-#if USV_PART >= 0 && !defined(USV_GEN_ONLY)
-#if USV_PART == 1
-#define USV_PAIR_1(M, KCH, SOFT) template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#else
-#define USV_PAIR_1(M, KCH, SOFT) extern template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); extern template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#endif
-#if USV_PART == 2
-#define USV_PAIR_2(M, KCH, SOFT) template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#else
-#define USV_PAIR_2(M, KCH, SOFT) extern template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); extern template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#endif
-#if USV_PART == 3
-#define USV_PAIR_3(M, KCH, SOFT) template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#else
-#define USV_PAIR_3(M, KCH, SOFT) extern template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); extern template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#endif
-#if USV_PART == 4
-#define USV_PAIR_4(M, KCH, SOFT) template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#else
-#define USV_PAIR_4(M, KCH, SOFT) extern template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); extern template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#endif
-#if USV_PART == 5
-#define USV_PAIR_5(M, KCH, SOFT) template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#else
-#define USV_PAIR_5(M, KCH, SOFT) extern template int launch_pair<M, KCH, SOFT>(usvmpc_handle *, int); extern template int export_pair<M, KCH, SOFT>(usvmpc_handle *);
-#endif
-#ifndef USV_BENCH_ONLY
-USV_PAIR_1(ModelM0, 0, false)
-USV_PAIR_3(ModelM1, 2, true)
-USV_PAIR_5(ModelM2, 2, false)
-#endif
-USV_PAIR_2(ModelM1, 1, true)
-USV_PAIR_4(ModelM2, 1, false)
-#endif
-
-#if USV_MAIN
-namespace {
-
 // planes per stage of the packed [B A] for this model (MatPack)
 int model_mat_planes(int model)
 {
@@ -1286,27 +1283,33 @@ int model_mat_planes(int model)
     return 0;
 }
 
-int launch(usvmpc_handle *h, int phase = 0)
+// the kernel table of the handle's model in this library (false: none)
+bool model_kernels(const usvmpc_handle *h, Kernels &k)
 {
     switch (h->desc.model) {
 #ifdef USV_BENCH_ONLY
-    case USVMPC_MODEL_PF_CA: if (h->kch <= 1) return launch_pair<ModelM2, 1, false>(h, phase); break;
-    case USVMPC_MODEL_GUIDANCE_CA1: if (h->kch <= 1) return launch_pair<ModelM1, 1, true>(h, phase); break;
+    case USVMPC_MODEL_PF_CA: if (h->kch <= 1) { k = kernels_for<ModelM2, 1, false>(h); return true; } break;
+    case USVMPC_MODEL_GUIDANCE_CA1: if (h->kch <= 1) { k = kernels_for<ModelM1, 1, true>(h); return true; } break;
 #elif !defined(USV_GEN_ONLY)
-    case USVMPC_MODEL_USV: return launch_pair<ModelM0, 0, false>(h, phase);
-    case USVMPC_MODEL_GUIDANCE_CA1:
-        return h->kch <= 1 ? launch_pair<ModelM1, 1, true>(h, phase) : launch_pair<ModelM1, 2, true>(h, phase);
-    case USVMPC_MODEL_PF_CA:
-        return h->kch <= 1 ? launch_pair<ModelM2, 1, false>(h, phase) : launch_pair<ModelM2, 2, false>(h, phase);
+    case USVMPC_MODEL_USV: k = kernels_for<ModelM0, 0, false>(h); return true;
+    case USVMPC_MODEL_GUIDANCE_CA1: k = h->kch <= 1 ? kernels_for<ModelM1, 1, true>(h) : kernels_for<ModelM1, 2, true>(h); return true;
+    case USVMPC_MODEL_PF_CA: k = h->kch <= 1 ? kernels_for<ModelM2, 1, false>(h) : kernels_for<ModelM2, 2, false>(h); return true;
 #endif
 #if defined(USV_GEN_MODEL_HEADER) && !defined(USV_BENCH_ONLY)
-    case USVMPC_MODEL_GENERATED: return launch_pair<ModelGen, USV_GEN_KCH, (USV_GEN_SOFT != 0)>(h, phase);
+    case USVMPC_MODEL_GENERATED: k = kernels_for<ModelGen, USV_GEN_KCH, (USV_GEN_SOFT != 0)>(h); return true;
 #endif
     }
-    h->err = "unknown model";
-    return USVMPC_E_ARG;
+    return false;
 }
 
+int launch(usvmpc_handle *h, int phase = 0)
+{
+    Kernels k;
+    if (!model_kernels(h, k)) { h->err = "unknown model"; return USVMPC_E_ARG; }
+    return launch_solve(h, k, phase);
+}
+
+// ---- multiplier read-back: buffers on first use, one kernel per solve they are asked for
 int ensure_export(usvmpc_handle *h)
 {
     if (h->nsolves == 0) { h->err = "no QP has been solved yet: nothing to read back"; return USVMPC_E_ARG; }
@@ -1330,21 +1333,10 @@ int ensure_export(usvmpc_handle *h)
     const size_t nbytes = (size_t)h->B * (h->N + 1) * (size_t)(P.nlam > 0 ? P.nlam : 1) * sizeof(double);
     HIP_TRY(h, hipMemsetAsync(P.lam_out, 0, nbytes, h->stream));
     HIP_TRY(h, hipMemsetAsync(P.t_out, 0, nbytes, h->stream));
-    int rc = USVMPC_E_ARG;
-    switch (h->desc.model) {
-#ifdef USV_BENCH_ONLY
-    case USVMPC_MODEL_PF_CA: if (h->kch <= 1) rc = export_pair<ModelM2, 1, false>(h); break;
-    case USVMPC_MODEL_GUIDANCE_CA1: if (h->kch <= 1) rc = export_pair<ModelM1, 1, true>(h); break;
-#elif !defined(USV_GEN_ONLY)
-    case USVMPC_MODEL_USV: rc = export_pair<ModelM0, 0, false>(h); break;
-    case USVMPC_MODEL_GUIDANCE_CA1: rc = h->kch <= 1 ? export_pair<ModelM1, 1, true>(h) : export_pair<ModelM1, 2, true>(h); break;
-    case USVMPC_MODEL_PF_CA: rc = h->kch <= 1 ? export_pair<ModelM2, 1, false>(h) : export_pair<ModelM2, 2, false>(h); break;
-#endif
-#if defined(USV_GEN_MODEL_HEADER) && !defined(USV_BENCH_ONLY)
-    case USVMPC_MODEL_GENERATED: rc = export_pair<ModelGen, USV_GEN_KCH, (USV_GEN_SOFT != 0)>(h); break;
-#endif
-    }
-    if (rc) { if (rc == USVMPC_E_ARG) h->err = "multiplier read-back: no kernel for this model in this library"; return rc; }
+    Kernels k;
+    if (!model_kernels(h, k)) { h->err = "multiplier read-back: no kernel for this model in this library"; return USVMPC_E_ARG; }
+    hipLaunchKernelGGL(k.qp_export, dim3((unsigned)((h->Bp + 3) / 4)), dim3(64), 0, h->stream, h->ptrs, (long)h->Bp);
+    HIP_TRY(h, hipGetLastError());
     h->export_at = h->nsolves;
     return 0;
 }
@@ -1439,7 +1431,7 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->lds_cap = 0;
     h->wide_mode = -1; h->wide_cap = 0; h->wide_hbm_cap = 0; h->last_wide = 0;
     h->wide_waves = -1; h->wide4_cap = 0; h->wide4_hbm_cap = 0;
-    h->handover_co = -1; h->co_spin_limit = 200000; h->co_wgs = 0; h->co_stream = nullptr; h->ev_co_pre = nullptr; h->ev_co_end = nullptr; h->d_co_ctl = nullptr;
+    h->handover_co = -1; h->co_spin_limit = 200000; h->co_wgs = 0; h->co_ready = false; h->co_stream = nullptr; h->ev_co_pre = nullptr; h->ev_co_end = nullptr; h->d_co_ctl = nullptr;
     h->handover_iter = -1; for (bool &e : h->ev3_set) e = false; h->resume_lds = false; h->handover_lds = true; h->d_susp_count = nullptr; h->d_susp_list = nullptr; h->d_susp_rec = nullptr; h->resume_cap = 0;
     h->max_waves = 0;
     {
@@ -1543,19 +1535,15 @@ int usvmpc_destroy(usvmpc_handle *h)
     if (h->aux_stream) {
         (void)hipStreamSynchronize(h->aux_stream);
         (void)hipStreamDestroy(h->aux_stream);
-        (void)hipEventDestroy(h->ev_pre);
-        (void)hipEventDestroy(h->ev_spec);
     }
-    if (h->co_stream) {
-        (void)hipStreamSynchronize(h->co_stream);
-        (void)hipStreamDestroy(h->co_stream);
-        (void)hipEventDestroy(h->ev_co_pre);
-        (void)hipEventDestroy(h->ev_co_end);
-    }
+    if (h->ev_pre) (void)hipEventDestroy(h->ev_pre);
+    if (h->ev_spec) (void)hipEventDestroy(h->ev_spec);
+    co_release(h);
     for (void *a : h->allocs) (void)hipFree(a);
     if (h->mirror) (void)hipHostFree(h->mirror);
     for (int r = 0; r < usvmpc_handle::RING; r++)
-        for (int i = 0; i < 4; i++) (void)hipEventDestroy(h->ev[r][i]);
+        for (int i = 0; i < 4; i++)
+            if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
     if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return 0;
