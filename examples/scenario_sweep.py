@@ -3,9 +3,11 @@
 (obstacle simulator -> NMPC node callbacks / waypoint manager -> acados_solve -> published set-points,
 catkin_ws/src/simulation/scripts/obstacle_sim_node.py + catkin_ws/src/nmpc_ca/src/nmpc_guidance_ca1.cpp) run for B
 random obstacle fields at once.  As in the reference's own main.py the plant is the model prediction: the next
-pose / velocity are read from x_1 of the solution.
+pose / velocity are read from x_1 of the solution.  With --plant-steps K the plant is an integrator of its own instead
+(BatchSimSolver: the same model over the same 0.05 s in K RK4 steps, from x_0 under u_0), i.e. a plant that differs from
+the controller's one-step prediction by its discretisation error.
 
-    python examples/scenario_sweep.py --batch 4096 --ticks 300
+    python examples/scenario_sweep.py --batch 4096 --ticks 300 [--plant-steps 10]
 """
 import argparse
 import os
@@ -16,7 +18,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: F401,E402  (before the solver library: one HIP runtime for both)
-from mpc_collisionavoidance_amd import BatchOcpSolver, usv_models  # noqa: E402
+from mpc_collisionavoidance_amd import AcadosSim, BatchOcpSolver, BatchSimSolver, usv_models  # noqa: E402
 from mpc_collisionavoidance_amd.guidance import GuidanceFrontEnd  # noqa: E402
 
 
@@ -30,11 +32,17 @@ def make_worlds(B, L, rng):
     return np.stack([x, y, r], axis=2)
 
 
-def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False):
+def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None):
     rng = np.random.default_rng(seed)
     dt = 0.05
     ocp = usv_models.make_ocp("usv_model_guidance_ca1", N * dt, N, K)
     s = BatchOcpSolver(ocp, B)
+    plant = None
+    if plant_steps:
+        sim = AcadosSim()
+        sim.model = ocp.model
+        sim.solver_options.T, sim.solver_options.num_steps, sim.solver_options.sens_forw = dt, int(plant_steps), False
+        plant = BatchSimSolver(sim, B)
     fe = GuidanceFrontEnd(s)
     wps = np.array([[4.0, -5.0], [4.0, 25.0], [10.0, 30.0]])
     world = make_worlds(B, L, rng)
@@ -50,7 +58,13 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False):
         st = s.solve()                               # acados_solve()
         out = fe.publish()                           # desired heading / r / speed
         bad |= (st != 0) & (out["active"] != 0)
-        x1 = s.get("x", 1)
+        if plant is None:
+            x1 = s.get("x", 1)
+        else:
+            plant.set("x", s.get("x", 0))
+            plant.set("u", s.get("u", 0))
+            plant.solve()
+            x1 = plant.get("x")
         vel, pose = x1[:, 0:2].copy(), x1[:, 5:8].copy()
         d = np.sqrt((pose[:, None, 0] - world[:, :, 0]) ** 2 + (pose[:, None, 1] - world[:, :, 1]) ** 2) - (world[:, :, 2] + 0.5)
         min_clear = np.minimum(min_clear, d.min(axis=1))
@@ -64,6 +78,8 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False):
               % (min_clear.min(), np.percentile(min_clear, 1), np.median(min_clear)))
         print("scenarios with a solver failure: %d; reached the second leg: %d" % (bad.sum(), (k >= 2).sum()))
     s.close()
+    if plant is not None:
+        plant.close()
     return res
 
 
@@ -72,5 +88,7 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--ticks", type=int, default=600)
     ap.add_argument("--horizon", type=int, default=100, help="the reference uses N = 100, Tf = 5 s; shorter horizons see the obstacles too late")
+    ap.add_argument("--plant-steps", type=int, default=None,
+                    help="integrate the plant in this many RK4 steps per tick (default: the plant is the controller's prediction x_1)")
     a = ap.parse_args()
-    run(a.batch, a.ticks, a.horizon)
+    run(a.batch, a.ticks, a.horizon, plant_steps=a.plant_steps)

@@ -200,7 +200,8 @@ int usvmpc_pipeline_stats(usvmpc_handle *h, long *used, long *discarded);
  * nmpc_guidance_ca1.cpp:577,612, usv_pf_ca/main.py:142-186. */
 int usvmpc_last_mapping(usvmpc_handle *h, int *mapping);
 /* Closed-loop hand-over on the device: x0 <- x_1 (+ sigma * N(0,1) on the states selected by option
- * "disturbance_mask", default all), enqueued on the stream.
+ * "disturbance_mask", default all; the draw of state j of instance b is keyed by (option "instance_offset" + b) * nx + j), enqueued on
+ * the stream.  A plant other than the model's own prediction: usvmpc_advance_sim below.
  * Replaces x0 = solver.get(1,"x"); solver.set(0,"lbx",x0); solver.set(0,"ubx",x0)
  * (catkin_ws/src/nmpc_ca/scripts/usv_guidance_ca1/main.py:169-175). */
 int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed);
@@ -276,8 +277,11 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream);
  *       main launch leave, wait - a bounded wait, "handover_co_spin" polls - for list entries to appear and finish those instances while the
  *       main launch is still draining; what they do not get to is done by the launch behind it (every entry is taken by exactly one of the
  *       two).  Scheduling only.  "handover_co_wgs": workgroups of that kernel (0 = one per CU: what finds room beside the main launch's workgroups at once);
- *   "disturbance_mask" (default all ones) - bit j set: usvmpc_advance adds its noise to state j (the reference's commented
- *       hooks disturb x0[3] and x0[5] only: catkin_ws/src/nmpc_ca/scripts/usv_pf_ca/main.py:181-183). */
+ *   "disturbance_mask" (default all ones) - bit j set: usvmpc_advance / usvmpc_advance_sim add their noise to state j (the reference's
+ *       commented hooks disturb x0[3] and x0[5] only: catkin_ws/src/nmpc_ca/scripts/usv_pf_ca/main.py:181-183);
+ *   "instance_offset" (default 0) - the global index of the handle's first instance.  The disturbance of state j of instance b is drawn
+ *       from the key (instance_offset + b) * nx + j, so a batch split over several handles (shards: set each handle's offset to the
+ *       index of its first instance) draws the same noise as one handle over the whole batch.  0 leaves the draws as they were. */
 int usvmpc_set_option(usvmpc_handle *h, const char *name, double value);
 /* ---- Guidance front end (model usv_model_guidance_ca1 only): the arithmetic either side of the solver
  * call in the reference's ROS node, batched on the device (class NMPC in
@@ -315,6 +319,39 @@ int usvmpc_calibrate_traffic(usvmpc_handle *h, int nplanes, double *bytes_read, 
  * pos [n][2], p [n][2K] -> h [n][K], grad [n][K][2]. */
 int usvmpc_debug_model_eval(int model, int device, int n, const double *x, const double *u, double *f, double *J);
 int usvmpc_debug_obstacle_eval(int device, int n, int K, const double *pos, const double *p, double *h, double *grad);
+/* ---- Integrator (acados_template.AcadosSimSolver): B instances of a model's explicit RK4 over one sampling period T, in num_steps
+ * steps of T / num_steps, with the forward sensitivities when sens_forw != 0.  The same model functions and RK4 arithmetic as the
+ * lineariser's (csrc/sim.hpp); x_next is the same bits with sens_forw on or off, and an instance's result does not depend on the batch.
+ * Arrays are FP64, instance-major; n is the length PER INSTANCE:
+ *   set "x" [B][nx] (n = nx), "u" [B][nu] (n = nu), "T" (n = 1: the period, one value for the batch);
+ *   get "x" [B][nx]: x_next of the last solve; "S_forw" [B][nx][nx + nu] (n = nx * (nx + nu)): [Sx | Su] row-major, the layout of
+ *       acados' S_forw as recalled (the acados sources are not at hand); "T".
+ * usvmpc_sim_solve is synchronous.  Device pointers: "x", "u" (inputs), "x_next", "S_forw" (outputs).  usvmpc_sim_create refuses
+ * (USVMPC_E_ARG) an unknown model, T <= 0 or NaN, num_steps < 1, batch < 1; usvmpc_sim_last_error(NULL) describes the last failed
+ * create of the calling thread.  No adjoint or second-order sensitivities, no implicit integrators. */
+typedef struct usvmpc_sim_desc {
+    int model;             /* USVMPC_MODEL_*; USVMPC_MODEL_GENERATED only in a library built for it */
+    int batch;
+    int device;
+    double T;              /* sampling period */
+    int num_steps;         /* RK4 steps per period (acados sim_method_num_steps) */
+    int sens_forw;         /* 1: also S_forw */
+} usvmpc_sim_desc;
+typedef struct usvmpc_sim usvmpc_sim;
+int usvmpc_sim_create(const usvmpc_sim_desc *d, usvmpc_sim **out);
+int usvmpc_sim_destroy(usvmpc_sim *s);
+int usvmpc_sim_set(usvmpc_sim *s, const char *field, const double *v, size_t n);
+int usvmpc_sim_solve(usvmpc_sim *s);
+int usvmpc_sim_get(usvmpc_sim *s, const char *field, double *out, size_t n);
+int usvmpc_sim_get_device_ptr(usvmpc_sim *s, const char *field, void **dptr);
+/* Adopt a caller-owned HIP stream for the integrator's copies and kernels */
+int usvmpc_sim_set_stream(usvmpc_sim *s, void *stream);
+const char *usvmpc_sim_last_error(usvmpc_sim *s);
+/* Closed-loop plant step on the device: x0 <- sim(x0, u at stage 0) over the plant's T in its num_steps RK4 steps, plus
+ * sigma * N(0,1) on the states of option "disturbance_mask" (keyed as usvmpc_advance: option "instance_offset"); enqueued on the
+ * solver's stream.  The plant must come from this library and have the solver's model, nx and device (else USVMPC_E_ARG); only its
+ * T and num_steps are read - its buffers are not touched. */
+int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, unsigned long long seed);
 /* bytes of device memory held by the handle */
 size_t usvmpc_device_bytes(usvmpc_handle *h);
 const char *usvmpc_last_error(usvmpc_handle *h);

@@ -40,6 +40,12 @@ class Desc(C.Structure):
                 ("hpipm_mode", C.c_int), ("cond_pred_corr", C.c_int), ("cpc_factor", C.c_double)]
 
 
+class SimDesc(C.Structure):
+    """usvmpc_sim_desc"""
+    _fields_ = [("model", C.c_int), ("batch", C.c_int), ("device", C.c_int), ("T", C.c_double), ("num_steps", C.c_int),
+                ("sens_forw", C.c_int)]
+
+
 # QP solver profiles (include/usvmpc.h, USVMPC_HPIPM_*): acados' `hpipm_mode` names, and this library's behaviour up to round 5
 HPIPM_MODES = {"BALANCE": 0, "SPEED": 1, "ROBUST": 2, "R04": 3}
 
@@ -59,7 +65,9 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_sync", "usvmpc_get_device_ptr", "usvmpc_last_kernel_ms", "usvmpc_kernel_ms", "usvmpc_tick_ms", "usvmpc_fail_counts", "usvmpc_unconverged_counts", "usvmpc_unconverged_total", "usvmpc_handover_counts", "usvmpc_handover_co_counts", "usvmpc_followup_ms", "usvmpc_pipeline_stats", "usvmpc_last_mapping",
            "usvmpc_advance", "usvmpc_set_stream", "usvmpc_set_option", "usvmpc_calibrate_traffic", "usvmpc_guidance_reset", "usvmpc_guidance_prepare", "usvmpc_guidance_sense",
            "usvmpc_guidance_publish", "usvmpc_guidance_state", "usvmpc_device_bytes", "usvmpc_last_error",
-           "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval"]
+           "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval",
+           "usvmpc_sim_create", "usvmpc_sim_destroy", "usvmpc_sim_set", "usvmpc_sim_solve", "usvmpc_sim_get", "usvmpc_sim_get_device_ptr",
+           "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim"]
 
 
 _libs = {}
@@ -120,6 +128,16 @@ def load(path):
     L.usvmpc_guidance_state.argtypes = [C.c_void_p, _ip, C.POINTER(C.c_float)]
     L.usvmpc_debug_model_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_obstacle_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+    L.usvmpc_sim_create.argtypes = [C.POINTER(SimDesc), C.POINTER(C.c_void_p)]
+    L.usvmpc_sim_destroy.argtypes = [C.c_void_p]
+    L.usvmpc_sim_set.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_size_t]
+    L.usvmpc_sim_solve.argtypes = [C.c_void_p]
+    L.usvmpc_sim_get.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_size_t]
+    L.usvmpc_sim_get_device_ptr.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    L.usvmpc_sim_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.usvmpc_sim_last_error.argtypes = [C.c_void_p]
+    L.usvmpc_sim_last_error.restype = C.c_char_p
+    L.usvmpc_advance_sim.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_ulonglong]
     L.usvmpc_device_bytes.argtypes = [C.c_void_p]
     L.usvmpc_device_bytes.restype = C.c_size_t
     L.usvmpc_last_error.argtypes = [C.c_void_p]

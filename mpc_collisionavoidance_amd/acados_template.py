@@ -12,6 +12,10 @@ The classes below keep those names, attributes, argument meaning and error behav
 length raises Exception, get returns a fresh array, solve returns the status and never raises),
 but the solver behind them is the HIP library (batch of 1).  `BatchOcpSolver` is the same object
 for B independent instances.
+
+acados' integrator face - `AcadosSim`, `AcadosSimSolver` (`x = integrator.simulate(x, u)`,
+`get("S_forw")`) - is here too, with `BatchSimSolver` for B instances and
+`BatchOcpSolver.advance_sim(plant)` for a closed loop whose plant is such an integrator.
 """
 import ctypes as C
 
@@ -385,6 +389,14 @@ class BatchOcpSolver:
         """Closed-loop hand-over on the device: x0 <- x_1 (+ sigma N(0,1)); asynchronous."""
         self._check(self._lib.usvmpc_advance(self._h, float(sigma), int(seed)))
 
+    def advance_sim(self, plant, sigma=0.0, seed=0):
+        """Closed-loop plant step on the device: x0 <- plant(x0, u_0) (+ sigma N(0,1) on the states of option "disturbance_mask");
+        plant: a BatchSimSolver of this solver's model and device (its T and num_steps are used, its buffers are not touched);
+        asynchronous, on this solver's stream (usvmpc_advance_sim)."""
+        if not isinstance(plant, BatchSimSolver):
+            raise Exception("advance_sim: the plant must be a BatchSimSolver")
+        self._check(self._lib.usvmpc_advance_sim(self._h, plant._s, float(sigma), int(seed)))
+
     def set_option(self, name, value):
         self._check(self._lib.usvmpc_set_option(self._h, name.encode(), float(value)))
 
@@ -489,3 +501,237 @@ class AcadosOcpSolver:
         if field_ == "residuals":  # acados: the NLP residuals for SQP; the QP's for an RTI iteration
             return self._b.get("nlp_res" if self._sqp else "res", 0)[0].copy()
         raise Exception("AcadosOcpSolver.get_stats(): {} is not a valid argument.".format(field_))
+
+
+# ---------------------------------------------------------------------------------------------- integrator (acados' AcadosSim face)
+class AcadosSimDims:
+    def __init__(self):
+        self.nx = None
+        self.nu = None
+        self.nz = 0
+        self.np = 0
+
+
+class AcadosSimOptions:
+    """acados' AcadosSimOpts as recalled (the acados sources are not part of this tree): ERK, 4 stages, one step, forward
+    sensitivities on, adjoint / algebraic / second-order sensitivities off; T has no default and must be set."""
+
+    def __init__(self):
+        self.T = None
+        self.integrator_type = "ERK"
+        self.collocation_type = "GAUSS_LEGENDRE"
+        self.num_stages = 4
+        self.num_steps = 1
+        self.newton_iter = 3
+        self.newton_tol = 0.0
+        self.sens_forw = True
+        self.sens_adj = False
+        self.sens_algebraic = False
+        self.sens_hess = False
+        self.output_z = True
+        self.sim_method_jac_reuse = 0
+        self.model_source = None  # "symbolic": run the model's generated code even if the registry has it (as AcadosOcpOptions)
+
+
+class AcadosSim:
+    def __init__(self):
+        self.model = AcadosModel()
+        self.dims = AcadosSimDims()
+        self.solver_options = AcadosSimOptions()
+        self.parameter_values = np.array([])
+        self.code_export_directory = "c_generated_code"
+
+
+def _sim_from_ocp(ocp):
+    """What acados' AcadosSimSolver makes of an AcadosOcp: its model over one shooting interval, T = tf / N, with the OCP's integrator
+    options.  Also the obstacle layout (chunks, soft) a generated model's library is built for - the one BatchOcpSolver uses."""
+    opts = ocp.solver_options
+    if opts.tf is None or ocp.dims.N is None:
+        raise Exception("AcadosSimSolver: the AcadosOcp needs solver_options.tf and dims.N (T = tf / N)")
+    sim = AcadosSim()
+    sim.model = ocp.model
+    sim.parameter_values = ocp.parameter_values
+    so = sim.solver_options
+    so.T = float(opts.tf) / int(ocp.dims.N)
+    so.integrator_type = opts.integrator_type
+    so.num_stages = getattr(opts, "sim_method_num_stages", 4) or 4
+    so.num_steps = getattr(opts, "sim_method_num_steps", 1) or 1
+    so.model_source = getattr(opts, "model_source", None)
+    K = 0 if ocp.model.con_h_expr is None else ocp.model.con_h_expr.size()[0]
+    idxsh = np.asarray(ocp.constraints.idxsh, dtype=int).reshape(-1)
+    return sim, (K + 15) // 16, bool(K and idxsh.size)
+
+
+def _check_sim_options(sim):
+    so = sim.solver_options
+    if so.integrator_type != "ERK":
+        raise Exception("AcadosSim: integrator_type = %r is not built, only \"ERK\"" % (so.integrator_type,))
+    if so.num_stages is None or int(so.num_stages) != 4:
+        raise Exception("AcadosSim: num_stages = %r is not built: the ERK tableau is the classic RK4 (num_stages = 4)" % (so.num_stages,))
+    if so.sens_adj:
+        raise Exception("AcadosSim: sens_adj is not built (forward sensitivities only)")
+    if so.sens_hess:
+        raise Exception("AcadosSim: sens_hess is not built (forward sensitivities only)")
+    if so.T is None or not (float(so.T) > 0.0) or not np.isfinite(float(so.T)):
+        raise Exception("AcadosSim: solver_options.T must be positive and finite (got %r)" % (so.T,))
+    if so.num_steps is None or int(so.num_steps) < 1:
+        raise Exception("AcadosSim: num_steps must be >= 1 (got %r)" % (so.num_steps,))
+
+
+class BatchSimSolver:
+    """B independent instances of an AcadosSim integrator on one MI355X (usvmpc_sim_*, csrc/sim.hpp): array-valued set / get, device
+    pointers and a caller stream for loops that stay on the device.  `sim` may also be an AcadosOcp (T = tf / N, its integrator options)."""
+
+    def __init__(self, sim, batch, device=0):
+        if isinstance(sim, AcadosOcp):
+            sim, kch, soft = _sim_from_ocp(sim)
+        else:
+            m = sim.model
+            K = 0 if getattr(m, "con_h_expr", None) is None else m.con_h_expr.size()[0]
+            kch, soft = (K + 15) // 16, False
+        _check_sim_options(sim)
+        self.sim = sim
+        self.B = int(batch)
+        so = sim.solver_options
+        # Route as BatchOcpSolver does: a registry model runs its hand-written device code; a symbolic model the registry does not
+        # cover (or solver_options.model_source = "symbolic") runs in a library generated for it
+        from . import casadi_lite
+        m = sim.model
+        symbolic = isinstance(getattr(m, "f_expl_expr", None), casadi_lite.MXVec)
+        known = m.name in _capi.MODEL_IDS and (m.x.size()[0], m.u.size()[0]) == _capi.MODEL_DIMS[_capi.MODEL_IDS[m.name]]
+        self.generated = symbolic and (not known or getattr(so, "model_source", None) == "symbolic")
+        if self.generated:
+            from . import codegen, genbuild
+            info = codegen.analyse(m)
+            self.nx, self.nu, mid = info.nx, info.nu, _capi.MODEL_GENERATED
+            self._lib = _capi.load(genbuild.device_lib_for_model(info, kch, soft))
+        else:
+            if not known:
+                raise Exception("model '%s' is not in the registry %s and carries no symbolic definition" % (m.name, sorted(_capi.MODEL_IDS)))
+            mid = _capi.MODEL_IDS[m.name]
+            self.nx, self.nu = _capi.MODEL_DIMS[mid]
+            self._lib = _capi.lib()
+        self.model_id = mid
+        self.T, self.num_steps, self.sens_forw = float(so.T), int(so.num_steps), bool(so.sens_forw)
+        d = _capi.SimDesc(model=mid, batch=self.B, device=int(device), T=self.T, num_steps=self.num_steps, sens_forw=int(self.sens_forw))
+        s = C.c_void_p()
+        rc = self._lib.usvmpc_sim_create(C.byref(d), C.byref(s))
+        if rc != 0:
+            raise RuntimeError("usvmpc_sim_create failed (%d): %s" % (rc, self._lib.usvmpc_sim_last_error(None).decode()))
+        self._s = s
+
+    def _check(self, rc):
+        if rc < 0:
+            raise Exception(self._lib.usvmpc_sim_last_error(self._s).decode())
+        return rc
+
+    def set(self, field, value):
+        """"x": [B, nx] (or one nx vector for every instance), "u": [B, nu] likewise, "T": the period (one value for the batch)."""
+        if field == "T":
+            a = np.ascontiguousarray(value, dtype=np.float64).reshape(-1)
+            if a.size != 1:
+                raise Exception('mismatching dimension for field "T" with dimension 1 (you have %d)' % a.size)
+            self._check(self._lib.usvmpc_sim_set(self._s, b"T", a.ctypes.data_as(_capi._dp), 1))
+            self.T = float(a[0])
+            return
+        if field not in ("x", "u"):
+            raise Exception("BatchSimSolver.set(): %s is not a valid argument (\"x\", \"u\", \"T\")" % field)
+        n = self.nx if field == "x" else self.nu
+        a = _as_batch(value, self.B, n, field)
+        self._check(self._lib.usvmpc_sim_set(self._s, field.encode(), a.ctypes.data_as(_capi._dp), n))
+
+    def solve(self):
+        """Integrates every instance (synchronous); returns 0."""
+        return self._check(self._lib.usvmpc_sim_solve(self._s))
+
+    def get(self, field):
+        """"x": x_next [B, nx]; "S_forw": [B, nx, nx + nu] = [Sx | Su]; "Sx": [B, nx, nx]; "Su": [B, nx, nu]; "T"."""
+        if field == "T":
+            return self.T
+        if field in ("Sx", "Su"):
+            S = self.get("S_forw")
+            return np.ascontiguousarray(S[:, :, :self.nx] if field == "Sx" else S[:, :, self.nx:])
+        if field not in ("x", "S_forw"):
+            raise Exception("BatchSimSolver.get(): %s is not a valid argument (\"x\", \"S_forw\", \"Sx\", \"Su\", \"T\")" % field)
+        n = self.nx if field == "x" else self.nx * (self.nx + self.nu)
+        out = np.zeros((self.B, n))
+        self._check(self._lib.usvmpc_sim_get(self._s, field.encode(), out.ctypes.data_as(_capi._dp), n))
+        return out.reshape(self.B, self.nx, self.nx + self.nu) if field == "S_forw" else out
+
+    def device_ptr(self, field):
+        """Device pointer of "x", "u" (inputs), "x_next" or "S_forw" (outputs)."""
+        p = C.c_void_p()
+        self._check(self._lib.usvmpc_sim_get_device_ptr(self._s, field.encode(), C.byref(p)))
+        return p.value
+
+    def set_stream(self, stream_ptr):
+        self._check(self._lib.usvmpc_sim_set_stream(self._s, C.c_void_p(stream_ptr)))
+
+    def close(self):
+        if getattr(self, "_s", None) is not None and self._s.value:
+            self._lib.usvmpc_sim_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AcadosSimSolver:
+    """Single-instance integrator with acados_template's calling convention: set / solve / get, simulate(x, u).  Given an AcadosOcp it
+    integrates the OCP's model over one shooting interval (T = tf / N) with the OCP's sim_method_num_steps, as acados does."""
+
+    def __init__(self, acados_sim, json_file="acados_sim.json", device=0, **kwargs):
+        self.json_file = json_file  # accepted for signature compatibility (as generate / build / verbose): nothing is rendered
+        self._b = BatchSimSolver(acados_sim, 1, device=device)
+        self.acados_sim = self._b.sim
+        self.model_name = self._b.sim.model.name
+        self.T = self._b.T
+        self.nx, self.nu = self._b.nx, self._b.nu
+        p = getattr(self._b.sim.model, "p", None)
+        self.np = 0 if p is None else int(p.size()[0])
+        self._p = np.zeros(self.np)
+        self.status = 0
+
+    def set(self, field_, value_):
+        if field_ == "T":
+            self._b.set("T", value_)
+            self.T = self._b.T
+            return
+        dims = {"x": self.nx, "u": self.nu, "p": self.np}
+        if field_ not in dims:
+            raise Exception("AcadosSimSolver.set(): {} is not a valid argument (\"x\", \"u\", \"p\", \"T\")".format(field_))
+        a = np.ascontiguousarray(value_, dtype=np.float64).reshape(-1)
+        if a.size != dims[field_]:
+            raise Exception('AcadosSimSolver.set(): mismatching dimension for field "{}" with dimension {} (you have {})'
+                            .format(field_, dims[field_], a.size))
+        if field_ == "p":  # (no model here has parameters in its dynamics - codegen refuses one that does: kept, nothing to pass on)
+            self._p = a.copy()
+            return
+        self._b.set(field_, a.reshape(1, -1))
+
+    def solve(self):
+        self.status = int(self._b.solve())
+        return self.status
+
+    def get(self, field_):
+        if field_ == "T":
+            return self.T
+        if field_ not in ("x", "S_forw", "Sx", "Su"):
+            raise Exception("AcadosSimSolver.get(): {} is not a valid argument (\"x\", \"S_forw\", \"Sx\", \"Su\", \"T\")".format(field_))
+        return self._b.get(field_)[0].copy()
+
+    def simulate(self, x=None, u=None, z=None, xdot=None, p=None):
+        """x_next from x and u (each as last set when None)."""
+        if x is not None:
+            self.set("x", x)
+        if u is not None:
+            self.set("u", u)
+        if p is not None:
+            self.set("p", p)
+        status = self.solve()
+        if status != 0:
+            raise Exception("acados_sim_solver for model {} returned status {}.".format(self.model_name, status))
+        return self.get("x")

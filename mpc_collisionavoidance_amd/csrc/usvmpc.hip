@@ -25,6 +25,7 @@
 #include "linearize.hpp"
 #include "models.hpp"
 #include "qp_ipm.hpp"
+#include "sim.hpp"
 #include "cond_launch.hpp"
 #ifdef USV_GEN_MODEL_HEADER // a model generated from a symbolic definition (codegen.py): struct ModelGen
 #include USV_GEN_MODEL_HEADER
@@ -268,7 +269,18 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long z)
     return z ^ (z >> 31);
 }
 
-__global__ void usv_advance(DevPtrs P, int nx, double sigma, unsigned long long seed, unsigned mask)
+// sigma * N(0,1) for state j of instance g: key = g * nx + j, g the instance's GLOBAL index (option "instance_offset" + its index in the
+// handle), so that a batch split over several handles draws the same disturbances as one handle over the whole batch (Box-Muller)
+__device__ __forceinline__ double noise(double sigma, unsigned long long seed, unsigned long long key)
+{
+    const unsigned long long h1 = splitmix64(seed ^ (2 * key));
+    const unsigned long long h2 = splitmix64(seed ^ (2 * key + 1));
+    const double u1 = ((double)(h1 >> 11) + 1.0) * (1.0 / 9007199254740993.0);
+    const double u2 = (double)(h2 >> 11) * (1.0 / 9007199254740992.0);
+    return sigma * sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+__global__ void usv_advance(DevPtrs P, int nx, double sigma, unsigned long long seed, unsigned mask, long long offset)
 {
     const DevSpec &S = *P.spec;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -276,14 +288,38 @@ __global__ void usv_advance(DevPtrs P, int nx, double sigma, unsigned long long 
     const long b = i / nx;
     const int j = (int)(i - b * nx);
     double v = P.x[(b * (S.N + 1) + 1) * nx + j];
-    if (sigma != 0.0 && ((mask >> j) & 1u)) {
-        const unsigned long long h1 = splitmix64(seed ^ (unsigned long long)(2 * i));
-        const unsigned long long h2 = splitmix64(seed ^ (unsigned long long)(2 * i + 1));
-        const double u1 = ((double)(h1 >> 11) + 1.0) * (1.0 / 9007199254740993.0);
-        const double u2 = (double)(h2 >> 11) * (1.0 / 9007199254740992.0);
-        v += sigma * sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-    }
+    if (sigma != 0.0 && ((mask >> j) & 1u)) v += noise(sigma, seed, (unsigned long long)((offset + b) * nx + j));
     const_cast<double *>(P.x0)[i] = v;
+}
+
+// The plant step of a closed loop with a plant of its own (usvmpc_advance_sim): x0 <- sim(x0, u_0) over T in `steps` RK4 steps (sim.hpp,
+// one lane per instance), plus the disturbance of usv_advance.  In place: a thread reads its instance's x0 whole before it writes it.
+template <class M>
+__global__ void __launch_bounds__(256) usv_advance_sim(DevPtrs P, double T, int steps, double sigma, unsigned long long seed, unsigned mask,
+                                                       long long offset)
+{
+    constexpr int NX = M::NX, NU = M::NU;
+    const DevSpec &S = *P.spec;
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= (long)S.B) return;
+    double *x0 = const_cast<double *>(P.x0) + b * NX;
+    const double *u0 = P.u + b * (long)S.N * NU;
+    double x[NX], U[NU > 0 ? NU : 1], s[NX], su[NU > 0 ? NU : 1];
+    sfor<0, NX>([&](auto i) { x[i] = x0[i]; s[i] = 0.0; });
+    sfor<0, NU>([&](auto l) { U[l] = u0[l]; su[l] = 0.0; });
+    erk_period<M, false>(x, U, s, su, T, steps);
+    sfor<0, NX>([&](auto j) {
+        double v = x[j];
+        if (sigma != 0.0 && ((mask >> j) & 1u)) v += noise(sigma, seed, (unsigned long long)((offset + b) * NX + j));
+        x0[j] = v;
+    });
+}
+
+// AcadosSimSolver's solve (usvmpc_sim_solve): x, u -> x_next (and S_forw = [Sx | Su] when SENS), sim.hpp
+template <class M, bool SENS>
+__global__ void __launch_bounds__(256) usv_sim(const double *x, const double *u, double *xn, double *S, long B, double T, int steps)
+{
+    sim_run<M, SENS>(x, u, xn, S, B, T, steps);
 }
 
 // Debug / test entry points: the model functions exactly as the lineariser calls them (M::fjvp: f and one Jacobian
@@ -442,6 +478,7 @@ struct usvmpc_handle {
     long aux_cap;             // the same for the aux-in-LDS instantiation (0: not yet known, -1: does not fit / would cost a wave)
     bool map_changed;         // the group -> instance map differs from the one the workspace's multipliers were written under
     unsigned noise_mask;      // states usvmpc_advance disturbs (option "disturbance_mask"; default: all)
+    long long instance_offset; // global index of the handle's first instance (option "instance_offset"): keys the disturbance
     int *d_fail_ring;         // [RING] instances with status != 0, one slot per solve
     int *d_unconv_ring;       // [RING] instances whose QP did not converge to the tolerances (qp_status != 0), one slot per solve
     unsigned long long *d_unconv_total; // [1] ... summed over every RTI solve of the handle (usvmpc_unconverged_total)
@@ -1343,6 +1380,73 @@ int ensure_export(usvmpc_handle *h)
 
 } // namespace
 
+// ---------------------------------------------------------------------------------- integrator handle (usvmpc_sim_*)
+// B instances of one model's ERK4 over one sampling period (sim.hpp).  Inputs x [B][nx], u [B][nu]; outputs x_next [B][nx] and, with
+// sens_forw, S_forw [B][nx][nx + nu].  `owner` tells a plant of THIS library from one made by another build (a generated-model library
+// holds other kernels under the same model id).
+static const char g_lib_tag = 0;
+thread_local std::string g_sim_create_err;
+
+struct usvmpc_sim {
+    const void *owner;
+    int model, nx, nu, nz, B, device;
+    double T;
+    int num_steps, sens;
+    hipStream_t stream;
+    bool own_stream;
+    double *x, *u, *xn, *S;   // device
+    std::string err;
+};
+
+namespace {
+
+#define SIM_TRY(s, call)                                                                          \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            (s)->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
+            return USVMPC_E_HIP;                                                                  \
+        }                                                                                         \
+    } while (0)
+
+int sim_check(const usvmpc_sim_desc &d, int &nx, int &nu, std::string &err)
+{
+    if (model_dims(d.model, nx, nu)) { err = "unknown model id " + std::to_string(d.model) + " in this library"; return USVMPC_E_ARG; }
+#ifdef USV_GEN_ONLY
+    if (d.model != USVMPC_MODEL_GENERATED) { err = "this library only holds the generated model"; return USVMPC_E_ARG; }
+#endif
+    if (d.batch < 1) { err = "batch must be >= 1"; return USVMPC_E_ARG; }
+    if (!(d.T > 0.0) || !std::isfinite(d.T)) { err = "T must be positive and finite"; return USVMPC_E_ARG; }
+    if (d.num_steps < 1) { err = "num_steps must be >= 1"; return USVMPC_E_ARG; }
+    return 0;
+}
+
+// the field table of the integrator: device array and its length per instance
+double *sim_field(usvmpc_sim *s, const std::string &f, bool set, int &n)
+{
+    if (f == "x" && set) { n = s->nx; return s->x; }
+    if (f == "u" && set) { n = s->nu; return s->u; }
+    if (f == "x" && !set) { n = s->nx; return s->xn; }
+    if (f == "S_forw" && !set) { n = s->nx * s->nz; return s->S; }
+    return nullptr;
+}
+
+template <class M>
+void sim_launch_model(usvmpc_sim *s)
+{
+    const long B = s->B;
+    if (s->sens) {
+        const long threads = B * LANES;
+        hipLaunchKernelGGL((usv_sim<M, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s->stream, s->x, s->u, s->xn, s->S, B, s->T,
+                           s->num_steps);
+    } else {
+        hipLaunchKernelGGL((usv_sim<M, false>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s->stream, s->x, s->u, s->xn, s->S, B, s->T,
+                           s->num_steps);
+    }
+}
+
+} // namespace
+
 // ---------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -1422,6 +1526,7 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->spec_for = -1; h->spec_valid = false; h->spec_outstanding = false; h->spec_perm = nullptr;
     h->spec_quiet = 0; h->spec_hits = 0; h->spec_misses = 0;
     h->noise_mask = ~0u;
+    h->instance_offset = 0;
     h->cond_N2 = 0; h->d_cond_dims = nullptr; h->d_cond_scratch = nullptr; h->cond_teams = 0; h->cond_lds = 0;
     h->dynamic_rows = true;
     h->qp_cap = 0;
@@ -1876,7 +1981,54 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
         if (rcf) return rcf;
     }
     const long n = (long)h->B * h->nx;
-    hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->noise_mask);
+    hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->noise_mask,
+                       h->instance_offset);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, unsigned long long seed)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!plant) { h->err = "advance_sim: null plant"; return USVMPC_E_ARG; }
+    if (plant->owner != &g_lib_tag) {
+        h->err = "advance_sim: the plant was created by another solver library (its model's kernels are not in this one)";
+        return USVMPC_E_ARG;
+    }
+    if (plant->model != h->desc.model || plant->nx != h->nx || plant->nu != h->nu) {
+        h->err = "advance_sim: the plant's model (" + std::to_string(plant->model) + ", nx " + std::to_string(plant->nx) +
+                 ") differs from the solver's (" + std::to_string(h->desc.model) + ", nx " + std::to_string(h->nx) + ")";
+        return USVMPC_E_ARG;
+    }
+    if (plant->device != h->device) {
+        h->err = "advance_sim: the plant is on device " + std::to_string(plant->device) + ", the solver on device " + std::to_string(h->device);
+        return USVMPC_E_ARG;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        const int rcf = mirror_flush(h);
+        if (rcf) return rcf;
+    }
+    const dim3 grid((unsigned)((h->B + 255) / 256)), block(256);
+    switch (h->desc.model) {
+#ifndef USV_GEN_ONLY
+    case USVMPC_MODEL_USV:
+        hipLaunchKernelGGL(usv_advance_sim<ModelM0>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        break;
+    case USVMPC_MODEL_GUIDANCE_CA1:
+        hipLaunchKernelGGL(usv_advance_sim<ModelM1>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        break;
+    case USVMPC_MODEL_PF_CA:
+        hipLaunchKernelGGL(usv_advance_sim<ModelM2>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        break;
+#endif
+#ifdef USV_GEN_MODEL_HEADER
+    case USVMPC_MODEL_GENERATED:
+        hipLaunchKernelGGL(usv_advance_sim<ModelGen>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        break;
+#endif
+    default: h->err = "advance_sim: no plant kernel for this model in this library"; return USVMPC_E_ARG;
+    }
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -1972,6 +2124,14 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
     if (s == "handover_co_wgs") { if (!(value >= 0.0 && value <= 1e6)) { h->err = "handover_co_wgs out of range"; return USVMPC_E_ARG; } h->co_wgs = (long)value; return 0; } // the follow-up launch with the planes copied into LDS when the horizon fits (default), or always over the planes in HBM
     if (s == "disturbance_mask") { // bit j: usvmpc_advance adds its noise to state j
         h->noise_mask = (unsigned)value;
+        return 0;
+    }
+    if (s == "instance_offset") { // global index of instance 0 of this handle: the disturbance of a shard is that of the unsharded batch
+        if (!(value >= 0.0 && value <= 9007199254740992.0) || value != (double)(long long)value) {
+            h->err = "instance_offset must be a non-negative integer";
+            return USVMPC_E_ARG;
+        }
+        h->instance_offset = (long long)value;
         return 0;
     }
     if (s == "merge_box_rows") { // 1 (default): box rows processed in their slot lanes when all of them ride there
@@ -2190,6 +2350,161 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream)
     h->own_stream = false;
     return 0;
 }
+
+int usvmpc_sim_create(const usvmpc_sim_desc *d, usvmpc_sim **out)
+{
+    if (!d || !out) return USVMPC_E_ARG;
+    *out = nullptr;
+    int nx = 0, nu = 0;
+    std::string err;
+    const int rc = sim_check(*d, nx, nu, err);
+    if (rc) {
+        g_sim_create_err = "usvmpc_sim_create: " + err;
+        return rc;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || d->device < 0 || d->device >= ndev) {
+        g_sim_create_err = "usvmpc_sim_create: no usable HIP device (count " + std::to_string(ndev) + ", requested " + std::to_string(d->device) +
+                           "); there is no CPU fallback";
+        return USVMPC_E_NODEVICE;
+    }
+    usvmpc_sim *s = new usvmpc_sim();
+    s->owner = &g_lib_tag;
+    s->model = d->model; s->nx = nx; s->nu = nu; s->nz = nx + nu; s->B = d->batch; s->device = d->device;
+    s->T = d->T; s->num_steps = d->num_steps; s->sens = d->sens_forw != 0;
+    s->stream = nullptr; s->own_stream = true;
+    s->x = s->u = s->xn = s->S = nullptr;
+    auto fail = [&](hipError_t e, const char *what) {
+        g_sim_create_err = std::string("usvmpc_sim_create: ") + what + ": " + hipGetErrorString(e);
+        (void)hipFree(s->x); (void)hipFree(s->u); (void)hipFree(s->xn); (void)hipFree(s->S);
+        if (s->stream) (void)hipStreamDestroy(s->stream);
+        delete s;
+        return USVMPC_E_HIP;
+    };
+    const size_t B = (size_t)s->B;
+    hipError_t e;
+    if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
+    if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess) { s->stream = nullptr; return fail(e, "hipStreamCreate"); }
+    if ((e = hipMalloc((void **)&s->x, B * nx * sizeof(double))) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMalloc((void **)&s->u, B * (nu ? nu : 1) * sizeof(double))) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMalloc((void **)&s->xn, B * nx * sizeof(double))) != hipSuccess) return fail(e, "hipMalloc");
+    if (s->sens && (e = hipMalloc((void **)&s->S, B * nx * s->nz * sizeof(double))) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemsetAsync(s->x, 0, B * nx * sizeof(double), s->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(s->u, 0, B * (nu ? nu : 1) * sizeof(double), s->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(s->xn, 0, B * nx * sizeof(double), s->stream)) != hipSuccess ||
+        (s->S && (e = hipMemsetAsync(s->S, 0, B * nx * s->nz * sizeof(double), s->stream)) != hipSuccess) ||
+        (e = hipStreamSynchronize(s->stream)) != hipSuccess)
+        return fail(e, "hipMemsetAsync");
+    *out = s;
+    return 0;
+}
+
+int usvmpc_sim_destroy(usvmpc_sim *s)
+{
+    if (!s) return USVMPC_E_ARG;
+    (void)hipSetDevice(s->device);
+    (void)hipStreamSynchronize(s->stream);
+    (void)hipFree(s->x); (void)hipFree(s->u); (void)hipFree(s->xn); (void)hipFree(s->S);
+    if (s->own_stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+    return 0;
+}
+
+int usvmpc_sim_set(usvmpc_sim *s, const char *field, const double *v, size_t n)
+{
+    if (!s) return USVMPC_E_ARG;
+    if (!v) { s->err = "null buffer"; return USVMPC_E_ARG; }
+    const std::string f(field ? field : "");
+    if (f == "T") {
+        if (n != 1) { s->err = "mismatching dimension for field 'T': expected 1, got " + std::to_string(n); return USVMPC_E_SIZE; }
+        if (!(v[0] > 0.0) || !std::isfinite(v[0])) { s->err = "T must be positive and finite"; return USVMPC_E_ARG; }
+        s->T = v[0];
+        return 0;
+    }
+    int len = 0;
+    double *dst = sim_field(s, f, true, len);
+    if (!dst) { s->err = "unknown field '" + f + "' (set: \"x\", \"u\", \"T\")"; return USVMPC_E_FIELD; }
+    if ((int)n != len) {
+        s->err = "mismatching dimension for field '" + f + "': expected " + std::to_string(len) + ", got " + std::to_string(n);
+        return USVMPC_E_SIZE;
+    }
+    if (len == 0) return 0;
+    SIM_TRY(s, hipSetDevice(s->device));
+    SIM_TRY(s, hipMemcpyAsync(dst, v, (size_t)s->B * len * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    SIM_TRY(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int usvmpc_sim_solve(usvmpc_sim *s)
+{
+    if (!s) return USVMPC_E_ARG;
+    SIM_TRY(s, hipSetDevice(s->device));
+    switch (s->model) {
+#ifndef USV_GEN_ONLY
+    case USVMPC_MODEL_USV: sim_launch_model<ModelM0>(s); break;
+    case USVMPC_MODEL_GUIDANCE_CA1: sim_launch_model<ModelM1>(s); break;
+    case USVMPC_MODEL_PF_CA: sim_launch_model<ModelM2>(s); break;
+#endif
+#ifdef USV_GEN_MODEL_HEADER
+    case USVMPC_MODEL_GENERATED: sim_launch_model<ModelGen>(s); break;
+#endif
+    default: s->err = "no integrator kernel for this model in this library"; return USVMPC_E_ARG;
+    }
+    SIM_TRY(s, hipGetLastError());
+    SIM_TRY(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int usvmpc_sim_get(usvmpc_sim *s, const char *field, double *out, size_t n)
+{
+    if (!s) return USVMPC_E_ARG;
+    if (!out) { s->err = "null buffer"; return USVMPC_E_ARG; }
+    const std::string f(field ? field : "");
+    if (f == "T") {
+        if (n != 1) { s->err = "mismatching dimension for field 'T': expected 1, got " + std::to_string(n); return USVMPC_E_SIZE; }
+        out[0] = s->T;
+        return 0;
+    }
+    if (f == "S_forw" && !s->sens) { s->err = "S_forw is not computed: the integrator was created with sens_forw = 0"; return USVMPC_E_FIELD; }
+    int len = 0;
+    const double *src = sim_field(s, f, false, len);
+    if (!src) { s->err = "unknown field '" + f + "' (get: \"x\", \"S_forw\", \"T\")"; return USVMPC_E_FIELD; }
+    if ((int)n != len) {
+        s->err = "mismatching dimension for field '" + f + "': expected " + std::to_string(len) + ", got " + std::to_string(n);
+        return USVMPC_E_SIZE;
+    }
+    SIM_TRY(s, hipSetDevice(s->device));
+    SIM_TRY(s, hipMemcpyAsync(out, src, (size_t)s->B * len * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    SIM_TRY(s, hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int usvmpc_sim_get_device_ptr(usvmpc_sim *s, const char *field, void **dptr)
+{
+    if (!s || !dptr) return USVMPC_E_ARG;
+    const std::string f(field ? field : "");
+    double *p = f == "x" ? s->x : f == "u" ? s->u : f == "x_next" ? s->xn : f == "S_forw" ? s->S : nullptr;
+    if (!p) {
+        s->err = f == "S_forw" ? "S_forw is not computed: the integrator was created with sens_forw = 0"
+                               : "unknown field '" + f + "' (\"x\", \"u\", \"x_next\", \"S_forw\")";
+        return USVMPC_E_FIELD;
+    }
+    *dptr = (void *)p;
+    return 0;
+}
+
+int usvmpc_sim_set_stream(usvmpc_sim *s, void *stream)
+{
+    if (!s) return USVMPC_E_ARG;
+    SIM_TRY(s, hipSetDevice(s->device));
+    SIM_TRY(s, hipStreamSynchronize(s->stream));
+    if (s->own_stream) (void)hipStreamDestroy(s->stream);
+    s->stream = (hipStream_t)stream;
+    s->own_stream = false;
+    return 0;
+}
+
+const char *usvmpc_sim_last_error(usvmpc_sim *s) { return s ? s->err.c_str() : g_sim_create_err.c_str(); }
 
 size_t usvmpc_device_bytes(usvmpc_handle *h) { return h ? h->bytes : 0; }
 

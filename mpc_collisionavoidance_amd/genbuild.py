@@ -61,6 +61,17 @@ def build_device_lib(info, kch, soft):
     return out
 
 
+def device_lib_for_model(info, kch, soft):
+    """A library holding this model's kernels for a caller that needs the model only (the integrator, AcadosSimSolver): one already
+    built for the model under any obstacle layout if there is one that is up to date, else the layout (kch, soft) is built."""
+    import glob
+    for d in sorted(glob.glob(os.path.join(GEN, codegen.digest(info) + "_k*_s*"))):
+        out, hdr = os.path.join(d, "libusvmpc_gen.so"), os.path.join(d, "model_gen.hpp")
+        if os.path.exists(hdr) and open(hdr).read() == codegen.emit_device_header(info) and not _stale(out, hdr):
+            return out
+    return build_device_lib(info, kch, soft)
+
+
 def build_emu_lib(info, kch, soft, emu_dir):
     """CPU lane-emulator build of the same kernels with the generated model (tests only)."""
     d, hdr = _dir(info, kch, soft)
