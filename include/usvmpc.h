@@ -246,6 +246,9 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream);
  *       few it has to skip are redone in front of the next QP launch); any usvmpc_set, option change or device-pointer access in
  *       between makes the next solve linearise afresh.  The queue order of a tick is then made one tick earlier.  Scheduling
  *       only: results are bit-identical to the un-pipelined sequence;
+ *   "lin_force_modes" (default 0; for tests) - 1 / 2: an RTI solve that would run the whole-batch lineariser runs the pipeline's two kernels
+ *       in its place, the speculative one with every instance taken as final (1) or none (2: the fix-up pass then does all the work).  The
+ *       same bits as 0;
  *   "host_mirror" (default: on for handles whose caller-visible arrays total <= 1 MiB, i.e. the single-instance drop-in faces) -
  *       usvmpc_set writes a pinned host mirror and the next solve uploads the dirty fields in one asynchronous copy instead
  *       (ordering: a set becomes visible on the device with the NEXT launch of the handle, not at the call - except once a device pointer

@@ -10,6 +10,7 @@
 // informative entries are then packed densely for HBM (MatPack, params.hpp).
 #pragma once
 #include "lanes.hpp"
+#include "lin_order.hpp"
 #include "params.hpp"
 #include "sfor.hpp"
 
@@ -45,24 +46,55 @@ struct ModelCall<M, std::void_t<typename M::Pre>> {
 //         AND so are those of the instance that still owns the group's planes under the running launch's map; otherwise it marks the
 //         instance for MODE 2.  The iterate is read with loads that bypass the non-coherent L2s (lanes::ld_shared).
 // MODE 2: fix-up after that launch: only the instances MODE 1 marked.
+// MODE 3: MODE 1 with its grid walked in the order the running launch retires its instances (run_item, lin_order.hpp), by one-wave
+//         workgroups: one fits into the registers a single leaving QP wave frees.
+// MODE 4: MODE 2 as one wave per group, which leaves at once when its instance has no mark (run_marked).
+// (which pair a launch takes: usvmpc.hip launch_solve)
 template <class M, int KCH, bool SOFT, bool MULTI = false, int MODE = 0>
 struct Linearize {
     static constexpr int NX = M::NX, NU = M::NU, NZ = NX + NU;
     using WL = WsLayout<M, KCH, SOFT>;
+    static constexpr bool SPEC = MODE == 1 || MODE == 3, FIXUP = MODE == 2 || MODE == 4;
 
-    // gid = k * Bp + g  (groups of a wave share the stage k)
+    // gid = k * Bp + g  (groups of a wave share the stage k): the whole-batch order of MODE 0
     USV_DEV static void run(const DevPtrs &P, long gid)
+    {
+        const long Bp = lanes::uniform(P.spec->Bp);
+        const int k = (int)(gid / Bp);
+        run_at(P, k, gid - (long)k * Bp);
+    }
+
+    // MODE 3: work item -> (group, stage) in the order the running QP launch retires its instances (lin_order.hpp); the four groups of a
+    // wave are neighbouring stages of one instance (two at an instance's end)
+    USV_DEV static void run_item(const DevPtrs &P, long item)
+    {
+        const LinItem it = lin_item(item, P.spec->N, (long)P.spec->B, P.perm_cur, P.inv_next);
+        run_at(P, it.k, it.g);
+    }
+
+    // MODE 4: group g's marked stages, row r of the wave taking the stages k = r, r + 4, ...  A wave whose instance has no mark - nearly
+    // all of them - leaves after reading the instance's redo words once.
+    USV_DEV static void run_marked(const DevPtrs &P, long g, int row)
+    {
+        const int N = lanes::uniform(P.spec->N);
+        const long gi = lin_slot(g, (long)lanes::uniform(P.spec->B));
+        const long b = P.perm ? (long)P.perm[gi] : gi;
+        int any = 0;
+        for (int w = 0; w < P.redo_words; w++) any |= P.redo[b * P.redo_words + w];
+        if (any == 0) return;
+        for (int k = row; k <= N; k += lanes::WAVE_ROWS) run_at(P, k, g);
+    }
+
+    // stage k of group g
+    USV_DEV static void run_at(const DevPtrs &P, const int k, const long g)
     {
         const DevSpec &S = *P.spec;
         const int lane = lanes::lane();
         const int N = lanes::uniform(S.N), K = lanes::uniform(S.K);
         const long Bp = lanes::uniform(S.Bp);
-        const int k = (int)(gid / Bp);
-        const long g = gid - (long)k * Bp;
-        const int nB = lanes::uniform(S.B);
-        const long gi = g < nB ? g : (long)nB - 1; // padded groups replay the last instance
+        const long gi = lin_slot(g, (long)lanes::uniform(S.B)); // padded groups replay the last instance
         const long b = P.perm ? (long)P.perm[gi] : gi;
-        if constexpr (MODE == 1) {
+        if constexpr (SPEC) {
             const long owner = P.perm_cur ? (long)P.perm_cur[gi] : gi;
             const bool ready = lanes::observe(P.epoch + b) == P.tick && lanes::observe(P.epoch + owner) == P.tick;
             if (!ready) { // (the whole 16-lane group leaves: nothing below crosses groups)
@@ -70,11 +102,11 @@ struct Linearize {
                 return;
             }
         }
-        if constexpr (MODE == 2) {
+        if constexpr (FIXUP) {
             if (((P.redo[b * P.redo_words + (k >> 5)] >> (k & 31)) & 1) == 0) return;
         }
-        auto ld = [](const double *q) { // the iterate: handed over by a kernel that may still be running (MODE 1)
-            if constexpr (MODE == 1) return lanes::ld_shared(q);
+        auto ld = [](const double *q) { // the iterate: handed over by a kernel that may still be running (MODE 1, 3)
+            if constexpr (SPEC) return lanes::ld_shared(q);
             else return *q;
         };
         // workspace: [stage][group][plane][16 lanes] (lanes::Planes)

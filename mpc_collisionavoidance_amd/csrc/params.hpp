@@ -183,6 +183,7 @@ struct DevPtrs {
     int *redo;            // [B][redo_words]  bit k: the speculative lineariser skipped stage k of the instance: the fix-up pass does it
     int redo_words;       //      (N + 1 + 31) / 32
     const int *perm_cur;  // [B]  speculative lineariser: the group -> instance map of the QP launch that is still running
+    const int *inv_next;  // [B]  speculative lineariser: instance -> group, the inverse of ITS map `perm` (lin_order.hpp); nullptr = identity
     int tick;             // the solve this launch belongs to (QP, fix-up) / whose results the speculative lineariser waits for
     // multiplier read-back (kernel usv_qp_export): [B][N+1][nlam] each, nlam = 2 (nrow + ns) - DevSpec
     double *lam_out, *t_out;

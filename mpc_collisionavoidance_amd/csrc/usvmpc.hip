@@ -46,13 +46,28 @@ using namespace usv;
 #ifndef USV_LIN_BLOCKS
 #define USV_LIN_BLOCKS 2 // 256-thread blocks per CU the lineariser is compiled for (2: 2 waves per SIMD, 256 registers)
 #endif
-// MODE: 0 the whole batch; 1 speculative for the next tick beside a running QP launch; 2 fix-up of what mode 1 skipped (linearize.hpp)
+// MODE: 0 the whole batch; 1 / 3 speculative for the next tick beside a running QP launch; 2 / 4 fix-up of what that pass skipped (linearize.hpp)
+// Workgroups and what `n` counts:
+//   0, 1, 2  256 threads, 16 (group, stage) pairs in stage-major order, n pairs
+//   3        ONE wave, 4 work items of lin_order.hpp, n items.  The QP launch it runs beside holds every SIMD's registers (2 waves x 256); a QP
+//            wave that leaves frees room for one of these waves (224 registers), on that SIMD only - a four-wave workgroup has to wait
+//            until each of the CU's SIMDs has lost a QP wave.
+//   4        256 threads = 4 waves, one wave per group (its rows share out the group's marked stages), n groups
+constexpr int LIN_MODES = 5;
+constexpr int lin_block(int mode) { return mode == 3 ? 64 : 256; }
 template <class M, int KCH, bool SOFT, bool MULTI, int MODE = 0>
-__global__ void __launch_bounds__(256, USV_LIN_BLOCKS) usv_linearize(DevPtrs P, long ngroups)
+__global__ void __launch_bounds__(lin_block(MODE), USV_LIN_BLOCKS) usv_linearize(DevPtrs P, long n)
 {
-    const long gid = lanes::group_linear();
-    if (gid >= ngroups) return; // ngroups is a multiple of 4: whole waves leave together
-    Linearize<M, KCH, SOFT, MULTI, MODE>::run(P, gid);
+    using L = Linearize<M, KCH, SOFT, MULTI, MODE>;
+    if constexpr (MODE == 4) {
+        const long g = (long)blockIdx.x * (lin_block(MODE) / 64) + (long)(threadIdx.x >> 6);
+        if (g < n) L::run_marked(P, g, (int)lanes::wave_row());
+    } else {
+        const long gid = lanes::group_linear();
+        if (gid >= n) return; // n is a multiple of 4: whole waves leave together
+        if constexpr (MODE == 3) L::run_item(P, gid);
+        else L::run(P, gid);
+    }
 }
 
 #ifndef USV_QP_WAVES
@@ -193,7 +208,7 @@ struct Kernels {
     qp_resume_t resume, resume_lds;              // the follow-up launch of a hand-over: over the planes in HBM / after copying them into LDS
     qp_resume_co_t resume_co;                    // ... and its co-resident form (usv_qp_resume_co)
     int nplw, ex_lds, ex_hbm;                    // planes per stage an instance keeps in LDS; planes of the exchange area (qp_ipm.hpp NPLW, EX_N)
-    group_kernel_t lin[2][3];                    // usv_linearize [MULTI][MODE]
+    group_kernel_t lin[2][LIN_MODES];            // usv_linearize [MULTI][MODE]
     group_kernel_t qp_export;                    // usv_qp_export
     int npt_hard, npt_soft;                      // WsLayout::NPT without / with soft state bounds
     int kch;                                     // the instantiation's KCH and SOFT (h->kch / h->soft may differ: usv_model with "soft" set)
@@ -407,7 +422,8 @@ static __global__ void usv_sort_scan(int *hist, int *cursor)
     }
 }
 
-static __global__ void __launch_bounds__(256) usv_sort_scatter(const int *qp_iter, const int *qp_iter_prev, int B, int *cursor, int *perm)
+// (inv: the inverse map, instance -> group, for the speculative lineariser's work order - lin_order.hpp; nullptr: not wanted)
+static __global__ void __launch_bounds__(256) usv_sort_scatter(const int *qp_iter, const int *qp_iter_prev, int B, int *cursor, int *perm, int *inv)
 {
     __shared__ int loc[SORT_BINS], base[SORT_BINS];
     if (threadIdx.x < SORT_BINS) loc[threadIdx.x] = 0;
@@ -421,7 +437,17 @@ static __global__ void __launch_bounds__(256) usv_sort_scatter(const int *qp_ite
     __syncthreads();
     if (threadIdx.x < SORT_BINS && loc[threadIdx.x] != 0) base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], loc[threadIdx.x]);
     __syncthreads();
-    if (i < B) perm[base[bin] + rank] = i;
+    if (i < B) {
+        perm[base[bin] + rank] = i;
+        if (inv) inv[i] = base[bin] + rank;
+    }
+}
+
+// instance -> group from group -> instance (option "lin_force_modes": the map of a solve that no sort of its own launch made)
+static __global__ void __launch_bounds__(256) usv_invert_map(const int *perm, int B, int *inv)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < B) inv[perm[g]] = g;
 }
 
 // ---------------------------------------------------------------------------------- handle
@@ -507,7 +533,7 @@ struct usvmpc_handle {
     bool pipeline;            // option; used for RTI solves of handles without a host mirror
     hipStream_t aux_stream;   // nullptr until first used
     hipEvent_t ev_pre, ev_spec;
-    int *d_epoch, *d_redo, *d_perm2;
+    int *d_epoch, *d_redo, *d_perm2, *d_inv;
     long spec_for;            // solve number the outstanding / finished speculative linearisation was made for (-1: none)
     bool spec_valid;          // ... and nothing it read has been changed by the caller since
     bool spec_outstanding;    // the second stream may still be writing the lineariser's planes
@@ -516,6 +542,12 @@ struct usvmpc_handle {
                               // protocol: scripts/usv_guidance_ca1/main.py:123-130) never pays for a speculative pass that is thrown away
     long spec_hits, spec_misses; // ahead-of-time linearisations used / discarded (usvmpc_pipeline_stats)
     const int *spec_perm;     // the group -> instance map it used (= the map the solve spec_for must use)
+    bool spec_fine;           // ... made by usv_linearize MODE 3 (its fix-up is MODE 4) instead of MODE 1 (MODE 2): launch_solve
+    // Option "lin_force_modes" (tests): a solve that would run the whole-batch lineariser runs the pipeline's kernels MODE 3 + MODE 4 in its
+    // place, on the main stream - 1: the speculative form with every instance final, then the fix-up (which finds nothing); 2: with no instance final (it
+    // marks everything), then the fix-up (which does everything).  Work order as in the pipeline, with the identity as the "running" map.
+    int lin_force;
+    int *d_force_epoch, *d_force_redo, *d_force_inv;
     // partial condensing (option "qp_cond_N"): RTI solves condense the QP to cond_N2 stages first (0: off - the Riccati sweep over the N stages)
     int cond_N2;
     CondDims cond_dims;       // sizes of the condensed QP (valid when d_cond_dims is set)
@@ -541,7 +573,9 @@ Kernels kernels_for(const usvmpc_handle *h)
     const bool pack = CANPACK && S.boxpack != 0;
     Kernels k = {};
     k.lin[0][0] = &usv_linearize<M, KCH, SOFT, false, 0>; k.lin[0][1] = &usv_linearize<M, KCH, SOFT, false, 1>; k.lin[0][2] = &usv_linearize<M, KCH, SOFT, false, 2>;
+    k.lin[0][3] = &usv_linearize<M, KCH, SOFT, false, 3>; k.lin[0][4] = &usv_linearize<M, KCH, SOFT, false, 4>;
     k.lin[1][0] = &usv_linearize<M, KCH, SOFT, true, 0>; k.lin[1][1] = &usv_linearize<M, KCH, SOFT, true, 1>; k.lin[1][2] = &usv_linearize<M, KCH, SOFT, true, 2>;
+    k.lin[1][3] = &usv_linearize<M, KCH, SOFT, true, 3>; k.lin[1][4] = &usv_linearize<M, KCH, SOFT, true, 4>;
     k.qp_export = S.any_bsoft ? &usv_qp_export<M, KCH, SOFT, false, true>
                               : pack ? &usv_qp_export<M, KCH, SOFT, CANPACK, false> : &usv_qp_export<M, KCH, SOFT, false, false>;
     k.npt_hard = WsLayout<M, KCH, SOFT, false>::NPT; k.npt_soft = WsLayout<M, KCH, SOFT, true>::NPT;
@@ -1178,17 +1212,21 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
     }
+    // the lineariser's grids (usv_linearize): (group, stage) pairs - or work items -, groups for MODE 4
     const long lin_groups = (long)(h->N + 1) * h->Bp;
-    const int lin_block = 256;
-    const long lin_grid = (lin_groups * LANES + lin_block - 1) / lin_block;
+    auto lin_count = [&](int mode) { return mode == 4 ? (long)h->Bp : lin_groups; };
+    auto lin_grid = [&](int mode) {
+        const long per_block = mode == 4 ? lin_block(mode) / 64 : lin_block(mode) / LANES;
+        return dim3((unsigned)((lin_count(mode) + per_block - 1) / per_block));
+    };
     hipEvent_t *ev = h->ev[h->nsolves % usvmpc_handle::RING];
     const int B = h->B;
     // counting sort of the previous solve's iteration counts into a group -> instance map
-    auto sort_into = [&](int *dst) {
+    auto sort_into = [&](int *dst, int *inv) {
         const int *prev2 = h->sort_two ? h->d_iter_prev : h->ptrs.qp_iter; // (option "sort_two_ticks" = 0: the last count alone)
         hipLaunchKernelGGL(usv_sort_hist, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_hist);
         hipLaunchKernelGGL(usv_sort_scan, dim3(1), dim3(64), 0, h->stream, h->d_hist, h->d_cursor);
-        hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst);
+        hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst, inv);
     };
     const group_kernel_t *lin = k.lin[h->spec.sim_steps > 1 ? 1 : 0]; // [MODE]
     // Pipelined lineariser (see usvmpc_handle): RTI solves of large handles
@@ -1203,7 +1241,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
         HIP_TRY(h, hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));
         if (dev_alloc(h, &h->d_epoch, (size_t)B, false) || dev_alloc(h, &h->d_redo, (size_t)B * ((h->N + 32) / 32), true) ||
-            dev_alloc(h, &h->d_perm2, (size_t)B, true))
+            dev_alloc(h, &h->d_perm2, (size_t)B, true) || dev_alloc(h, &h->d_inv, (size_t)B, true))
             return USVMPC_E_HIP;
         HIP_TRY(h, hipMemsetAsync(h->d_epoch, 0xff, (size_t)B * sizeof(int), h->stream)); // -1: nothing is final yet
     }
@@ -1225,7 +1263,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         // group -> instance map must not change inside one SQP call; a phase-1 launch re-sorts BEFORE its QP writes the multipliers:
         // map and workspace stay consistent)
         if (phase == 0) h->map_changed = true;
-        sort_into(h->d_perm);
+        sort_into(h->d_perm, nullptr);
         HIP_TRY(h, hipGetLastError());
         h->ptrs.perm = h->d_perm;
     }
@@ -1236,11 +1274,31 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
     h->ptrs.redo = pipe ? h->d_redo : nullptr;
     h->ptrs.redo_words = (h->N + 32) / 32;
     h->ptrs.perm_cur = nullptr;
+    h->ptrs.inv_next = nullptr;
     h->ptrs.tick = (int)h->nsolves;
     h->ev3_set[h->nsolves % usvmpc_handle::RING] = false;
     HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    // (MODE 2: only what the speculative pass had to skip)
-    hipLaunchKernelGGL(lin[use_spec ? 2 : 0], dim3((unsigned)lin_grid), dim3(lin_block), 0, h->stream, h->ptrs, lin_groups);
+    // (MODE 2 / 4: only what the speculative pass had to skip)
+    const int lin_mode = use_spec ? (h->spec_fine ? 4 : 2) : 0;
+    if (h->lin_force != 0 && lin_mode == 0 && phase == 0) { // (usvmpc_handle::lin_force)
+        const size_t nredo = (size_t)B * h->ptrs.redo_words;
+        if (!h->d_force_epoch && (dev_alloc(h, &h->d_force_epoch, (size_t)B, false) || dev_alloc(h, &h->d_force_redo, nredo, false) ||
+                                  dev_alloc(h, &h->d_force_inv, (size_t)B, false)))
+            return USVMPC_E_HIP;
+        DevPtrs Pf = h->ptrs;
+        Pf.epoch = h->d_force_epoch;
+        Pf.redo = h->d_force_redo;
+        HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->d_force_epoch, h->lin_force == 1 ? Pf.tick : -1, (size_t)B, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->d_force_redo, 0, nredo * sizeof(int), h->stream));
+        if (Pf.perm) {
+            hipLaunchKernelGGL(usv_invert_map, dim3((B + 255) / 256), dim3(256), 0, h->stream, Pf.perm, B, h->d_force_inv);
+            Pf.inv_next = h->d_force_inv;
+        }
+        hipLaunchKernelGGL(lin[3], lin_grid(3), dim3(lin_block(3)), 0, h->stream, Pf, lin_count(3));
+        hipLaunchKernelGGL(lin[4], lin_grid(4), dim3(lin_block(4)), 0, h->stream, Pf, lin_count(4));
+    } else {
+        hipLaunchKernelGGL(lin[lin_mode], lin_grid(lin_mode), dim3(lin_block(lin_mode)), 0, h->stream, h->ptrs, lin_count(lin_mode));
+    }
     HIP_TRY(h, hipGetLastError());
     if (pipe) HIP_TRY(h, hipMemsetAsync(h->d_redo, 0, (size_t)B * ((h->N + 32) / 32) * sizeof(int), h->stream));
     HIP_TRY(h, hipEventRecord(ev[1], h->stream));
@@ -1253,7 +1311,8 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         // the NEXT tick's map, from the counts this launch is about to overwrite, into the buffer this tick does not use
         if (h->sort_enabled) {
             int *dst = (h->ptrs.perm == h->d_perm) ? h->d_perm2 : h->d_perm;
-            sort_into(dst);
+            // (d_inv: read by the speculative lineariser only, which every later sort of this stream comes behind - ev_spec above)
+            sort_into(dst, h->d_inv);
             HIP_TRY(h, hipGetLastError());
             next_perm = dst;
         }
@@ -1285,7 +1344,14 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         DevPtrs Pn = h->ptrs;
         Pn.perm = next_perm;
         Pn.perm_cur = h->ptrs.perm;
-        hipLaunchKernelGGL(lin[1], dim3((unsigned)lin_grid), dim3(lin_block), 0, h->aux_stream, Pn, lin_groups);
+        Pn.inv_next = next_perm ? h->d_inv : nullptr;
+        // Which form: in the retire order, by one-wave workgroups (MODE 3, fix-up MODE 4), when this QP launch hands nothing over.  A launch
+        // that does (batches up to three times the resident rows) needs the slots its leaving waves free for its follow-up workgroups, a
+        // large share of its instances is still running when the lineariser arrives, and the fix-up has a large share to redo: measured
+        // at 16 384 instances the fine form cost 0.6 ms of QP launch and 0.35 ms of fix-up per 21 ms tick; at 65 536 it saves 1.4 of 71.5 ms.
+        h->spec_fine = h->ptrs.susp_count == nullptr;
+        const int spec_mode = h->spec_fine ? 3 : 1;
+        hipLaunchKernelGGL(lin[spec_mode], lin_grid(spec_mode), dim3(lin_block(spec_mode)), 0, h->aux_stream, Pn, lin_count(spec_mode));
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->ev_spec, h->aux_stream));
         h->spec_for = h->nsolves + 1;
@@ -1522,7 +1588,9 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->last_cond = false;
     h->pipeline = true;
     h->aux_stream = nullptr; h->ev_pre = nullptr; h->ev_spec = nullptr;
-    h->d_epoch = nullptr; h->d_redo = nullptr; h->d_perm2 = nullptr;
+    h->d_epoch = nullptr; h->d_redo = nullptr; h->d_perm2 = nullptr; h->d_inv = nullptr;
+    h->spec_fine = false;
+    h->lin_force = 0; h->d_force_epoch = nullptr; h->d_force_redo = nullptr; h->d_force_inv = nullptr;
     h->spec_for = -1; h->spec_valid = false; h->spec_outstanding = false; h->spec_perm = nullptr;
     h->spec_quiet = 0; h->spec_hits = 0; h->spec_misses = 0;
     h->noise_mask = ~0u;
@@ -2074,6 +2142,11 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         return 0;
     }
     if (s == "sort_two_ticks") { h->sort_two = value != 0.0; return 0; }
+    if (s == "lin_force_modes") { // (tests: usvmpc_handle::lin_force)
+        if (value != 0.0 && value != 1.0 && value != 2.0) { h->err = "lin_force_modes: 0, 1 or 2"; return USVMPC_E_ARG; }
+        h->lin_force = (int)value;
+        return 0;
+    }
     if (s == "aux_in_lds") { h->aux_lds = value != 0.0; reset_caps(h); return 0; }
     if (s == "lds_workspace") { // -1: when the batch is small (default), 0: never, 1: whenever an instance's planes fit in LDS
         h->lds_mode = value < 0.0 ? -1 : (value > 0.0 ? 1 : 0);
