@@ -136,6 +136,30 @@ int usvmpc_get(usvmpc_handle *h, const char *field, int stage, double *out, size
  * of its own on the first such get after a solve. */
 /* further get fields: "obs_tmin" (stage ignored, n = 1): the smallest lower-side slack t_l over the instance's obstacle rows
  * in the last QP (1e300 without rows) - below ~1e-3 the solution touches a keep-out circle, i.e. an obstacle row is active */
+/* ---- Obstacle tracks: a position (ox, oy) and a constant velocity (vx, vy) per instance and obstacle slot, kept on the device, from which the
+ * handle derives p itself - a closed loop against MOVING obstacles without rebuilding and uploading [B][N+1][2K] doubles every tick.
+ *   set / get "obs_pos", "obs_vel": [batch][2K], pairs per obstacle in slot order, laid out like one stage of "p"; the stage argument is
+ *       ignored (as for "x0").  The device buffers are made by the first set of either field (a handle that never uses tracks pays nothing);
+ *       "obs_vel" defaults to 0.  USVMPC_E_FIELD for a model without obstacle rows (K = 0).  usvmpc_get_device_ptr serves both (a caller
+ *       that holds such a pointer may move the obstacles with kernels of its own: the prediction then runs before every solve).  The
+ *       keep-out radii stay where they are: "lh".
+ *   option "obstacle_tracks" = 1 (after "obs_pos" was set; default 0): every usvmpc_solve / _solve_async / _solve_sqp first writes
+ *           p[b][k][2i + c] = obs_pos[b][2i + c] + ((double)k * dt) * obs_vel[b][2i + c]      k = 0 .. N,  dt = Tf / N
+ *       on the handle's stream (kernel usv_obstacle_predict; product and sum rounded separately, no fused multiply-add: the bits numpy makes
+ *       from the same expression), behind the upload of pending host writes and ahead of every kernel that reads p; skipped while neither
+ *       the tracks nor the world clock changed.  With "static_obstacles" = 1 only stage 0 is written (a world that moves between ticks and is
+ *       held still inside the horizon).  While the option is on usvmpc_set "p" is refused (USVMPC_E_ARG) and usvmpc_get "p" returns what the
+ *       device holds; switched off, p is the caller's again, as it stands.  The lineariser does not read p: linearisations made ahead of
+ *       time (option "pipeline_linearize") stay valid.
+ *   usvmpc_obstacles_step(h, T): the world moves on, obs_pos += T * obs_vel (unfused), then per instance
+ *           clearance = min over slots i of  sqrt((X - ox_i)^2 + (Y - oy_i)^2) - lh[b][0][i]
+ *       with (X, Y) the position states of x0 (the states the model's obstacle rows read); enqueued on the handle's stream (kernel
+ *       usv_obstacle_step).  While the option is on usvmpc_advance calls it with T = dt and usvmpc_advance_sim with the plant's period, behind
+ *       their own kernel - one call is still the tick's hand-over; option "obstacle_step_on_advance" = 0 (default 1) leaves the world to the
+ *       caller (a tracker that sets "obs_pos" every tick).
+ *   get "clearance" [batch] (n = 1): the value after the last world step; "clearance_min": its running minimum since the caller last set
+ *       "obs_pos" (which resets it to 1e300).  Parked slots ((1000, 1000), lh 0) need no special case. */
+int usvmpc_obstacles_step(usvmpc_handle *h, double T);
 /* integer per-instance results: "status" (0 | 4; after usvmpc_solve_sqp 0 | 2 | 4), "qp_status" (0 ok,
  * 1 max iter, 2 min step, 3 nan, 4 x0 violates a hard obstacle row of stage 0 - the QP has no feasible point), "qp_iter", "sqp_iter" */
 int usvmpc_get_int(usvmpc_handle *h, const char *field, int *out);
@@ -284,7 +308,9 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream);
  *       commented hooks disturb x0[3] and x0[5] only: catkin_ws/src/nmpc_ca/scripts/usv_pf_ca/main.py:181-183);
  *   "instance_offset" (default 0) - the global index of the handle's first instance.  The disturbance of state j of instance b is drawn
  *       from the key (instance_offset + b) * nx + j, so a batch split over several handles (shards: set each handle's offset to the
- *       index of its first instance) draws the same noise as one handle over the whole batch.  0 leaves the draws as they were. */
+ *       index of its first instance) draws the same noise as one handle over the whole batch.  0 leaves the draws as they were;
+ *   "obstacle_tracks" (default 0), "obstacle_step_on_advance" (default 1) - p derived from the obstacle tracks, the world stepped by the
+ *       hand-over: "Obstacle tracks" above. */
 int usvmpc_set_option(usvmpc_handle *h, const char *name, double value);
 /* ---- Guidance front end (model usv_model_guidance_ca1 only): the arithmetic either side of the solver
  * call in the reference's ROS node, batched on the device (class NMPC in

@@ -67,7 +67,7 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_guidance_publish", "usvmpc_guidance_state", "usvmpc_device_bytes", "usvmpc_last_error",
            "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval",
            "usvmpc_sim_create", "usvmpc_sim_destroy", "usvmpc_sim_set", "usvmpc_sim_solve", "usvmpc_sim_get", "usvmpc_sim_get_device_ptr",
-           "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim"]
+           "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step"]
 
 
 _libs = {}
@@ -138,6 +138,7 @@ def load(path):
     L.usvmpc_sim_last_error.argtypes = [C.c_void_p]
     L.usvmpc_sim_last_error.restype = C.c_char_p
     L.usvmpc_advance_sim.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_ulonglong]
+    L.usvmpc_obstacles_step.argtypes = [C.c_void_p, C.c_double]
     L.usvmpc_device_bytes.argtypes = [C.c_void_p]
     L.usvmpc_device_bytes.restype = C.c_size_t
     L.usvmpc_last_error.argtypes = [C.c_void_p]

@@ -158,6 +158,19 @@ def _as_batch(value, B, n, what):
     return np.ascontiguousarray(a.reshape(B, n))
 
 
+def _as_tracks(value, B, K, what):
+    """Obstacle tracks in any of their shapes - [B, K, 2], [B, 2K], or one [K, 2] / [2K] set for every instance - as the contiguous
+    [B, 2K] array of the C ABI ((ox, oy) pairs in slot order).  A wrong count raises with acados' wording; NaN is refused."""
+    a = np.ascontiguousarray(value, dtype=np.float64)
+    n = 2 * int(K)
+    if a.ndim >= 2 and a.shape[-1] == 2 and a.shape[-2] != K:
+        raise Exception('mismatching dimension for field "%s" with dimension %d (you have %d)' % (what, n, 2 * a.shape[-2]))
+    a = _as_batch(a, B, n, what)
+    if np.isnan(a).any():
+        raise Exception('field "%s" contains NaN' % what)
+    return a
+
+
 class BatchOcpSolver:
     """B independent instances of one OCP on one MI355X; array-valued set/get replace the
     3N+4 ctypes round trips per tick of the reference loop (usv_guidance_ca1/main.py:123-130)."""
@@ -177,6 +190,7 @@ class BatchOcpSolver:
         self._desc = _capi.desc_from_ocp(ocp, batch=self.B, device=device, generated=self.generated)
         self.N = self._desc.N
         self.K = self._desc.K
+        self.dt = self._desc.Tf / self._desc.N   # the shooting interval as the library computes it
         if self.generated:
             from . import codegen, genbuild
             info = codegen.analyse(m)
@@ -250,6 +264,10 @@ class BatchOcpSolver:
         return rc
 
     def set(self, field, stage, value):
+        if field in ("obs_pos", "obs_vel"):     # the obstacle tracks (the stage is ignored)
+            a = _as_tracks(value, self.B, self.K, field)
+            self._check(self._lib.usvmpc_set(self._h, field.encode(), 0, a.ctypes.data_as(_capi._dp), 2 * self.K))
+            return
         n, _ = self._field(field, stage)
         a = _as_batch(value, self.B, n, field)
         self._check(self._lib.usvmpc_set(self._h, field.encode(), int(stage), a.ctypes.data_as(_capi._dp), n))
@@ -271,6 +289,14 @@ class BatchOcpSolver:
         if field == "obs_tmin":
             out = np.zeros(self.B)
             self._check(self._lib.usvmpc_get(self._h, b"obs_tmin", 0, out.ctypes.data_as(_capi._dp), 1))
+            return out
+        if field in ("obs_pos", "obs_vel"):     # the obstacle tracks, [B, K, 2]
+            out = np.zeros((self.B, self.K, 2))
+            self._check(self._lib.usvmpc_get(self._h, field.encode(), 0, out.ctypes.data_as(_capi._dp), 2 * self.K))
+            return out
+        if field in ("clearance", "clearance_min"):   # [B]: after the last world step / its minimum since "obs_pos" was last set
+            out = np.zeros(self.B)
+            self._check(self._lib.usvmpc_get(self._h, field.encode(), 0, out.ctypes.data_as(_capi._dp), 1))
             return out
         n, _ = self._field(field, stage)
         out = np.zeros((self.B, n))
@@ -399,6 +425,22 @@ class BatchOcpSolver:
 
     def set_option(self, name, value):
         self._check(self._lib.usvmpc_set_option(self._h, name.encode(), float(value)))
+
+    def set_obstacle_tracks(self, pos, vel=None):
+        """Obstacle tracks: positions (and constant velocities; None leaves them as they are - 0 at first) of the K obstacle slots,
+        [B, K, 2], [B, 2K] or one [K, 2] set for every instance.  Switches option "obstacle_tracks" on: from now on every solve derives p
+        on the device (p[k] = pos + k dt vel), and advance / advance_sim move the world along (include/usvmpc.h, "Obstacle tracks")."""
+        if vel is not None:
+            v = _as_tracks(vel, self.B, self.K, "obs_vel")
+            self._check(self._lib.usvmpc_set(self._h, b"obs_vel", 0, v.ctypes.data_as(_capi._dp), 2 * self.K))
+        p = _as_tracks(pos, self.B, self.K, "obs_pos")
+        self._check(self._lib.usvmpc_set(self._h, b"obs_pos", 0, p.ctypes.data_as(_capi._dp), 2 * self.K))
+        self.set_option("obstacle_tracks", 1)
+
+    def step_obstacles(self, T):
+        """The world moves on by T: obs_pos += T obs_vel, then get("clearance", 0) / get("clearance_min", 0); asynchronous
+        (usvmpc_obstacles_step)."""
+        self._check(self._lib.usvmpc_obstacles_step(self._h, float(T)))
 
     def set_stream(self, stream_ptr):
         self._check(self._lib.usvmpc_set_stream(self._h, C.c_void_p(stream_ptr)))

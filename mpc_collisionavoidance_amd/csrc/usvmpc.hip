@@ -24,6 +24,7 @@
 #include "host_spec.hpp"
 #include "linearize.hpp"
 #include "models.hpp"
+#include "obstacle_tracks.hpp"
 #include "qp_ipm.hpp"
 #include "sim.hpp"
 #include "cond_launch.hpp"
@@ -330,6 +331,44 @@ __global__ void __launch_bounds__(256) usv_advance_sim(DevPtrs P, double T, int 
     });
 }
 
+// ---- Obstacle tracks (option "obstacle_tracks"; the arithmetic: obstacle_tracks.hpp).
+// usv_obstacle_predict: p of every stage from the tracks, p[b][k][slot] = pos[b][slot] + (k dt) vel[b][slot] - a pure streaming write (1.7 GB at
+// N = 80, K = 20, 65 536 instances), one 16-byte store per (ox, oy) pair.  One workgroup per instance: thread t owns slot t % K of stage
+// offset t / K (divided once), keeps its pair of the tracks in registers and walks the stages in steps of 256 / K, so that in every pass the live
+// lanes write 256 / K whole stages = ONE contiguous run of p, lane t the t-th pair of it (a wave's stores cover 1 KiB without gaps; the
+// 256 % K last lanes idle).  last: N, or 0 when every stage uses stage 0's set ("static_obstacles").
+__global__ void __launch_bounds__(256) usv_obstacle_predict(const double2 *pos, const double2 *vel, double2 *p, int N, int K, int last, double dt)
+{
+    const int per = 256 / K; // (1 <= K <= 32)
+    const int k0 = (int)threadIdx.x / K, i = (int)threadIdx.x - k0 * K;
+    if (k0 >= per) return;
+    const long b = blockIdx.x;
+    const double2 q = pos[b * K + i], v = vel[b * K + i];
+    double2 *row = p + b * (long)(N + 1) * K + i;
+    for (int k = k0; k <= last; k += per) {
+        double2 o;
+        o.x = track_predict(q.x, v.x, k, dt);
+        o.y = track_predict(q.y, v.y, k, dt);
+        row[(long)k * K] = o;
+    }
+}
+
+// usv_obstacle_step: the world moves on by T (pos += T vel), then the clearance the vehicle keeps - x0's position states (ipx, ipy) against
+// the stepped obstacles and stage 0's lh - and its running minimum (reset: the minimum starts again).  One lane per instance.
+__global__ void __launch_bounds__(256) usv_obstacle_step(double *pos, const double *vel, const double *x0, const double *lh, double *clear,
+                                                         double *clear_min, int B, int K, int N, int nx, int ipx, int ipy, double T, int reset)
+{
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= (long)B) return;
+    double *q = pos + b * 2 * K;
+    const double *v = vel + b * 2 * K;
+    for (int j = 0; j < 2 * K; j++) q[j] = track_step(q[j], v[j], T);
+    const double c = track_clearance(x0[b * nx + ipx], x0[b * nx + ipy], q, lh + b * (long)N * K, K);
+    clear[b] = c;
+    const double m = clear_min[b];
+    clear_min[b] = (reset || c < m) ? c : m;
+}
+
 // AcadosSimSolver's solve (usvmpc_sim_solve): x, u -> x_next (and S_forw = [Sx | Su] when SENS), sim.hpp
 template <class M, bool SENS>
 __global__ void __launch_bounds__(256) usv_sim(const double *x, const double *u, double *xn, double *S, long B, double T, int steps)
@@ -555,6 +594,17 @@ struct usvmpc_handle {
     double *d_cond_scratch;   // [cond_teams][cond_dims.total]
     long cond_teams;
     size_t cond_lds;          // dynamic LDS of the condensing kernel, bytes
+    // Obstacle tracks (option "obstacle_tracks"): position and velocity per instance and obstacle slot, laid out like one stage of p.  While the
+    // option is on p is DERIVED: every solve first runs usv_obstacle_predict on the main stream (launch_solve) - unless neither the tracks nor
+    // the world clock nor the stages it writes changed since it last ran.  Buffers exist from the first set of a track field.
+    double *d_obs_pos, *d_obs_vel;   // [B][2K] each
+    double *d_clear, *d_clear_min;   // [B] clearance after the last world step / its minimum since the caller last set "obs_pos"
+    bool tracks_on;           // the option
+    bool tracks_pos_set;      // "obs_pos" has been set (or its device pointer handed out)
+    bool tracks_dirty;        // p on the device is not what the tracks predict
+    bool tracks_extern;       // a device pointer to a track field was handed out: the prediction runs before every solve
+    bool step_on_advance;     // option "obstacle_step_on_advance": usvmpc_advance / _advance_sim move the world too
+    bool clear_reset;         // the next world step starts the running minimum afresh (until then "clearance_min" reads 1e300)
     long export_at;           // nsolves the multiplier read-back buffers (ptrs.lam_out / t_out) were filled at; -1: never
     bool last_cond;           // the last launch solved the partially condensed QP (its rows live in per-team scratch, not in the workspace)
     bool layout_dirty;        // the row layout option changed after the last solve: the workspace cannot be read back
@@ -810,10 +860,118 @@ int mirror_flush(usvmpc_handle *h)
     return 0;
 }
 
+// ---- obstacle tracks (usvmpc_handle: d_obs_pos ..): buffers on first use, the caller-visible fields, the two launches
+int tracks_alloc(usvmpc_handle *h)
+{
+    if (h->K == 0) { h->err = "obstacle tracks: this model has no obstacle rows (K = 0)"; return USVMPC_E_FIELD; }
+    if (h->d_obs_pos) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t B = (size_t)h->B, n = B * 2 * (size_t)h->K;
+    double *pos = nullptr, *vel = nullptr, *cl = nullptr, *clm = nullptr;
+    if (dev_alloc(h, &pos, n, true) || dev_alloc(h, &vel, n, true) || dev_alloc(h, &cl, B, false) || dev_alloc(h, &clm, B, false))
+        return USVMPC_E_HIP;
+    const std::vector<double> far(B, 1e300); // (no world step yet)
+    HIP_TRY(h, hipMemcpyAsync(cl, far.data(), B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(clm, far.data(), B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->d_obs_pos = pos; h->d_obs_vel = vel; h->d_clear = cl; h->d_clear_min = clm;
+    return 0;
+}
+
+bool is_tracks_field(const std::string &s) { return s == "obs_pos" || s == "obs_vel" || s == "clearance" || s == "clearance_min"; }
+
+// usvmpc_set / usvmpc_get of "obs_pos" / "obs_vel" ([B][2K]) and usvmpc_get of "clearance" / "clearance_min" ([B]); the stage is ignored
+int tracks_field(usvmpc_handle *h, const std::string &s, double *host, size_t n, bool set)
+{
+    if (h->K == 0) { h->err = "field '" + s + "': this model has no obstacle rows (K = 0), hence no obstacle tracks"; return USVMPC_E_FIELD; }
+    const bool track = s == "obs_pos" || s == "obs_vel";
+    if (set && !track) { h->err = "field '" + s + "' is read-only"; return USVMPC_E_FIELD; }
+    const size_t want = track ? 2 * (size_t)h->K : 1;
+    if (n != want) {
+        h->err = "mismatching dimension for field '" + s + "': expected " + std::to_string(want) + ", got " + std::to_string(n);
+        return USVMPC_E_SIZE;
+    }
+    if (!set && !h->d_obs_pos) { h->err = "field '" + s + "': no obstacle tracks yet (set \"obs_pos\" first)"; return USVMPC_E_ARG; }
+    const int rca = tracks_alloc(h);
+    if (rca) return rca;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nbytes = (size_t)h->B * want * sizeof(double);
+    if (set) {
+        HIP_TRY(h, hipMemcpyAsync(s == "obs_pos" ? h->d_obs_pos : h->d_obs_vel, host, nbytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->tracks_dirty = true;
+        if (s == "obs_pos") { h->tracks_pos_set = true; h->clear_reset = true; }
+        return 0;
+    }
+    if (s == "clearance_min" && h->clear_reset) { // (the positions were set anew and the world has not moved since)
+        for (int b = 0; b < h->B; b++) host[b] = 1e300;
+        return 0;
+    }
+    const double *src = s == "obs_pos" ? h->d_obs_pos : s == "obs_vel" ? h->d_obs_vel : s == "clearance" ? h->d_clear : h->d_clear_min;
+    HIP_TRY(h, hipMemcpyAsync(host, src, nbytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// position states of the handle's model (the states its obstacle rows read)
+bool model_pos_index(int model, int &ipx, int &ipy)
+{
+    switch (model) {
+#ifndef USV_GEN_ONLY
+    case USVMPC_MODEL_GUIDANCE_CA1: ipx = ModelM1::IPX; ipy = ModelM1::IPY; return true;
+    case USVMPC_MODEL_PF_CA: ipx = ModelM2::IPX; ipy = ModelM2::IPY; return true;
+#endif
+#ifdef USV_GEN_MODEL_HEADER
+    case USVMPC_MODEL_GENERATED: ipx = ModelGen::IPX; ipy = ModelGen::IPY; return true;
+#endif
+    }
+    return false;
+}
+
+// p <- the tracks' prediction, on the main stream (launch_solve: behind the upload of pending host writes, ahead of every reader of p)
+int tracks_predict(usvmpc_handle *h)
+{
+    const int last = h->spec.p_static ? 0 : h->N;
+    hipLaunchKernelGGL(usv_obstacle_predict, dim3((unsigned)h->B), dim3(256), 0, h->stream, (const double2 *)h->d_obs_pos,
+                       (const double2 *)h->d_obs_vel, (double2 *)const_cast<double *>(h->ptrs.p), h->N, h->K, last, h->spec.dt);
+    HIP_TRY(h, hipGetLastError());
+    h->tracks_dirty = false;
+    return 0;
+}
+
+// the world step (usvmpc_obstacles_step; usvmpc_advance / _advance_sim behind their own kernel): enqueued on the main stream
+int tracks_step(usvmpc_handle *h, double T)
+{
+    if (!h->d_obs_pos || !h->tracks_pos_set) { h->err = "obstacles_step: no obstacle tracks yet (set \"obs_pos\" first)"; return USVMPC_E_ARG; }
+    if (!(T == T) || T - T != 0.0) { h->err = "obstacles_step: T must be finite"; return USVMPC_E_ARG; }
+    int ipx = 0, ipy = 0;
+    if (!model_pos_index(h->desc.model, ipx, ipy)) { h->err = "obstacles_step: this model has no position states"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    {   // (x0 and lh are read: pending host writes go up first)
+        const int rcf = mirror_flush(h);
+        if (rcf) return rcf;
+    }
+    hipLaunchKernelGGL(usv_obstacle_step, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->d_obs_pos, (const double *)h->d_obs_vel,
+                       h->ptrs.x0, h->ptrs.lh, h->d_clear, h->d_clear_min, h->B, h->K, h->N, h->nx, ipx, ipy, T, h->clear_reset ? 1 : 0);
+    HIP_TRY(h, hipGetLastError());
+    h->clear_reset = false;
+    h->tracks_dirty = true;
+    return 0;
+}
+
 int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, size_t n, bool set)
 {
     if (!h) return USVMPC_E_ARG;
+    if (is_tracks_field(std::string(field ? field : "")) && h->K == 0) return tracks_field(h, field, host, n, set); // (the field error, whatever the buffer)
     if (!host) { h->err = "null buffer"; return USVMPC_E_ARG; }
+    {
+        const std::string fs(field ? field : "");
+        if (is_tracks_field(fs)) return tracks_field(h, fs, host, n, set);
+        if (set && h->tracks_on && fs == "p") {
+            h->err = "field 'p' is derived from the obstacle tracks while option \"obstacle_tracks\" is 1: set \"obs_pos\" / \"obs_vel\", or switch the option off";
+            return USVMPC_E_ARG;
+        }
+    }
     if (!set && (std::string(field ? field : "") == "lam" || std::string(field ? field : "") == "t")) {
         const int rce = ensure_export(h);
         if (rce) return rce;
@@ -1212,6 +1370,12 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
     }
+    // option "obstacle_tracks": p is what the tracks predict (the lineariser - the pipelined one included - never reads p: nothing made ahead
+    // of time is invalidated; skipped while tracks, world clock and the stages written are what they were - not under a caller's device pointer)
+    if (h->tracks_on && (h->tracks_dirty || h->tracks_extern)) {
+        const int rct = tracks_predict(h);
+        if (rct) return rct;
+    }
     // the lineariser's grids (usv_linearize): (group, stage) pairs - or work items -, groups for MODE 4
     const long lin_groups = (long)(h->N + 1) * h->Bp;
     auto lin_count = [&](int mode) { return mode == 4 ? (long)h->Bp : lin_groups; };
@@ -1595,6 +1759,9 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->spec_quiet = 0; h->spec_hits = 0; h->spec_misses = 0;
     h->noise_mask = ~0u;
     h->instance_offset = 0;
+    h->d_obs_pos = nullptr; h->d_obs_vel = nullptr; h->d_clear = nullptr; h->d_clear_min = nullptr;
+    h->tracks_on = false; h->tracks_pos_set = false; h->tracks_dirty = false; h->tracks_extern = false;
+    h->step_on_advance = true; h->clear_reset = false;
     h->cond_N2 = 0; h->d_cond_dims = nullptr; h->d_cond_scratch = nullptr; h->cond_teams = 0; h->cond_lds = 0;
     h->dynamic_rows = true;
     h->qp_cap = 0;
@@ -1827,6 +1994,16 @@ int usvmpc_get_device_ptr(usvmpc_handle *h, const char *field, void **dptr)
 {
     if (!h || !dptr) return USVMPC_E_ARG;
     const std::string s(field ? field : "");
+    if (s == "obs_pos" || s == "obs_vel") {
+        // a track field: the caller's own kernels may move the obstacles behind the handle's back, so the prediction runs before every solve
+        // from now on.  Nothing a lineariser reads is exposed: the pipeline keeps running.
+        const int rca = tracks_alloc(h);
+        if (rca) return rca;
+        h->tracks_extern = true;
+        if (s == "obs_pos") h->tracks_pos_set = true;
+        *dptr = s == "obs_pos" ? h->d_obs_pos : h->d_obs_vel;
+        return 0;
+    }
     const DevPtrs &P = h->ptrs;
     const void *p = s == "x" ? (const void *)P.x : s == "u" ? (const void *)P.u : s == "x0" ? (const void *)P.x0
                   : s == "yref" ? (const void *)P.yref : s == "yref_e" ? (const void *)P.yref_e
@@ -2052,7 +2229,15 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
     hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->noise_mask,
                        h->instance_offset);
     HIP_TRY(h, hipGetLastError());
+    if (h->tracks_on && h->step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
     return 0;
+}
+
+int usvmpc_obstacles_step(usvmpc_handle *h, double T)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (h->K == 0) { h->err = "obstacles_step: this model has no obstacle rows (K = 0)"; return USVMPC_E_FIELD; }
+    return tracks_step(h, T);
 }
 
 int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, unsigned long long seed)
@@ -2098,6 +2283,7 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     default: h->err = "advance_sim: no plant kernel for this model in this library"; return USVMPC_E_ARG;
     }
     HIP_TRY(h, hipGetLastError());
+    if (h->tracks_on && h->step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
     return 0;
 }
 
@@ -2105,6 +2291,17 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
 {
     if (!h) return USVMPC_E_ARG;
     const std::string s(name ? name : "");
+    // (the obstacle-track options come first: p is read by no lineariser, so a linearisation made ahead of time stays good across them)
+    if (s == "obstacle_tracks") {
+        if (value != 0.0 && value != 1.0) { h->err = "obstacle_tracks: 0 or 1"; return USVMPC_E_ARG; }
+        if (value == 0.0) { h->tracks_on = false; return 0; } // (p stays as it stands and is the caller's again)
+        if (h->K == 0) { h->err = "obstacle_tracks: this model has no obstacle rows (K = 0)"; return USVMPC_E_ARG; }
+        if (!h->tracks_pos_set) { h->err = "obstacle_tracks: set \"obs_pos\" before switching the option on"; return USVMPC_E_ARG; }
+        h->tracks_on = true;
+        h->tracks_dirty = true;
+        return 0;
+    }
+    if (s == "obstacle_step_on_advance") { h->step_on_advance = value != 0.0; return 0; }
     {
         const int rcs = spec_cancel(h); // (options change maps, layouts or launches: a lineariser that ran ahead is not trusted across them)
         if (rcs) return rcs;
@@ -2225,7 +2422,7 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         return 0;
     }
     if (s == "static_obstacles" || s == "pack_box_rows") {
-        if (s == "static_obstacles") h->spec.p_static = value != 0.0;
+        if (s == "static_obstacles") { h->spec.p_static = value != 0.0; h->tracks_dirty = true; } // (the stages the prediction writes change)
         else { h->spec.boxpack = (value != 0.0 && h->spec.boxpack_ok) ? 1 : 0; reset_caps(h); h->layout_dirty = true; }
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipMemcpyAsync(h->d_spec, &h->spec, sizeof(DevSpec), hipMemcpyHostToDevice, h->stream));

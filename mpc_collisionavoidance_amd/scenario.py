@@ -151,6 +151,7 @@ def make_batch(name, N, K, B, dt=None, seed=1234, moving=False, n_active=None, g
     K = int(K)
     p = np.zeros((B, N + 1, 2 * K))
     lh = np.zeros((B, N, K))
+    obs_pos, obs_vel = np.zeros((B, K, 2)), np.zeros((B, K, 2))
     if K:
         na = K if n_active is None else int(n_active)
         R = rng.uniform(0.3, 1.5, (B, K)) + 0.5
@@ -212,6 +213,7 @@ def make_batch(name, N, K, B, dt=None, seed=1234, moving=False, n_active=None, g
         p[:, :, 0::2] = ox[:, None, :] + t * vel[:, None, :, 0]
         p[:, :, 1::2] = oy[:, None, :] + t * vel[:, None, :, 1]
         lh[:] = lhv[:, None, :]
+        obs_pos, obs_vel = np.stack([ox, oy], axis=2), np.ascontiguousarray(vel)   # the tracks p was made from (predict_tracks)
     # initial guess: kinematic straight-line rollout (constant body velocities, u = 0).  acados'
     # own cold start x_k = x0 linearises every stage's obstacle rows at the current position,
     # which makes the hard rows of usv_model_pf_ca mutually inconsistent with moving at all.
@@ -234,7 +236,21 @@ def make_batch(name, N, K, B, dt=None, seed=1234, moving=False, n_active=None, g
         x_init[:, :, 11] += tk * vy
     u_init = np.zeros((B, N, nu))
     return dict(x0=x0, yref=yref, yref_e=yref_e, p=p, lh=lh, x_init=x_init, u_init=u_init,
-                nx=nx, nu=nu, K=K, N=N, dt=dt, sim_steps=sim_steps, generator=generator)
+                nx=nx, nu=nu, K=K, N=N, dt=dt, sim_steps=sim_steps, generator=generator,
+                obs_pos=obs_pos, obs_vel=obs_vel)
+
+
+def predict_tracks(pos, vel, N, dt):
+    """p [B, N+1, 2K] of obstacle tracks pos, vel [B, K, 2]: stage k holds pos + (k dt) vel - the expression make_batch builds p with, so
+    predict_tracks(wl["obs_pos"], wl["obs_vel"], N, dt) IS wl["p"], bit for bit, and so is what the device derives under option
+    "obstacle_tracks" (csrc/obstacle_tracks.hpp: product and sum rounded separately)."""
+    pos, vel = np.asarray(pos, dtype=float), np.asarray(vel, dtype=float)
+    B, K = pos.shape[0], pos.shape[1]
+    p = np.zeros((B, N + 1, 2 * K))
+    t = (np.arange(N + 1) * dt)[None, :, None]
+    p[:, :, 0::2] = pos[:, None, :, 0] + t * vel[:, None, :, 0]
+    p[:, :, 1::2] = pos[:, None, :, 1] + t * vel[:, None, :, 1]
+    return p
 
 
 def make_bench_batch(name, N, K, B, seed=1234, moving=False, verbatim=False, n_active=None):
@@ -265,3 +281,10 @@ def load_into(solver, wl):
     if wl["K"]:
         solver.set_all("p", wl["p"])
         solver.set_all("lh", wl["lh"])
+
+
+def load_tracks(solver, wl):
+    """Hand a workload's obstacle tracks to a BatchOcpSolver and switch it to deriving p from them (after load_into: lh stays the
+    caller's).  From then on solver.advance / advance_sim move the obstacles along with the vehicle."""
+    if wl["K"]:
+        solver.set_obstacle_tracks(wl["obs_pos"], wl["obs_vel"])
