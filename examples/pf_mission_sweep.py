@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Multi-leg path-following missions with the headline model, the whole tick on the device: the reference's path-following node
+(catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp: waypoint manager, x0 / reference assembly, published thrusts) around usv_model_pf_ca with hard
+obstacle rows, for B random obstacle fields at once (scenario.make_pf_missions: two legs, four obstacles beside them).  A tick is
+
+    prepare() -> solve_async() -> publish(fetch=False) -> advance()
+
+with no host array and no stream synchronisation in it: the front end reads the vessel's state from the solver's own x0 and writes the solver
+inputs in place (guidance.PathFollowingFrontEnd, device-resident mode).  The plant is the controller's prediction x_1, as in the reference's
+own main.py; with --plant-steps K an RK4 integrator of its own (advance_sim: x0 <- sim(x0, u_0) in K steps).
+
+    python examples/pf_mission_sweep.py --batch 8192 --ticks 560 [--plant-steps 10]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (before the solver library: one HIP runtime for both)
+from mpc_collisionavoidance_amd import AcadosSim, BatchOcpSolver, BatchSimSolver, scenario, usv_models  # noqa: E402
+from mpc_collisionavoidance_amd.guidance import PathFollowingFrontEnd  # noqa: E402
+
+RING = 64   # solves whose failure counts the library keeps
+
+
+def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False):
+    cfg = scenario.PF_MISSION_OCP
+    dt = cfg["dt"]
+    m = scenario.make_pf_missions(B, seed)
+    ocp = usv_models.make_ocp("usv_model_pf_ca", N * dt, N, K)
+    ocp.solver_options.sim_method_num_steps = cfg["sim_steps"]
+    s = BatchOcpSolver(ocp, B)
+    plant = None
+    if plant_steps:
+        sim = AcadosSim()
+        sim.model = ocp.model
+        sim.solver_options.T, sim.solver_options.num_steps, sim.solver_options.sens_forw = dt, int(plant_steps), False
+        plant = BatchSimSolver(sim, B)
+    fe = PathFollowingFrontEnd(s)
+    s.set("x0", 0, m["x0"])
+    s.set_all("x", np.tile(m["x0"][:, None, :], (1, N + 1, 1)))        # acados' own initial iterate: x_k = x0, u = 0
+    s.set_all("u", np.zeros((B, N, 2)))
+    fe.reset(m["waypoints"])
+    fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"])
+    npts = m["waypoints"].shape[1]
+    fails = np.zeros(ticks, dtype=int)
+    active0 = None
+    s.sync()
+    t0 = time.perf_counter()
+    for i in range(ticks):
+        fe.prepare()
+        s.solve_async()
+        if i == 0:
+            active0 = fe.publish()["active"].copy()                      # (the one read-back inside the loop)
+        else:
+            fe.publish(fetch=False)
+        if plant is None:
+            s.advance()
+        else:
+            s.advance_sim(plant)
+        if (i + 1) % RING == 0 or i == ticks - 1:                         # the device counts the failed solves: fetched once per RING ticks
+            n = (i % RING) + 1
+            fails[i + 1 - n:i + 1] = s.fail_counts(n)
+    s.sync()
+    el = time.perf_counter() - t0
+    st = fe.state()
+    last_active = fe.publish()["active"]                                 # (publishes the last tick again: the same values)
+    k = st["wp_index"]
+    # yref rewrites the rule predicts: every instance active at tick 0, plus one per switch onto a further segment - a switch whose next tick
+    # has not come yet (the run ended on the switch tick) and the last switch (mission over: nothing is written) do not count
+    new_segments = np.minimum(k, npts - 1) - 1 - ((k > 1) & (k < npts) & (last_active == 0))
+    res = dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, finish_tick=st["finish_tick"], min_clearance=st["min_clearance"],
+               waypoint_index=k, switches=k - 1, new_segments=new_segments, active_at_tick_0=int(active0.sum()), yref_writes=st["yref_writes"],
+               failures_per_tick=fails, final_status=s.get_int("status"), final_pose=s.get("x0", 0)[:, [10, 11, 0]])
+    if not quiet:
+        fin = st["finish_tick"] >= 0
+        print("%d missions x %d ticks in %.2f s (%.1f ticks/s, %.0f mission-ticks/s)" % (B, ticks, el, ticks / el, B * ticks / el))
+        if fin.any():
+            print("finished: %d of %d, at ticks %d .. %d" % (fin.sum(), B, st["finish_tick"][fin].min(), st["finish_tick"][fin].max()))
+        else:
+            print("finished: 0 of %d" % B)
+        mc = st["min_clearance"]
+        print("minimum clearance to the keep-out circle (R + 0.5 m): worst %.4f m, median %.4f m" % (mc.min(), np.median(mc)))
+        print("failed solves: %d over all ticks (%d ticks with at least one); yref rewrites: %d of %d instance-ticks"
+              % (fails.sum(), (fails > 0).sum(), st["yref_writes"], B * ticks))
+    s.close()
+    if plant is not None:
+        plant.close()
+    return res
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--ticks", type=int, default=560)
+    ap.add_argument("--horizon", type=int, default=40)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--plant-steps", type=int, default=None,
+                    help="integrate the plant in this many RK4 steps per tick (default: the plant is the controller's prediction x_1)")
+    a = ap.parse_args()
+    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps)

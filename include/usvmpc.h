@@ -336,6 +336,41 @@ int usvmpc_guidance_sense(usvmpc_handle *h, const double *pose, const double *wo
                           double *obstacles, int *n_obstacles);
 int usvmpc_guidance_publish(usvmpc_handle *h, double *heading, double *r_des, double *speed, double *ye, int *active);
 int usvmpc_guidance_state(usvmpc_handle *h, int *wp_index, float *past_psied);
+/* ---- Path-following front end (model usv_model_pf_ca only; any other model: USVMPC_E_ARG with a message): the arithmetic either side
+ * of the solver call in the reference's path-following ROS node, batched on the device (class NMPC in catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp;
+ * nmpc_pf_ca.cpp is the same file; the arithmetic: csrc/pf_guidance.hpp).  Per-instance state (waypoint index k, past thrust, the reference
+ * triple last written, running minimum clearance) lives in the handle.  Arrays are host pointers, instance-major.
+ *   reset   = main(), new waypoint list                  :392-401   waypoints [B][2*npts], npts >= 2; k = 1, past thrust 0 (:172-173); switches
+ *             "static_obstacles" on; refused while option "obstacle_tracks" is on (the tracks own p)
+ *   world   = the obstacle field, uploaded once: world [B][n_world][3] = NED (X, Y, R), 0 <= n_world <= 64; an obstacle is visible when
+ *             sqrt((X-nedx)^2 + (Y-nedy)^2) < max_radius (obstacle_sim_node.py:71).  The node itself has no obstacle callback: the nearest K
+ *             visible ones by distance - (R + 0.5), ties by list index, go to stage 0 of p in the NED frame, bit for bit, and
+ *             lh = (R + 0.5) + margin (option "pf_lh_margin", default 0.2: scripts/usv_pf_ca/main.py:126); unused slots (1000, 1000), lh 0
+ *   prepare = velocityCallback / waypoint_manager / control (input part)   :198-206, :226-268, :273-335
+ *             HOST-FED: vel_uvr [B][3] = (u, v, r), pose [B][3] = (nedx, nedy, psi); past thrust from the front end's state; returns when the
+ *             arrays may be reused.  DEVICE-RESIDENT: both NULL - the vessel's state is read from the handle's own x0 as usvmpc_advance /
+ *             usvmpc_advance_sim left it (u, v, r = x0[3..5]; psi, nedx, nedy = x0[0], x0[10], x0[11]; past thrust = x0[12..13]) and the
+ *             solver inputs are written in place: the call enqueues on the handle's stream and returns, no synchronisation.
+ *             Per instance: distance to the segment's end > 1: ACTIVE - x0, and yref / yref_e ONLY when (sin ak, cos ak, u_des) differ bit
+ *             for bit from what the front end last wrote there (or the caller has written yref / yref_e since, by usvmpc_set or through a
+ *             device pointer: then every active instance is rewritten once); distance <= 1: SWITCH TICK - k += 1 and nothing else (:252-256:
+ *             x0, yref and the published values keep what they hold; the batched solve still runs); k >= npts: MISSION OVER.  Obstacles and the
+ *             running minimum clearance are updated for every instance whose mission is not over.  A pending host mirror is uploaded first;
+ *             usvmpc_get of "x0", "yref", "yref_e", "p", "lh" afterwards returns what the kernel wrote.  For the pipelined lineariser a prepare
+ *             counts as a caller write of yref (a handle driven by this front end linearises inside its solves).
+ *   publish = control (output part) :347-376   active: thr_port / thr_stbd = x_1[12], x_1[13] (kept as past thrust), e_u = (float)(0.7 - u),
+ *             e_ye = (float)(0 - ye), Tx = port + 0.78 stbd, Tz = (port - 0.78 stbd) 0.41 / 2 (the node's constants), speed 0.7; mission over:
+ *             thrusters and speed 0 (:260-266); switch tick: unchanged.  active [B]: 1 for an active tick.  Any output may be NULL; with all NULL the
+ *             call only enqueues, otherwise it synchronises the stream.
+ *   state   : wp_index [B], finish_tick [B] (prepares since reset, from 0, at the first one that found the mission over; -1 before),
+ *             min_clearance [B] (smallest distance - (R + 0.5) over the visible obstacles, any tick; 1e300 before the first update),
+ *             yref_writes [1] (instance rewrites of yref since reset).  Any may be NULL. */
+int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts);
+int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius);
+int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pose);
+int usvmpc_pf_publish(usvmpc_handle *h, double *thr_port, double *thr_stbd, double *Tx, double *Tz, float *e_u, float *e_ye, double *speed,
+                      int *active);
+int usvmpc_pf_state(usvmpc_handle *h, int *wp_index, int *finish_tick, double *min_clearance, long long *yref_writes);
 /* Profiling aid: stream `nplanes` workspace planes with the solver kernels' access instruction
  * (kernel usv_calib_stream) and report the exact byte counts, to calibrate HBM PMC counters.
  * Overwrites solver scratch; the next usvmpc_solve re-initialises it. */

@@ -67,7 +67,8 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_guidance_publish", "usvmpc_guidance_state", "usvmpc_device_bytes", "usvmpc_last_error",
            "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval",
            "usvmpc_sim_create", "usvmpc_sim_destroy", "usvmpc_sim_set", "usvmpc_sim_solve", "usvmpc_sim_get", "usvmpc_sim_get_device_ptr",
-           "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step"]
+           "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step",
+           "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state"]
 
 
 _libs = {}
@@ -126,6 +127,12 @@ def load(path):
     L.usvmpc_guidance_sense.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.c_double, _dp, _ip]
     L.usvmpc_guidance_publish.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
     L.usvmpc_guidance_state.argtypes = [C.c_void_p, _ip, C.POINTER(C.c_float)]
+    _fp = C.POINTER(C.c_float)
+    L.usvmpc_pf_reset.argtypes = [C.c_void_p, _dp, C.c_int]
+    L.usvmpc_pf_world.argtypes = [C.c_void_p, _dp, C.c_int, C.c_double]
+    L.usvmpc_pf_prepare.argtypes = [C.c_void_p, _dp, _dp]
+    L.usvmpc_pf_publish.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _fp, _dp, _ip]
+    L.usvmpc_pf_state.argtypes = [C.c_void_p, _ip, _ip, _dp, C.POINTER(C.c_longlong)]
     L.usvmpc_debug_model_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_obstacle_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_sim_create.argtypes = [C.POINTER(SimDesc), C.POINTER(C.c_void_p)]

@@ -25,6 +25,7 @@
 #include "linearize.hpp"
 #include "models.hpp"
 #include "obstacle_tracks.hpp"
+#include "pf_guidance.hpp"
 #include "qp_ipm.hpp"
 #include "sim.hpp"
 #include "cond_launch.hpp"
@@ -369,6 +370,142 @@ __global__ void __launch_bounds__(256) usv_obstacle_step(double *pos, const doub
     clear_min[b] = (reset || c < m) ? c : m;
 }
 
+// ---- Path-following front end (model usv_model_pf_ca; the arithmetic: pf_guidance.hpp).
+constexpr int PF_GROUP = 64; // instances per workgroup of usv_pf_prepare
+
+static __global__ void usv_pf_reset(PfPtrs F, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) *F.yref_writes = 0ull;
+    if (b >= B) return;
+    F.k[b] = 1; // main :394
+    F.phase[b] = PF_SWITCH; // (nothing to publish yet)
+    F.finish_tick[b] = -1;
+    F.past[2 * b] = 0.0; F.past[2 * b + 1] = 0.0; // :172-173
+    F.last[3 * b] = F.last[3 * b + 1] = F.last[3 * b + 2] = __builtin_nan("");
+    F.u[b] = 0.0; F.ye[b] = 0.0;
+    F.min_clear[b] = 1e300;
+    F.thr_port[b] = 0.0; F.thr_stbd[b] = 0.0; F.Tx[b] = 0.0; F.Tz[b] = 0.0; F.speed[b] = 0.0;
+    F.e_u[b] = 0.0f; F.e_ye[b] = 0.0f;
+    F.active[b] = 0;
+}
+
+// usv_pf_prepare: one workgroup per PF_GROUP consecutive instances, in two steps.
+// 1. Decide: the first wave, one lane per instance - vessel state (host-fed arrays or x0 in place), waypoint manager, x0, the nearest-K
+//    selection over the instance's world list (L <= 64; the distances in LDS, one column per lane) into stage 0 of p / lh, and whether the
+//    instance's reference rows must be rewritten: only when (sin ak, cos ak, u_des) differ bit for bit from what it last wrote, or the caller
+//    may have written yref (stale).  The triple and the decision go to LDS.  These are 14 + 3L + 3K doubles per instance: small, scattered.
+// 2. Stream: the workgroup's yref rows are ONE contiguous run of PF_GROUP * N * 16 doubles (335 MB over 65 536 instances at N = 40 - the
+//    reference rewrites it every tick).  All 256 threads walk it in 16-byte stores, thread t the t-th pair of each 4 KiB pass (a wave's stores
+//    cover 1 KiB without gaps), skipping the instances that keep their rows; 256 % 8 == 0, so a thread always holds the same pair of a row and
+//    only its instance moves on.  yref_e (7 pairs per instance) likewise.  No thread walks an instance's rows alone.
+__global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int tick, int stale)
+{
+    const DevSpec &S = *P.spec;
+    const int B = S.B, N = S.N, K = S.K;
+    __shared__ double s_d[PF_LMAX * PF_GROUP];
+    __shared__ double s_ref[PF_GROUP][3];
+    __shared__ int s_write[PF_GROUP];
+    __shared__ unsigned s_count;
+    const int t = (int)threadIdx.x;
+    const long b0 = (long)blockIdx.x * PF_GROUP;
+    const int cnt = (int)((long)B - b0 < (long)PF_GROUP ? (long)B - b0 : (long)PF_GROUP);
+    if (t == 0) s_count = 0u;
+    if (t < PF_GROUP) s_write[t] = 0;
+    __syncthreads();
+    if (t < cnt) {
+        const long b = b0 + t;
+        double *x0 = const_cast<double *>(P.x0) + b * PF_NX;
+        double u, v, r, psi, nedx, nedy, pp, ps;
+        if (F.vel) {
+            u = F.vel[3 * b]; v = F.vel[3 * b + 1]; r = F.vel[3 * b + 2];
+            nedx = F.pose[3 * b]; nedy = F.pose[3 * b + 1]; psi = F.pose[3 * b + 2];
+            pp = F.past[2 * b]; ps = F.past[2 * b + 1];
+        } else { // as usv_advance / usv_advance_sim left it
+            psi = x0[0]; u = x0[3]; v = x0[4]; r = x0[5]; nedx = x0[10]; nedy = x0[11]; pp = x0[12]; ps = x0[13];
+        }
+        u = pf_fix_u(u);
+        const int k = F.k[b];
+        PfSegment seg;
+        const int phase = pf_waypoint(F.wp + b * 2 * F.npts, F.npts, k, nedx, nedy, seg);
+        F.phase[b] = phase;
+        if (phase == PF_SWITCH) F.k[b] = k + 1;
+        if (phase == PF_OVER && F.finish_tick[b] < 0) F.finish_tick[b] = tick;
+        if (phase != PF_OVER) {
+            const int L = F.nworld < PF_LMAX ? F.nworld : PF_LMAX;
+            const double dmin = pf_select(F.world + b * 3 * F.nworld, L, K, nedx, nedy, F.max_radius, F.margin, s_d + t, PF_GROUP,
+                                          const_cast<double *>(P.p) + b * (long)(N + 1) * 2 * K, const_cast<double *>(P.lh) + b * (long)N * K, nullptr);
+            if (dmin < F.min_clear[b]) F.min_clear[b] = dmin;
+        }
+        if (phase == PF_ACTIVE) {
+            pf_x0(psi, u, v, r, seg, nedx, nedy, pp, ps, x0);
+            F.u[b] = u; F.ye[b] = seg.ye;
+        }
+        double *last = F.last + 3 * b;
+        if (pf_yref_write(phase, stale != 0, last, seg)) {
+            last[0] = seg.sin_ak; last[1] = seg.cos_ak; last[2] = seg.u_des;
+            s_ref[t][0] = seg.sin_ak; s_ref[t][1] = seg.cos_ak; s_ref[t][2] = seg.u_des;
+            s_write[t] = 1;
+            atomicAdd(&s_count, 1u);
+        } else if (stale) {
+            last[0] = last[1] = last[2] = __builtin_nan(""); // (rows the caller may have overwritten: rewritten at the instance's next active tick)
+        }
+    }
+    __syncthreads();
+    const unsigned nwrite = s_count;
+    if (nwrite == 0u) return;
+    if (t == 0) atomicAdd(F.yref_writes, (unsigned long long)nwrite);
+    {
+        double2 *row = reinterpret_cast<double2 *>(const_cast<double *>(P.yref)) + b0 * (long)N * (PF_NY / 2);
+        const int per = N * (PF_NY / 2), total = cnt * per; // pairs per instance / of the workgroup
+        const int pair = t & 7;
+        int inst = 0, rem = t; // j = inst * per + rem
+        while (rem >= per) { rem -= per; inst++; }
+        for (int j = t; j < total; j += 256) {
+            if (s_write[inst]) {
+                double2 o;
+                o.x = pf_yref_entry(2 * pair, s_ref[inst][0], s_ref[inst][1], s_ref[inst][2]);
+                o.y = pf_yref_entry(2 * pair + 1, s_ref[inst][0], s_ref[inst][1], s_ref[inst][2]);
+                row[j] = o;
+            }
+            rem += 256;
+            while (rem >= per) { rem -= per; inst++; }
+        }
+    }
+    {
+        double2 *row = reinterpret_cast<double2 *>(const_cast<double *>(P.yref_e)) + b0 * (long)(PF_NX / 2);
+        for (int j = t; j < cnt * (PF_NX / 2); j += 256) {
+            const int inst = j / (PF_NX / 2), pair = j - inst * (PF_NX / 2);
+            if (!s_write[inst]) continue;
+            double2 o;
+            o.x = pf_yref_entry(2 * pair, s_ref[inst][0], s_ref[inst][1], s_ref[inst][2]);
+            o.y = pf_yref_entry(2 * pair + 1, s_ref[inst][0], s_ref[inst][1], s_ref[inst][2]);
+            row[j] = o;
+        }
+    }
+}
+
+// usv_pf_publish: the node's outputs after the solve, one lane per instance (a dozen scalars each).  An active instance reads the thrusters
+// from x_1 and keeps them as its past thrust; one whose mission is over publishes zero thrust and speed; a switch tick publishes nothing.
+__global__ void __launch_bounds__(256) usv_pf_publish(DevPtrs P, PfPtrs F)
+{
+    const DevSpec &S = *P.spec;
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= (long)S.B) return;
+    const int phase = F.phase[b];
+    F.active[b] = phase == PF_ACTIVE ? 1 : 0;
+    if (phase == PF_ACTIVE) {
+        const double *x1 = P.x + (b * (S.N + 1) + 1) * PF_NX;
+        PfOutputs o;
+        pf_publish(x1[12], x1[13], PF_SPEED, F.u[b], F.ye[b], o);
+        F.thr_port[b] = o.thr_port; F.thr_stbd[b] = o.thr_stbd; F.Tx[b] = o.Tx; F.Tz[b] = o.Tz; F.speed[b] = o.speed;
+        F.e_u[b] = o.e_u; F.e_ye[b] = o.e_ye;
+        F.past[2 * b] = o.thr_port; F.past[2 * b + 1] = o.thr_stbd; // :359-360
+    } else if (phase == PF_OVER) { // :260-266
+        F.thr_port[b] = 0.0; F.thr_stbd[b] = 0.0; F.speed[b] = 0.0;
+    }
+}
+
 // AcadosSimSolver's solve (usvmpc_sim_solve): x, u -> x_next (and S_forw = [Sx | Su] when SENS), sim.hpp
 template <class M, bool SENS>
 __global__ void __launch_bounds__(256) usv_sim(const double *x, const double *u, double *xn, double *S, long B, double T, int steps)
@@ -510,6 +647,15 @@ struct usvmpc_handle {
     double *gd_psi;
     double *gd_world;   // [B][n_world][3] world obstacles of the last usvmpc_guidance_sense
     size_t gd_world_cap;
+    // Path-following front end (usvmpc_pf_*, model usv_model_pf_ca): device buffers on first use; pf_ready after usvmpc_pf_reset
+    PfPtrs pf;
+    bool pf_alloc, pf_ready;
+    bool pf_stale;            // the caller may have written yref / yref_e since the front end last did: the next prepare rewrites every active instance
+    int pf_tick;              // prepares since the last reset
+    int pf_npts_cap;
+    size_t pf_world_cap;      // doubles
+    double pf_margin;         // option "pf_lh_margin"
+    double *pf_vel, *pf_pose; // [B][3] staging of the host-fed mode
     bool sort_enabled;
     bool sort_two;            // sort key: the larger of the last two iteration counts instead of the last one (option, default off)
     bool merge_rows;
@@ -984,6 +1130,7 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
         stage = stage < 0 ? -1 : 0;
     int rc = lookup(h, field, stage, set, f);
     if (rc) return rc;
+    if (set && (std::string(field) == "yref" || std::string(field) == "yref_e")) h->pf_stale = true; // (the path-following front end rewrites its rows)
     if ((int)n != f.n) {
         h->err = std::string("mismatching dimension for field '") + field + "': expected " + std::to_string(f.n) +
                  ", got " + std::to_string(n);
@@ -1857,6 +2004,9 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->sort_enabled = true;
     h->sort_two = false;
     h->merge_rows = true;
+    std::memset(&h->pf, 0, sizeof(h->pf));
+    h->pf_alloc = false; h->pf_ready = false; h->pf_stale = true; h->pf_tick = 0; h->pf_npts_cap = 0; h->pf_world_cap = 0; h->pf_margin = 0.2;
+    h->pf_vel = nullptr; h->pf_pose = nullptr;
     h->gd_ready = false; h->gd_npts_cap = 0; h->gd_psi = nullptr; h->gd_world = nullptr; h->gd_world_cap = 0;
     std::memset(&h->gd, 0, sizeof(h->gd));
     TRY_C(dev_alloc(h, &P.ws, (N + 1) * (size_t)ws_planes(h->nx, h->nu, h->kch, h->soft, model_mat_planes(h->desc.model), h->spec.any_bsoft != 0) * stride, true));
@@ -2014,6 +2164,7 @@ int usvmpc_get_device_ptr(usvmpc_handle *h, const char *field, void **dptr)
                   : s == "obs_tmin" ? (const void *)P.obs_tmin
                   : s == "nlp_res" ? (const void *)P.nlp_res : s == "sqp_iter" ? (const void *)P.sqp_iter : nullptr;
     if (!p) { h->err = "unknown field '" + s + "'"; return USVMPC_E_FIELD; }
+    if (s == "yref" || s == "yref_e") h->pf_stale = true; // (the caller may write the rows behind the path-following front end's back)
     {   // the caller is about to read (or write) device memory directly: pending host writes go up, and the host mirror no longer
         // vouches for the device's x / u
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2297,11 +2448,17 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         if (value == 0.0) { h->tracks_on = false; return 0; } // (p stays as it stands and is the caller's again)
         if (h->K == 0) { h->err = "obstacle_tracks: this model has no obstacle rows (K = 0)"; return USVMPC_E_ARG; }
         if (!h->tracks_pos_set) { h->err = "obstacle_tracks: set \"obs_pos\" before switching the option on"; return USVMPC_E_ARG; }
+        if (h->pf_ready) { h->err = "obstacle_tracks: the path-following front end owns p on this handle"; return USVMPC_E_ARG; }
         h->tracks_on = true;
         h->tracks_dirty = true;
         return 0;
     }
     if (s == "obstacle_step_on_advance") { h->step_on_advance = value != 0.0; return 0; }
+    if (s == "pf_lh_margin") { // the path-following front end's lh = (R + boat radius) + margin (scripts/usv_pf_ca/main.py:126: 0.2)
+        if (!(value >= 0.0) || value - value != 0.0) { h->err = "pf_lh_margin must be finite and non-negative"; return USVMPC_E_ARG; }
+        h->pf_margin = value;
+        return 0;
+    }
     {
         const int rcs = spec_cancel(h); // (options change maps, layouts or launches: a lineariser that ran ahead is not trusted across them)
         if (rcs) return rcs;
@@ -2571,6 +2728,159 @@ int usvmpc_guidance_state(usvmpc_handle *h, int *wp_index, float *past_psied)
     const size_t B = h->B;
     if (wp_index) HIP_TRY(h, hipMemcpyAsync(wp_index, h->gd.k, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (past_psied) HIP_TRY(h, hipMemcpyAsync(past_psied, h->gd.past_psied, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- path-following front end (usv_model_pf_ca only): see pf_guidance.hpp
+static int pf_check(usvmpc_handle *h)
+{
+    if (h->desc.model != USVMPC_MODEL_PF_CA) { h->err = "the path-following front end (usvmpc_pf_*) belongs to usv_model_pf_ca"; return USVMPC_E_ARG; }
+    return 0;
+}
+
+static int pf_alloc(usvmpc_handle *h)
+{
+    if (h->pf_alloc) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t B = h->B;
+    PfPtrs &F = h->pf;
+    if (dev_alloc(h, &F.k, B, true) || dev_alloc(h, &F.phase, B, true) || dev_alloc(h, &F.finish_tick, B, true) || dev_alloc(h, &F.past, B * 2, true) ||
+        dev_alloc(h, &F.last, B * 3, true) || dev_alloc(h, &F.u, B, true) || dev_alloc(h, &F.ye, B, true) || dev_alloc(h, &F.min_clear, B, true) ||
+        dev_alloc(h, &F.yref_writes, 1, true) || dev_alloc(h, &F.thr_port, B, true) || dev_alloc(h, &F.thr_stbd, B, true) ||
+        dev_alloc(h, &F.Tx, B, true) || dev_alloc(h, &F.Tz, B, true) || dev_alloc(h, &F.speed, B, true) || dev_alloc(h, &F.e_u, B, true) ||
+        dev_alloc(h, &F.e_ye, B, true) || dev_alloc(h, &F.active, B, true) || dev_alloc(h, &h->pf_vel, B * 3, true) ||
+        dev_alloc(h, &h->pf_pose, B * 3, true))
+        return USVMPC_E_HIP;
+    F.max_radius = 100.0;
+    h->pf_alloc = true;
+    return 0;
+}
+
+int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!waypoints || npts < 2) { h->err = "pf_reset: a waypoint list of at least two points is needed"; return USVMPC_E_ARG; }
+    if (h->tracks_on) { h->err = "pf_reset: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    rc = pf_alloc(h);
+    if (rc) return rc;
+    PfPtrs &F = h->pf;
+    const size_t B = h->B;
+    if (npts > h->pf_npts_cap) {
+        dev_free(h, const_cast<double *>(F.wp), B * 2 * (size_t)h->pf_npts_cap * sizeof(double));
+        F.wp = nullptr; h->pf_npts_cap = 0;
+        double *d = nullptr;
+        if (dev_alloc(h, &d, B * 2 * (size_t)npts, true)) return USVMPC_E_HIP;
+        F.wp = d;
+        h->pf_npts_cap = npts;
+    }
+    F.npts = npts;
+    HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.wp), waypoints, B * 2 * (size_t)npts * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(usv_pf_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, F, (int)B);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->pf_ready = true; h->pf_stale = true; h->pf_tick = 0;
+    if (!h->spec.p_static) return usvmpc_set_option(h, "static_obstacles", 1.0);
+    return 0;
+}
+
+int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (n_world < 0 || n_world > PF_LMAX) { h->err = "pf_world: n_world must lie in 0.." + std::to_string(PF_LMAX); return USVMPC_E_ARG; }
+    if (n_world > 0 && !world) { h->err = "pf_world: null world list"; return USVMPC_E_ARG; }
+    if (!(max_radius == max_radius)) { h->err = "pf_world: max_radius is NaN"; return USVMPC_E_ARG; }
+    rc = pf_alloc(h);
+    if (rc) return rc;
+    PfPtrs &F = h->pf;
+    const size_t need = (size_t)h->B * (size_t)n_world * 3;
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare that reads the old list may be in flight)
+    if (need > h->pf_world_cap) {
+        dev_free(h, const_cast<double *>(F.world), h->pf_world_cap * sizeof(double));
+        F.world = nullptr; h->pf_world_cap = 0;
+        double *d = nullptr;
+        if (dev_alloc(h, &d, need, false)) return USVMPC_E_HIP;
+        F.world = d;
+        h->pf_world_cap = need;
+    }
+    if (need) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.world), world, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    F.nworld = n_world;
+    F.max_radius = max_radius;
+    return 0;
+}
+
+int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pose)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
+    if ((vel_uvr == nullptr) != (pose == nullptr)) { h->err = "pf_prepare: give both vel_uvr and pose, or neither (device-resident)"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = mirror_flush(h);
+    if (rc) return rc;
+    rc = spec_cancel(h); // (a caller write of yref as far as the pipelined lineariser is concerned: pf_guidance.hpp)
+    if (rc) return rc;
+    PfPtrs F = h->pf;
+    F.margin = h->pf_margin;
+    const size_t B = h->B;
+    if (vel_uvr) {
+        HIP_TRY(h, hipMemcpyAsync(h->pf_vel, vel_uvr, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->pf_pose, pose, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        F.vel = h->pf_vel; F.pose = h->pf_pose;
+    } else {
+        F.vel = nullptr; F.pose = nullptr;
+    }
+    hipLaunchKernelGGL(usv_pf_prepare, dim3((unsigned)((B + PF_GROUP - 1) / PF_GROUP)), dim3(256), 0, h->stream, h->ptrs, F, h->pf_tick, h->pf_stale ? 1 : 0);
+    HIP_TRY(h, hipGetLastError());
+    h->pf_stale = false;
+    h->pf_tick++;
+    if (vel_uvr) HIP_TRY(h, hipStreamSynchronize(h->stream)); // (the copies read caller memory: it must be reusable when this call returns)
+    return 0;
+}
+
+int usvmpc_pf_publish(usvmpc_handle *h, double *thr_port, double *thr_stbd, double *Tx, double *Tz, float *e_u, float *e_ye, double *speed,
+                      int *active)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const PfPtrs &F = h->pf;
+    const size_t B = h->B;
+    hipLaunchKernelGGL(usv_pf_publish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, F);
+    HIP_TRY(h, hipGetLastError());
+    if (thr_port) HIP_TRY(h, hipMemcpyAsync(thr_port, F.thr_port, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (thr_stbd) HIP_TRY(h, hipMemcpyAsync(thr_stbd, F.thr_stbd, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (Tx) HIP_TRY(h, hipMemcpyAsync(Tx, F.Tx, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (Tz) HIP_TRY(h, hipMemcpyAsync(Tz, F.Tz, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (e_u) HIP_TRY(h, hipMemcpyAsync(e_u, F.e_u, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (e_ye) HIP_TRY(h, hipMemcpyAsync(e_ye, F.e_ye, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (speed) HIP_TRY(h, hipMemcpyAsync(speed, F.speed, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (active) HIP_TRY(h, hipMemcpyAsync(active, F.active, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (thr_port || thr_stbd || Tx || Tz || e_u || e_ye || speed || active) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int usvmpc_pf_state(usvmpc_handle *h, int *wp_index, int *finish_tick, double *min_clearance, long long *yref_writes)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const PfPtrs &F = h->pf;
+    const size_t B = h->B;
+    if (wp_index) HIP_TRY(h, hipMemcpyAsync(wp_index, F.k, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (finish_tick) HIP_TRY(h, hipMemcpyAsync(finish_tick, F.finish_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (min_clearance) HIP_TRY(h, hipMemcpyAsync(min_clearance, F.min_clear, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (yref_writes) HIP_TRY(h, hipMemcpyAsync(yref_writes, F.yref_writes, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }

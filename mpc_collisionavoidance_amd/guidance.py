@@ -73,3 +73,112 @@ class GuidanceFrontEnd:
         self.s._check(self._lib.usvmpc_guidance_state(self.s._h, k.ctypes.data_as(_capi._ip),
                                                       pp.ctypes.data_as(C.POINTER(C.c_float))))
         return k, pp
+
+
+def _as_waypoints(waypoints, B):
+    """[B, npts, 2], [B, 2 npts] or one [npts, 2] list for every instance -> contiguous [B, 2 npts]; npts >= 2."""
+    w = np.ascontiguousarray(waypoints, dtype=np.float64)
+    if w.ndim == 2 and w.shape[1] == 2:
+        # [npts, 2]: one list for all.  (A [B, 2] array cannot be a per-instance list: that would be one point each.)
+        w = np.tile(w[None], (B, 1, 1))
+    if w.ndim not in (2, 3):
+        raise Exception("waypoints: expected [%d, npts, 2] or [npts, 2], got %s" % (B, list(w.shape)))
+    if w.shape[0] != B:
+        raise Exception("waypoints: expected [%d, npts, 2] or [npts, 2], got %s" % (B, list(w.shape)))
+    w = np.ascontiguousarray(w.reshape(B, -1))
+    if w.shape[1] % 2 or w.shape[1] < 4:
+        raise Exception("waypoints: at least two (x, y) points per instance are needed, got %d values" % w.shape[1])
+    if not np.isfinite(w).all():
+        raise Exception("waypoints contain NaN or infinity")
+    return w
+
+
+def _as_world(world, B, lmax=64):
+    """World obstacles (X, Y, R): [B, L, 3], one [L, 3] list for every instance, or None / empty for no obstacle -> contiguous [B, L, 3]."""
+    if world is None:
+        return np.zeros((B, 0, 3))
+    w = np.asarray(world, dtype=np.float64)
+    if w.size == 0:
+        return np.zeros((B, 0, 3))
+    if w.shape[-1] != 3 or w.ndim not in (2, 3):
+        raise Exception("world: expected [%d, L, 3] or [L, 3] rows of (X, Y, R), got %s" % (B, list(w.shape)))
+    if w.ndim == 2:
+        w = np.tile(w[None], (B, 1, 1))
+    if w.shape[0] != B:
+        raise Exception("world: expected %d instances, got %d" % (B, w.shape[0]))
+    if w.shape[1] > lmax:
+        raise Exception("world: at most %d obstacles per instance, got %d" % (lmax, w.shape[1]))
+    if np.isnan(w).any():
+        raise Exception("world contains NaN")
+    return np.ascontiguousarray(w)
+
+
+class PathFollowingFrontEnd:
+    """Batched counterpart of the reference's path-following ROS node around the solver (class NMPC,
+    catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp = nmpc_pf_ca.cpp) for usv_model_pf_ca: waypoint manager, x0 and reference assembly, nearest-K
+    obstacle selection, published thrusts.  The arithmetic runs on the device (csrc/pf_guidance.hpp).  Two ways to drive it:
+
+        host-fed          prepare(vel_uvr, pose) -> solve -> publish()         (the ROS node's callbacks)
+        device-resident   prepare() -> solve_async -> publish(fetch=False) -> advance / advance_sim
+                          the vessel's state is read from the solver's own x0; no host array, no synchronisation
+    """
+
+    def __init__(self, solver):
+        if solver.ocp.model.name != "usv_model_pf_ca" or getattr(solver, "generated", False):
+            raise Exception("the path-following front end belongs to usv_model_pf_ca (this solver's model: %s)" % solver.ocp.model.name)
+        self.s = solver
+        self.B = solver.B
+        self._lib = solver._lib
+
+    def reset(self, waypoints):
+        """New waypoint list: [B, npts, 2] (or [npts, 2] for all).  k = 1, past thrust 0; the solver switches to static obstacles."""
+        w = _as_waypoints(waypoints, self.B)
+        self.s._check(self._lib.usvmpc_pf_reset(self.s._h, w.ctypes.data_as(_capi._dp), w.shape[1] // 2))
+
+    def set_world(self, world, max_radius=100.0, margin=None):
+        """The obstacle field (X, Y, R) in NED: [B, L, 3] or [L, 3] for all, L <= 64; uploaded once.  margin: lh = (R + 0.5) + margin."""
+        w = _as_world(world, self.B)
+        if margin is not None:
+            self.s.set_option("pf_lh_margin", float(margin))
+        self.s._check(self._lib.usvmpc_pf_world(self.s._h, w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius)))
+
+    def prepare(self, vel_uvr=None, pose=None):
+        """vel_uvr [B,3] = (u, v, r), pose [B,3] = (nedx, nedy, psi); both None: device-resident (enqueues and returns)."""
+        if (vel_uvr is None) != (pose is None):
+            raise Exception("prepare: give both vel_uvr and pose, or neither")
+        if vel_uvr is None:
+            self.s._check(self._lib.usvmpc_pf_prepare(self.s._h, None, None))
+            return
+        v = _as_rows(vel_uvr, self.B, "vel_uvr")
+        p = _as_rows(pose, self.B, "pose")
+        self.s._check(self._lib.usvmpc_pf_prepare(self.s._h, v.ctypes.data_as(_capi._dp), p.ctypes.data_as(_capi._dp)))
+
+    def publish(self, fetch=True):
+        """After the solve: dict(thr_port, thr_stbd, Tx, Tz, e_u, e_ye, speed, active).  fetch=False: enqueue only, returns None."""
+        if not fetch:
+            self.s._check(self._lib.usvmpc_pf_publish(self.s._h, None, None, None, None, None, None, None, None))
+            return None
+        port, stbd, tx, tz, sp = (np.zeros(self.B) for _ in range(5))
+        eu, eye = np.zeros(self.B, dtype=np.float32), np.zeros(self.B, dtype=np.float32)
+        act = np.zeros(self.B, dtype=np.int32)
+        fp = C.POINTER(C.c_float)
+        self.s._check(self._lib.usvmpc_pf_publish(self.s._h, port.ctypes.data_as(_capi._dp), stbd.ctypes.data_as(_capi._dp),
+                                                  tx.ctypes.data_as(_capi._dp), tz.ctypes.data_as(_capi._dp), eu.ctypes.data_as(fp),
+                                                  eye.ctypes.data_as(fp), sp.ctypes.data_as(_capi._dp), act.ctypes.data_as(_capi._ip)))
+        return dict(thr_port=port, thr_stbd=stbd, Tx=tx, Tz=tz, e_u=eu, e_ye=eye, speed=sp, active=act)
+
+    def state(self):
+        """dict(wp_index [B], finish_tick [B] (-1: not finished), min_clearance [B], yref_writes)."""
+        k, ft = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        mc = np.zeros(self.B)
+        n = C.c_longlong(0)
+        self.s._check(self._lib.usvmpc_pf_state(self.s._h, k.ctypes.data_as(_capi._ip), ft.ctypes.data_as(_capi._ip),
+                                                mc.ctypes.data_as(_capi._dp), C.byref(n)))
+        return dict(wp_index=k, finish_tick=ft, min_clearance=mc, yref_writes=int(n.value))
+
+
+def _as_rows(value, B, what):
+    a = np.ascontiguousarray(value, dtype=np.float64)
+    if a.size != 3 * B:
+        raise Exception("%s: expected [%d, 3], got %s" % (what, B, list(a.shape)))
+    return np.ascontiguousarray(a.reshape(B, 3))

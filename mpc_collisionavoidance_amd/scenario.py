@@ -288,3 +288,36 @@ def load_tracks(solver, wl):
     caller's).  From then on solver.advance / advance_sim move the obstacles along with the vehicle."""
     if wl["K"]:
         solver.set_obstacle_tracks(wl["obs_pos"], wl["obs_vel"])
+
+
+# ---- Path-following missions for usv_model_pf_ca behind guidance.PathFollowingFrontEnd: two legs, four obstacles beside them.
+PF_MISSION_WAYPOINTS = np.array([[4.0, -5.0], [4.0, 1.0], [8.0, 5.0]])
+PF_MISSION_OCP = dict(N=40, dt=0.05, sim_steps=5, K=4, max_radius=100.0, margin=0.2)
+
+
+def make_pf_missions(B, seed=0):
+    """B missions, instance b drawn from numpy.random.default_rng(seed + b) - an instance does not depend on the batch it is in.
+    Returns dict(waypoints [B,3,2], world [B,4,3] = (X, Y, R), x0 [B,14]).  Obstacle i lies beside leg i % 2: a point t ~ U(0.25, 0.8)
+    along the leg, moved 0.9 .. 1.6 m along the leg's unit normal (-dy, dx) / |.| to either side, radius 0.1 .. 0.4 m (keep-out radius
+    R + 0.5 + 0.2: the path stays free by 0.1 m at least, the vessel has to swerve for the nearer ones).  Nearer obstacles (0.5 .. 0.9 m)
+    leave a third of the missions stuck in front of a hard row: this spacing is deliberate.  The vessel starts at (4 +- 1, -5), heading
+    pi/2 +- 0.3, u = 0.001, everything else 0."""
+    w = PF_MISSION_WAYPOINTS
+    world = np.zeros((B, 4, 3))
+    x0 = np.zeros((B, 14))
+    for b in range(B):
+        rng = np.random.default_rng(seed + b)
+        for i in range(4):
+            leg = i % 2
+            t = rng.uniform(0.25, 0.8)
+            d = w[leg + 1] - w[leg]
+            c = w[leg] + t * d
+            n = np.array([-d[1], d[0]]) / np.hypot(d[0], d[1])
+            off = rng.uniform(0.9, 1.6)
+            sign = 1.0 if rng.uniform(0.0, 1.0) < 0.5 else -1.0
+            c = c + sign * off * n
+            world[b, i] = (c[0], c[1], rng.uniform(0.1, 0.4))
+        psi0 = np.pi / 2 + rng.uniform(-0.3, 0.3)
+        nedx = 4.0 + rng.uniform(-1.0, 1.0)
+        x0[b, 0], x0[b, 3], x0[b, 10], x0[b, 11] = psi0, 0.001, nedx, -5.0
+    return dict(waypoints=np.tile(w[None], (B, 1, 1)), world=world, x0=x0)
