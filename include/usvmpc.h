@@ -210,6 +210,8 @@ int usvmpc_handover_co_counts(usvmpc_handle *h, int n, int *finished, int *timeo
  * were used by the following solve / discarded because the caller wrote x, u or yref in between.  The lineariser only runs ahead after
  * two solves in a row without such a write, so a caller that sets yref every tick (the reference's protocol) discards none. */
 int usvmpc_pipeline_stats(usvmpc_handle *h, long *used, long *discarded);
+/* option "lin_pairs": how many lineariser launches of the handle so far ran the kernels that serve two (instance, stage) pairs per row */
+int usvmpc_lin_pair_launches(usvmpc_handle *h, long *launches);
 /* Which mapping the last solve (RTI, or the last launch of a full SQP) ran on: 0 = four instances per wavefront (one per 16-lane row: the throughput mapping), 1 = ONE
  * instance per wavefront (option "wide": the latency mapping north_star names - the four rows of the wave share out the stage-local
  * constraint-row work of four consecutive stages), 4 = one instance per workgroup of FOUR wavefronts (option "wide_waves": a whole CU
@@ -273,6 +275,9 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream);
  *   "lin_force_modes" (default 0; for tests) - 1 / 2: an RTI solve that would run the whole-batch lineariser runs the pipeline's two kernels
  *       in its place, the speculative one with every instance taken as final (1) or none (2: the fix-up pass then does all the work).  The
  *       same bits as 0;
+ *   "lin_pairs" (default 1 for usv_model and usv_model_pf_ca, 0 for usv_model_guidance_ca1 and a generated model) - 1: the lineariser's kernels that serve two (instance,
+ *       stage) pairs per 16-lane row (for models that declare the at most eight sensitivity columns to integrate); 0: one pair per row.  The
+ *       same bits either way; 1 on a model without the declaration is an error;
  *   "host_mirror" (default: on for handles whose caller-visible arrays total <= 1 MiB, i.e. the single-instance drop-in faces) -
  *       usvmpc_set writes a pinned host mirror and the next solve uploads the dirty fields in one asynchronous copy instead
  *       (ordering: a set becomes visible on the device with the NEXT launch of the handle, not at the call - except once a device pointer

@@ -372,6 +372,12 @@ class BatchOcpSolver:
         self._check(self._lib.usvmpc_pipeline_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def lin_pair_launches(self):
+        """Lineariser launches so far that ran the kernels with two (instance, stage) pairs per row (option "lin_pairs"; usvmpc_lin_pair_launches)."""
+        a = C.c_long()
+        self._check(self._lib.usvmpc_lin_pair_launches(self._h, C.byref(a)))
+        return a.value
+
     def last_mapping(self):
         """0: the last RTI solve ran four instances per wavefront; 1: one instance per wavefront (option "wide"); 4: one instance per
         workgroup of four wavefronts (option "wide_waves") - usvmpc_last_mapping."""

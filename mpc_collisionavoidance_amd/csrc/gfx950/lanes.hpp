@@ -177,6 +177,15 @@ USV_DEV double gmin(double v)
 // vector compares, conservative waits) although the control flow is wave-uniform by construction.
 USV_DEV int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// A value the compiler must take as new at this point.  For per-lane patterns made inside a loop whose body needs every register: derived from
+// a value it can see through they are loop-invariant, get hoisted and are then spilled (linearize.hpp run_pair_at under run_pair_marked).
+#define USV_LANES_OPAQUE 1
+USV_DEV int opaque(int v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 // no instruction may be scheduled across this point
 USV_DEV void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 

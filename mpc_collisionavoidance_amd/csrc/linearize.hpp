@@ -37,6 +37,21 @@ struct ModelCall<M, std::void_t<typename M::Pre>> {
         M::fjvp_pre(p, x, U, s, su, f, js);
     }
 };
+// ... also handing out the integrands of the model's quadrature entries (PairQuad, params.hpp); a model without such entries: the plain call
+template <class M, class = void>
+struct ModelQuad {
+    USV_DEV static void fjvp(const typename ModelCall<M>::Pre &p, const double *x, const double *U, const double *s, const double *su, double *f, double *js, double *)
+    {
+        ModelCall<M>::fjvp(p, x, U, s, su, f, js);
+    }
+};
+template <class M>
+struct ModelQuad<M, std::void_t<decltype(M::PAIR_NQUAD)>> {
+    USV_DEV static void fjvp(const typename M::Pre &p, const double *x, const double *U, const double *s, const double *su, double *f, double *js, double *qd)
+    {
+        M::fjvp_quad(p, x, U, s, su, f, js, qd);
+    }
+};
 
 // MULTI: more than one RK4 step per interval (the initial sensitivity column is then a carried variable
 // instead of a lane pattern the compiler rematerialises for free: 28 more VGPRs for M2, hence a separate build)
@@ -198,6 +213,198 @@ struct Linearize {
         });
         tile[WL::P_RB0 * LANES] = xlane ? bres : 0.0;
         // (obstacle rows are linearised inside the QP kernel from the iterate and (p, lh): QpIpm::obs_geom)
+    }
+
+    // ------------------------------------------------------------------------------------------------------------------------------------
+    // Two (instance, stage) pairs per 16-lane row, for models that say which at most 8 columns need integrating (PairCols, params.hpp):
+    // lane L serves half L >> 3 of the row and integrates the column of slot L & 7 with exactly the arithmetic the lane of that column runs
+    // in run_at; nothing crosses a row, every exchange is a gather among the 8 lanes of a half.  Each plane still has 16 entries, so a lane
+    // stores two of them (entry e = slot and slot + 8).  Control flow is uniform over a ROW: a half with nothing to do (nothing there,
+    // terminal stage, not ready, not marked) keeps its lanes going on valid addresses and stores nothing.  Same bits as run_at.
+    using PC = PairCols<M>;
+    static constexpr int HALF = LANES / 2;
+
+    // MODE 0 / 1 / 2: the halves in stage-major order (lin_order.hpp); n = (N + 1) Bp pairs
+    USV_DEV static void run_pair(const DevPtrs &P, long row)
+    {
+        const LinItem it = lin_pair_plain(row, lanes::lane() >> 3, P.spec->N, (long)P.spec->Bp);
+        run_pair_at(P, it.k < 0 ? 0 : it.k, it.g, it.k >= 0);
+    }
+
+    // MODE 3: the retire order; the two halves of a row are neighbouring stages of ONE instance
+    USV_DEV static void run_pair_item(const DevPtrs &P, long row)
+    {
+        const LinItem it = lin_pair_retire(row, lanes::lane() >> 3, P.spec->N, (long)P.spec->B, (long)P.spec->Bp, P.perm_cur, P.inv_next);
+        run_pair_at(P, it.k < 0 ? 0 : it.k, it.g, it.k >= 0);
+    }
+
+    // MODE 4: group g's marked stages shared out over the 2 x WAVE_ROWS halves of its wave
+    USV_DEV static void run_pair_marked(const DevPtrs &P, long g, int row)
+    {
+        const int N = lanes::uniform(P.spec->N);
+        const long gi = lin_slot(g, (long)lanes::uniform(P.spec->B));
+        const long b = P.perm ? (long)P.perm[gi] : gi;
+        int any = 0;
+        for (int w = 0; w < P.redo_words; w++) any |= P.redo[b * P.redo_words + w];
+        if (any == 0) return;
+        const int half = lanes::lane() >> 3;
+        for (int t = 0; lin_pair_marked(t, row, 0, lanes::WAVE_ROWS) <= N; t++) { // (row-uniform: the first half's stage)
+            const int k = lin_pair_marked(t, row, half, lanes::WAVE_ROWS);
+            run_pair_at(P, k <= N ? k : N, g, k <= N);
+        }
+    }
+
+    // stage k of group g in this lane's half of the row; !live: nothing there (k, g are then any valid pair)
+    USV_DEV static void run_pair_at(const DevPtrs &P, const int k, const long g, const bool live)
+    {
+        const DevSpec &S = *P.spec;
+#ifdef USV_LANES_OPAQUE // (run_pair_marked calls this in a loop: hoisted out of it, the lane patterns below - unit columns, entry selects - cost
+                        // some 30 registers, which spill)
+        const int lane = lanes::opaque(lanes::lane());
+#else
+        const int lane = lanes::lane();
+#endif
+        const int slot = lane & (HALF - 1), hb = lane & HALF;
+        const int N = lanes::uniform(S.N);
+        const long Bp = lanes::uniform(S.Bp);
+        const long gi = lin_slot(g, (long)lanes::uniform(S.B));
+        const long b = P.perm ? (long)P.perm[gi] : gi;
+        bool act = live;
+        if constexpr (SPEC) {
+            const long owner = P.perm_cur ? (long)P.perm_cur[gi] : gi;
+            const bool ready = lanes::observe(P.epoch + b) == P.tick && lanes::observe(P.epoch + owner) == P.tick;
+            if (live && !ready && slot == 0) lanes::set_bits(P.redo + b * P.redo_words + (k >> 5), 1 << (k & 31)); // this stage of this instance: later
+            act = live && ready;
+        }
+        if constexpr (FIXUP) act = act && ((P.redo[b * P.redo_words + (k >> 5)] >> (k & 31)) & 1) != 0;
+        const bool integ = act && k < N;
+        // the row leaves, or ends after the cost gradient, only as a whole: what the other half has to do
+        const int mine = (act ? 1 : 0) | (integ ? 2 : 0);
+        const int both = mine | (int)lanes::gather((double)mine, lane ^ HALF);
+        if (both == 0) return;
+        auto ld = [](const double *q) {
+            if constexpr (SPEC) return lanes::ld_shared(q);
+            else return *q;
+        };
+        double *tile = P.ws + (((long)k * Bp + g) * lanes::uniform(S.npt)) * LANES + slot; // entry `slot` of plane 0; entry slot + 8: + HALF
+        const int ku = k < N ? k : N - 1; // (a half at the terminal stage idles through the integration on the interval before it)
+
+        double x[NX], U[NU > 0 ? NU : 1];
+        const double *xk = P.x + ((long)b * (N + 1) + ku) * NX;
+        sfor<0, NX>([&](auto i) { x[i] = ld(xk + i); });
+        const double *uk = P.u + ((long)b * N + ku) * NU;
+        sfor<0, NU>([&](auto i) { U[i] = ld(uk + i); });
+
+        {   // cost gradient, reference part (run_at)
+            const bool st = k < N;
+            const double *yr = st ? P.yref + ((long)b * N + k) * S.ny : P.yref_e + (long)b * S.ny_e;
+            const int ny = st ? S.ny : S.ny_e;
+            sfor<0, 2>([&](auto h2) {
+                const double *Mrow = (st ? S.Mc : S.Me) + (slot + HALF * h2) * LANES;
+                double acc = 0.0;
+                for (int y = 0; y < ny; y++) acc = fma(-Mrow[y], yr[y], acc);
+                if (act) tile[WL::P_GQ * LANES + HALF * h2] = acc;
+            });
+        }
+        if ((both & 2) == 0) return; // row-uniform
+
+        // ---- ERK4 + forward VDE (run_at) for the column of this lane's slot; the quadrature entries accumulate beside it, in every lane,
+        // by the operations the lane of the entry's column would perform on its sa[row] ----
+        constexpr int NQ = PC::NQUAD;
+        const int nsteps = MULTI ? S.sim_steps : 1;
+        const double dt = S.dt / (double)nsteps;
+        int col = -1;
+        sfor<0, PC::NCOL>([&](auto c) {
+            constexpr int var = PC::col(decltype(c)::value);
+            col = (slot == c) ? var : col;
+        });
+        double s0[NX], f[NX], js[NX], xs[NX], ss[NX], xa[NX], sa[NX], su[NU > 0 ? NU : 1];
+        double qd[NQ > 0 ? NQ : 1], qa[NQ > 0 ? NQ : 1], q0[NQ > 0 ? NQ : 1];
+        sfor<0, NU>([&](auto l) { su[l] = (col == l) ? 1.0 : 0.0; });
+        sfor<0, NX>([&](auto i) { s0[i] = (col == NU + i) ? 1.0 : 0.0; });
+        sfor<0, NQ>([&](auto e) { q0[e] = 0.0; });
+        using MC = ModelCall<M>;
+        using MQ = ModelQuad<M>;
+        const typename MC::Pre pre = MC::prepare(x);
+        for (int step = 0; step < nsteps; step++) { // wave-uniform
+            MQ::fjvp(pre, x, U, s0, su, f, js, qd);
+            sfor<0, NX>([&](auto i) {
+                xa[i] = f[i];
+                sa[i] = js[i];
+                xs[i] = fma(0.5 * dt, f[i], x[i]);
+                ss[i] = fma(0.5 * dt, js[i], s0[i]);
+            });
+            sfor<0, NQ>([&](auto e) { qa[e] = qd[e]; });
+            MQ::fjvp(pre, xs, U, ss, su, f, js, qd);
+            sfor<0, NX>([&](auto i) {
+                xa[i] = fma(2.0, f[i], xa[i]);
+                sa[i] = fma(2.0, js[i], sa[i]);
+                xs[i] = fma(0.5 * dt, f[i], x[i]);
+                ss[i] = fma(0.5 * dt, js[i], s0[i]);
+            });
+            sfor<0, NQ>([&](auto e) { qa[e] = fma(2.0, qd[e], qa[e]); });
+            MQ::fjvp(pre, xs, U, ss, su, f, js, qd);
+            sfor<0, NX>([&](auto i) {
+                xa[i] = fma(2.0, f[i], xa[i]);
+                sa[i] = fma(2.0, js[i], sa[i]);
+                xs[i] = fma(dt, f[i], x[i]);
+                ss[i] = fma(dt, js[i], s0[i]);
+            });
+            sfor<0, NQ>([&](auto e) { qa[e] = fma(2.0, qd[e], qa[e]); });
+            MQ::fjvp(pre, xs, U, ss, su, f, js, qd);
+            sfor<0, NX>([&](auto i) {
+                x[i] = fma(dt / 6.0, xa[i] + f[i], x[i]);
+                sa[i] = fma(dt / 6.0, sa[i] + js[i], s0[i]);
+                if constexpr (MULTI) s0[i] = sa[i];
+            });
+            sfor<0, NQ>([&](auto e) {
+                qa[e] = fma(dt / 6.0, qa[e] + qd[e], q0[e]);
+                if constexpr (MULTI) q0[e] = qa[e];
+            });
+        }
+        const double *xn = P.x + ((long)b * (N + 1) + ku + 1) * NX;
+        double bres[2] = {0.0, 0.0};
+        // (the difference stays inside the conditional arm, as in run_at: the compiler then keeps what only x[i] needs of the last RK stage under
+        // the same condition in both forms, and contracts the rest of that stage alike - with it hoisted out, single-step kernels differed in the
+        // last place of [B A])
+        sfor<0, NX>([&](auto i) {
+            constexpr int e = NU + decltype(i)::value;
+            if constexpr (e < HALF) bres[0] = (slot == e) ? x[i] - ld(xn + i) : bres[0];
+            else bres[1] = (slot == e - HALF) ? x[i] - ld(xn + i) : bres[1];
+        });
+        // the MatPack stream (run_at): entry 16 q + e comes from the lane of ITS half that integrated the entry's column, or is a quadrature
+        using MP = MatPack<M>;
+        sfor<0, MP::NPK>([&](auto q) {
+            sfor<0, 2>([&](auto h2) {
+                const int sidx = 16 * q + slot + HALF * h2;
+                double val = 0.0;
+                sfor<0, NX>([&](auto j) {
+                    constexpr int jj = decltype(j)::value, qq = decltype(q)::value;
+                    constexpr int st0 = MP::start(jj), cnt = MP::count(jj);
+                    if constexpr (cnt > 0 && st0 < 16 * qq + 16 && st0 + cnt > 16 * qq) {
+                        const int within = sidx - st0;
+                        int c_l = 0; // slot that owns this entry's column
+                        sfor<0, cnt>([&](auto ci) {
+                            constexpr int c = MP::nth(MP::row_mask(jj), decltype(ci)::value);
+                            constexpr int sl = PC::slot_of(c);
+                            if constexpr (PC::quad_of(jj, c) < 0) c_l = (within == decltype(ci)::value) ? sl : c_l;
+                        });
+                        const double gth = lanes::gather(sa[jj], hb | c_l);
+                        val = (within >= 0 && within < cnt) ? gth : val;
+                        sfor<0, cnt>([&](auto ci) {
+                            constexpr int c = MP::nth(MP::row_mask(jj), decltype(ci)::value);
+                            constexpr int qe = PC::quad_of(jj, c);
+                            if constexpr (qe >= 0) val = (within == decltype(ci)::value) ? qa[qe] : val;
+                        });
+                    }
+                });
+                if (integ) tile[(WL::P_MAT + q) * LANES + HALF * h2] = val;
+            });
+        });
+        if (integ) {
+            tile[WL::P_RB0 * LANES] = bres[0];
+            tile[WL::P_RB0 * LANES + HALF] = bres[1];
+        }
     }
 };
 

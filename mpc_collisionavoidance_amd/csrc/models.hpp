@@ -70,6 +70,9 @@ struct ModelM0 {
     // everything; a thrust row is its own state plus dt * its rate
     static constexpr unsigned SENS[NX] = {0x7fu, 0x7fu, 0x7fu, 1u << 0, 1u << 1};
     static constexpr unsigned DIAG_ONE = (1u << 3) | (1u << 4);
+    // columns the lineariser integrates (PairCols, params.hpp): all seven
+    static constexpr int PAIR_NCOL = 7;
+    static constexpr int PAIR_COLS[PAIR_NCOL] = {0, 1, 2, 3, 4, 5, 6};
     USV_DEV static void fjvp(const double *x, const double *U, const double *s, const double *su, double *f, double *js)
     {
         Dof3::eval(0.78, x[0], x[1], x[2], x[3], x[4], s[0], s[1], s[2], s[3], s[4], f, js);
@@ -91,6 +94,8 @@ struct ModelM1 {
     static constexpr unsigned CH = (1u << 0) | (1u << 1) | (1u << 2) | (1u << 4) | (1u << 5); // U, u, v, chie, psied
     static constexpr unsigned SENS[NX] = {0u, 0u, CH, CH, 1u << 0, CH | (1u << 8), CH | (1u << 8), CH};
     static constexpr unsigned DIAG_ONE = 0xffu & ~(1u << 3);
+    // (no PAIR_COLS: the six columns U, u, v, chie, psied, psi would fit half a row, but with one RK4 step per interval - this model's only use -
+    // the paired kernel's [B A] differed from the 16-lane one's in the last place on the device, profiles/lin_pairs_planes.txt)
     // x = (u, v, ye, chie, psied, xned, yned, psi), T1 = 1
     USV_DEV static void fjvp(const double *x, const double *U, const double *s, const double *su, double *f, double *js)
     {
@@ -143,6 +148,12 @@ struct ModelM2 {
                                           CORE | (1u << 2) | (1u << 11), 0u, 0u, 0u, CORE | (1u << 2), CORE | (1u << 2),
                                           1u << 0, 1u << 1};
     static constexpr unsigned DIAG_ONE = 0x3fffu & ~((1u << 3) | (1u << 4) | (1u << 5));
+    // columns the lineariser integrates (PairCols, params.hpp): U0, U1, psi, u, v, r, Tport, Tstbd.  Column ak holds the one entry (ye, ak), and
+    // ye feeds nothing: a quadrature of the factor of s[9] in js[6] along the nominal trajectory (fjvp_quad)
+    static constexpr int PAIR_NCOL = 8;
+    static constexpr int PAIR_COLS[PAIR_NCOL] = {0, 1, 2, 5, 6, 7, 14, 15};
+    static constexpr int PAIR_NQUAD = 1;
+    static constexpr int PAIR_QUAD[PAIR_NQUAD][2] = {{6, NU + 9}};
     // x = (psi, sinpsi, cospsi, u, v, r, ye, x1, y1, ak, nedx, nedy, Tport, Tstbd), c = 1
     //
     // Transcendentals: the reference writes beta = atan2(v, u + .001), chi = psi + beta and uses sin / cos of psi, chi
@@ -183,6 +194,12 @@ struct ModelM2 {
     }
     USV_DEV static void fjvp_pre(const Pre &pre, const double *x, const double *U, const double *s, const double *su, double *f, double *js)
     {
+        double qd[PAIR_NQUAD];
+        fjvp_quad(pre, x, U, s, su, f, js, qd);
+    }
+    // ... handing out, per quadrature entry, the factor the entry's variable is multiplied by in the entry's row
+    USV_DEV static void fjvp_quad(const Pre &pre, const double *x, const double *U, const double *s, const double *su, double *f, double *js, double *qd)
+    {
         const double psi = x[0], u = x[3], v = x[4], r = x[5];
         const double ue = u + .001;
         const double r2 = ue * ue + v * v;
@@ -220,7 +237,9 @@ struct ModelM2 {
         js[3] = j3[0];
         js[4] = j3[1];
         js[5] = j3[2];
-        js[6] = -dvx * sa + dvy * ca + (-vx * ca - vy * sa) * s[9];
+        const double dye_dak = -vx * ca - vy * sa;
+        qd[0] = dye_dak;
+        js[6] = -dvx * sa + dvy * ca + dye_dak * s[9];
         js[7] = 0.0;
         js[8] = 0.0;
         js[9] = 0.0;

@@ -1,5 +1,6 @@
 // params.hpp — plain-data structs shared by the host C-ABI layer and the device kernels.
 #pragma once
+#include <type_traits>
 
 namespace usv {
 
@@ -106,6 +107,74 @@ struct MatPack {
         return true;
     }
     static_assert(consistent(), "OUT_UNIT / IN_UNIT disagree with SENS / DIAG_ONE");
+};
+
+// Which columns of [B A] the lineariser has to integrate (the paired lineariser: linearize.hpp run_pair_at).  A model may declare
+//   PAIR_NCOL, PAIR_COLS[PAIR_NCOL]    the at most 8 variables of [u;x] whose sensitivity column needs a lane of its own - half a 16-lane row,
+//                                      so that one row serves two (instance, stage) pairs;
+//   PAIR_NQUAD, PAIR_QUAD[..][2]       (optional) "quadrature entries" (row j, variable c) of SENS: c's column holds nothing else, c itself never
+//                                      moves (OUT_UNIT) and row j feeds nothing back (IN_UNIT), so the entry is the plain RK4 quadrature along the
+//                                      nominal trajectory of what the model multiplies by s_c in row j (M::fjvp_quad hands that value out) - every
+//                                      lane can form it, no lane has to integrate the column.
+// A model that declares nothing (generated models) is linearised one pair per row.
+template <class M, class = void>
+struct PairQuad {
+    static constexpr int N = 0;
+    static constexpr int row(int) { return -1; }
+    static constexpr int var(int) { return -1; }
+};
+template <class M>
+struct PairQuad<M, std::void_t<decltype(M::PAIR_NQUAD)>> {
+    static constexpr int N = M::PAIR_NQUAD;
+    static constexpr int row(int e) { return M::PAIR_QUAD[e][0]; }
+    static constexpr int var(int e) { return M::PAIR_QUAD[e][1]; }
+};
+template <class M, class = void>
+struct PairCols {
+    static constexpr bool ENABLED = false;
+};
+template <class M>
+struct PairCols<M, std::void_t<decltype(M::PAIR_NCOL)>> {
+    static constexpr bool ENABLED = true;
+    static constexpr int NX = M::NX, NU = M::NU, NZ = NX + NU, HALF = LANES / 2;
+    static constexpr int NCOL = M::PAIR_NCOL;
+    using Q = PairQuad<M>;
+    static constexpr int NQUAD = Q::N;
+    static constexpr int col(int slot) { return slot < NCOL ? M::PAIR_COLS[slot] : -1; } // variable integrated by lane slot of a half
+    static constexpr int slot_of(int c)                                                  // ... and the lane that integrates variable c (-1: none)
+    {
+        for (int s = 0; s < NCOL; s++)
+            if (M::PAIR_COLS[s] == c) return s;
+        return -1;
+    }
+    static constexpr int quad_of(int j, int c) // number of the quadrature entry (row j, variable c), -1: it is none
+    {
+        for (int e = 0; e < NQUAD; e++)
+            if (Q::row(e) == j && Q::var(e) == c) return e;
+        return -1;
+    }
+    // the declaration against the pattern: every SENS bit is a declared column or a quadrature entry; a quadrature entry's variable is a
+    // state that never moves and has no lane, its row variable feeds nothing
+    static constexpr bool consistent()
+    {
+        if (NCOL < 0 || NCOL > HALF) return false;
+        for (int s = 0; s < NCOL; s++) {
+            if (M::PAIR_COLS[s] < 0 || M::PAIR_COLS[s] >= NZ || slot_of(M::PAIR_COLS[s]) != s) return false;
+            if ((M::IN_UNIT >> M::PAIR_COLS[s]) & 1u) return false; // (a unit column stores nothing: no lane)
+        }
+        for (int e = 0; e < NQUAD; e++) {
+            const int j = Q::row(e), c = Q::var(e);
+            if (j < 0 || j >= NX || c < NU || c >= NZ || quad_of(j, c) != e) return false;
+            if (((M::SENS[j] >> c) & 1u) == 0u || slot_of(c) >= 0) return false;
+            if (((M::OUT_UNIT >> (c - NU)) & 1u) == 0u) return false;
+            if (((M::IN_UNIT >> (NU + j)) & 1u) == 0u) return false;
+        }
+        for (int j = 0; j < NX; j++)
+            for (int c = 0; c < NZ; c++)
+                if (((M::SENS[j] >> c) & 1u) && slot_of(c) < 0 && quad_of(j, c) < 0) return false;
+        return true;
+    }
+    static_assert(consistent(), "PAIR_COLS / PAIR_QUAD disagree with SENS / IN_UNIT / OUT_UNIT");
 };
 
 // Plane map of one stage of the solver workspace `ws` (lane-major planes, one window per stage).  The

@@ -55,15 +55,25 @@ using namespace usv;
 //            wave that leaves frees room for one of these waves (224 registers), on that SIMD only - a four-wave workgroup has to wait
 //            until each of the CU's SIMDs has lost a QP wave.
 //   4        256 threads = 4 waves, one wave per group (its rows share out the group's marked stages), n groups
+// PAIR (models with PairCols, params.hpp; option "lin_pairs"): a 16-lane row serves two (group, stage) pairs (Linearize::run_pair_at), the workgroups
+// are the same and n counts ROWS for MODE 0 - 3: 0, 1, 2 the pairs in the same stage-major order, two to a row; 3 the rows of the retire
+// order, padded to whole waves (lin_order.hpp: a wave takes 8 items, the two of a row from one instance); 4 groups as before, the marked
+// stages shared out over the wave's eight halves.
 constexpr int LIN_MODES = 5;
 constexpr int lin_block(int mode) { return mode == 3 ? 64 : 256; }
-template <class M, int KCH, bool SOFT, bool MULTI, int MODE = 0>
+template <class M, int KCH, bool SOFT, bool MULTI, bool PAIR = false, int MODE = 0>
 __global__ void __launch_bounds__(lin_block(MODE), USV_LIN_BLOCKS) usv_linearize(DevPtrs P, long n)
 {
     using L = Linearize<M, KCH, SOFT, MULTI, MODE>;
     if constexpr (MODE == 4) {
         const long g = (long)blockIdx.x * (lin_block(MODE) / 64) + (long)(threadIdx.x >> 6);
-        if (g < n) L::run_marked(P, g, (int)lanes::wave_row());
+        if constexpr (PAIR) { if (g < n) L::run_pair_marked(P, g, (int)lanes::wave_row()); }
+        else if (g < n) L::run_marked(P, g, (int)lanes::wave_row());
+    } else if constexpr (PAIR) {
+        const long row = lanes::group_linear();
+        if (row >= n) return; // (n is a multiple of 4, lin_order.hpp: whole waves leave together)
+        if constexpr (MODE == 3) L::run_pair_item(P, row);
+        else L::run_pair(P, row);
     } else {
         const long gid = lanes::group_linear();
         if (gid >= n) return; // n is a multiple of 4: whole waves leave together
@@ -211,6 +221,7 @@ struct Kernels {
     qp_resume_co_t resume_co;                    // ... and its co-resident form (usv_qp_resume_co)
     int nplw, ex_lds, ex_hbm;                    // planes per stage an instance keeps in LDS; planes of the exchange area (qp_ipm.hpp NPLW, EX_N)
     group_kernel_t lin[2][LIN_MODES];            // usv_linearize [MULTI][MODE]
+    group_kernel_t lin_pair[2][LIN_MODES];       // ... two pairs per row (PAIR); null: the model does not declare its columns (PairCols)
     group_kernel_t qp_export;                    // usv_qp_export
     int npt_hard, npt_soft;                      // WsLayout::NPT without / with soft state bounds
     int kch;                                     // the instantiation's KCH and SOFT (h->kch / h->soft may differ: usv_model with "soft" set)
@@ -732,6 +743,10 @@ struct usvmpc_handle {
     // place, on the main stream - 1: the speculative form with every instance final, then the fix-up (which finds nothing); 2: with no instance final (it
     // marks everything), then the fix-up (which does everything).  Work order as in the pipeline, with the identity as the "running" map.
     int lin_force;
+    // Option "lin_pairs": the lineariser's kernels that serve two (group, stage) pairs per 16-lane row (usv_linearize PAIR; same bits) - the default
+    // for a model that declares the columns to integrate (PairCols, params.hpp); 0: one pair per row
+    int lin_pairs;
+    long lin_pair_launches;   // launches of the paired kernels so far (usvmpc_lin_pair_launches)
     int *d_force_epoch, *d_force_redo, *d_force_inv;
     // partial condensing (option "qp_cond_N"): RTI solves condense the QP to cond_N2 stages first (0: off - the Riccati sweep over the N stages)
     int cond_N2;
@@ -768,10 +783,16 @@ Kernels kernels_for(const usvmpc_handle *h)
     const DevSpec &S = h->spec;
     const bool pack = CANPACK && S.boxpack != 0;
     Kernels k = {};
-    k.lin[0][0] = &usv_linearize<M, KCH, SOFT, false, 0>; k.lin[0][1] = &usv_linearize<M, KCH, SOFT, false, 1>; k.lin[0][2] = &usv_linearize<M, KCH, SOFT, false, 2>;
-    k.lin[0][3] = &usv_linearize<M, KCH, SOFT, false, 3>; k.lin[0][4] = &usv_linearize<M, KCH, SOFT, false, 4>;
-    k.lin[1][0] = &usv_linearize<M, KCH, SOFT, true, 0>; k.lin[1][1] = &usv_linearize<M, KCH, SOFT, true, 1>; k.lin[1][2] = &usv_linearize<M, KCH, SOFT, true, 2>;
-    k.lin[1][3] = &usv_linearize<M, KCH, SOFT, true, 3>; k.lin[1][4] = &usv_linearize<M, KCH, SOFT, true, 4>;
+    k.lin[0][0] = &usv_linearize<M, KCH, SOFT, false, false, 0>; k.lin[0][1] = &usv_linearize<M, KCH, SOFT, false, false, 1>; k.lin[0][2] = &usv_linearize<M, KCH, SOFT, false, false, 2>;
+    k.lin[0][3] = &usv_linearize<M, KCH, SOFT, false, false, 3>; k.lin[0][4] = &usv_linearize<M, KCH, SOFT, false, false, 4>;
+    k.lin[1][0] = &usv_linearize<M, KCH, SOFT, true, false, 0>; k.lin[1][1] = &usv_linearize<M, KCH, SOFT, true, false, 1>; k.lin[1][2] = &usv_linearize<M, KCH, SOFT, true, false, 2>;
+    k.lin[1][3] = &usv_linearize<M, KCH, SOFT, true, false, 3>; k.lin[1][4] = &usv_linearize<M, KCH, SOFT, true, false, 4>;
+    if constexpr (PairCols<M>::ENABLED) {
+        k.lin_pair[0][0] = &usv_linearize<M, KCH, SOFT, false, true, 0>; k.lin_pair[0][1] = &usv_linearize<M, KCH, SOFT, false, true, 1>; k.lin_pair[0][2] = &usv_linearize<M, KCH, SOFT, false, true, 2>;
+        k.lin_pair[0][3] = &usv_linearize<M, KCH, SOFT, false, true, 3>; k.lin_pair[0][4] = &usv_linearize<M, KCH, SOFT, false, true, 4>;
+        k.lin_pair[1][0] = &usv_linearize<M, KCH, SOFT, true, true, 0>; k.lin_pair[1][1] = &usv_linearize<M, KCH, SOFT, true, true, 1>; k.lin_pair[1][2] = &usv_linearize<M, KCH, SOFT, true, true, 2>;
+        k.lin_pair[1][3] = &usv_linearize<M, KCH, SOFT, true, true, 3>; k.lin_pair[1][4] = &usv_linearize<M, KCH, SOFT, true, true, 4>;
+    }
     k.qp_export = S.any_bsoft ? &usv_qp_export<M, KCH, SOFT, false, true>
                               : pack ? &usv_qp_export<M, KCH, SOFT, CANPACK, false> : &usv_qp_export<M, KCH, SOFT, false, false>;
     k.npt_hard = WsLayout<M, KCH, SOFT, false>::NPT; k.npt_soft = WsLayout<M, KCH, SOFT, true>::NPT;
@@ -1523,9 +1544,15 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         const int rct = tracks_predict(h);
         if (rct) return rct;
     }
-    // the lineariser's grids (usv_linearize): (group, stage) pairs - or work items -, groups for MODE 4
+    // the lineariser's grids (usv_linearize): (group, stage) pairs - or work items -, groups for MODE 4; two pairs per row (option "lin_pairs"): rows
     const long lin_groups = (long)(h->N + 1) * h->Bp;
-    auto lin_count = [&](int mode) { return mode == 4 ? (long)h->Bp : lin_groups; };
+    const bool pairs = h->lin_pairs != 0;
+    if (pairs && k.lin_pair[0][0] == nullptr) { h->err = "lin_pairs: the model does not declare the columns to integrate"; return USVMPC_E_ARG; }
+    auto lin_count = [&](int mode) {
+        if (mode == 4) return (long)h->Bp;
+        if (!pairs) return lin_groups;
+        return mode == 3 ? lin_pair_retire_rows(h->N, (long)h->Bp) : lin_pair_plain_rows(h->N, (long)h->Bp);
+    };
     auto lin_grid = [&](int mode) {
         const long per_block = mode == 4 ? lin_block(mode) / 64 : lin_block(mode) / LANES;
         return dim3((unsigned)((lin_count(mode) + per_block - 1) / per_block));
@@ -1539,7 +1566,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         hipLaunchKernelGGL(usv_sort_scan, dim3(1), dim3(64), 0, h->stream, h->d_hist, h->d_cursor);
         hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst, inv);
     };
-    const group_kernel_t *lin = k.lin[h->spec.sim_steps > 1 ? 1 : 0]; // [MODE]
+    const group_kernel_t *lin = (pairs ? k.lin_pair : k.lin)[h->spec.sim_steps > 1 ? 1 : 0]; // [MODE]
     // Pipelined lineariser (see usvmpc_handle): RTI solves of large handles
     const bool cond = phase == 0 && h->cond_N2 > 0; // RTI solve on the partially condensed QP (cond_ipm.hpp)
     const bool pipe = phase == 0 && h->pipeline && !h->mirror && !h->extern_access && h->dynamic_rows && h->B >= 16384 && !cond;
@@ -1607,8 +1634,10 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         }
         hipLaunchKernelGGL(lin[3], lin_grid(3), dim3(lin_block(3)), 0, h->stream, Pf, lin_count(3));
         hipLaunchKernelGGL(lin[4], lin_grid(4), dim3(lin_block(4)), 0, h->stream, Pf, lin_count(4));
+        if (pairs) h->lin_pair_launches += 2;
     } else {
         hipLaunchKernelGGL(lin[lin_mode], lin_grid(lin_mode), dim3(lin_block(lin_mode)), 0, h->stream, h->ptrs, lin_count(lin_mode));
+        if (pairs) h->lin_pair_launches++;
     }
     HIP_TRY(h, hipGetLastError());
     if (pipe) HIP_TRY(h, hipMemsetAsync(h->d_redo, 0, (size_t)B * ((h->N + 32) / 32) * sizeof(int), h->stream));
@@ -1663,6 +1692,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         h->spec_fine = h->ptrs.susp_count == nullptr;
         const int spec_mode = h->spec_fine ? 3 : 1;
         hipLaunchKernelGGL(lin[spec_mode], lin_grid(spec_mode), dim3(lin_block(spec_mode)), 0, h->aux_stream, Pn, lin_count(spec_mode));
+        if (pairs) h->lin_pair_launches++;
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->ev_spec, h->aux_stream));
         h->spec_for = h->nsolves + 1;
@@ -1695,6 +1725,22 @@ int model_mat_planes(int model)
 #endif
     }
     return 0;
+}
+
+// whether the model declares the columns the lineariser has to integrate (PairCols: the paired lineariser, option "lin_pairs")
+bool model_has_pairs(int model)
+{
+    switch (model) {
+#ifndef USV_GEN_ONLY
+    case USVMPC_MODEL_USV: return PairCols<ModelM0>::ENABLED;
+    case USVMPC_MODEL_GUIDANCE_CA1: return PairCols<ModelM1>::ENABLED;
+    case USVMPC_MODEL_PF_CA: return PairCols<ModelM2>::ENABLED;
+#endif
+#ifdef USV_GEN_MODEL_HEADER
+    case USVMPC_MODEL_GENERATED: return PairCols<ModelGen>::ENABLED;
+#endif
+    }
+    return false;
 }
 
 // the kernel table of the handle's model in this library (false: none)
@@ -1901,6 +1947,7 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->aux_stream = nullptr; h->ev_pre = nullptr; h->ev_spec = nullptr;
     h->d_epoch = nullptr; h->d_redo = nullptr; h->d_perm2 = nullptr; h->d_inv = nullptr;
     h->spec_fine = false;
+    h->lin_pairs = model_has_pairs(h->desc.model) ? 1 : 0; h->lin_pair_launches = 0;
     h->lin_force = 0; h->d_force_epoch = nullptr; h->d_force_redo = nullptr; h->d_force_inv = nullptr;
     h->spec_for = -1; h->spec_valid = false; h->spec_outstanding = false; h->spec_perm = nullptr;
     h->spec_quiet = 0; h->spec_hits = 0; h->spec_misses = 0;
@@ -2356,6 +2403,13 @@ int usvmpc_pipeline_stats(usvmpc_handle *h, long *used, long *discarded)
     return 0;
 }
 
+int usvmpc_lin_pair_launches(usvmpc_handle *h, long *launches)
+{
+    if (!h || !launches) return USVMPC_E_ARG;
+    *launches = h->lin_pair_launches;
+    return 0;
+}
+
 int usvmpc_last_mapping(usvmpc_handle *h, int *mapping)
 {
     if (!h || !mapping) return USVMPC_E_ARG;
@@ -2499,6 +2553,12 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
     if (s == "lin_force_modes") { // (tests: usvmpc_handle::lin_force)
         if (value != 0.0 && value != 1.0 && value != 2.0) { h->err = "lin_force_modes: 0, 1 or 2"; return USVMPC_E_ARG; }
         h->lin_force = (int)value;
+        return 0;
+    }
+    if (s == "lin_pairs") { // (usvmpc_handle::lin_pairs)
+        if (value != 0.0 && value != 1.0) { h->err = "lin_pairs: 0 or 1"; return USVMPC_E_ARG; }
+        if (value != 0.0 && !model_has_pairs(h->desc.model)) { h->err = "lin_pairs: the model does not declare the columns to integrate"; return USVMPC_E_ARG; }
+        h->lin_pairs = (int)value;
         return 0;
     }
     if (s == "aux_in_lds") { h->aux_lds = value != 0.0; reset_caps(h); return 0; }
