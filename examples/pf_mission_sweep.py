@@ -9,7 +9,11 @@ with no host array and no stream synchronisation in it: the front end reads the 
 inputs in place (guidance.PathFollowingFrontEnd, device-resident mode).  The plant is the controller's prediction x_1, as in the reference's
 own main.py; with --plant-steps K an RK4 integrator of its own (advance_sim: x0 <- sim(x0, u_0) in K steps).
 
-    python examples/pf_mission_sweep.py --batch 8192 --ticks 560 [--plant-steps 10]
+With --moving the obstacles drift at constant velocities (scenario.make_pf_missions(moving=True)): prepare() then writes the predicted
+obstacle set of every stage and advance() moves the world along - the tick is the same four calls.  --no-predict holds the moving world
+still inside the horizon (option "pf_predict" 0), the baseline that shows what prediction buys.
+
+    python examples/pf_mission_sweep.py --batch 8192 --ticks 560 [--plant-steps 10] [--moving [--no-predict]]
 """
 import argparse
 import os
@@ -26,10 +30,10 @@ from mpc_collisionavoidance_amd.guidance import PathFollowingFrontEnd  # noqa: E
 RING = 64   # solves whose failure counts the library keeps
 
 
-def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False):
+def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False, predict=True):
     cfg = scenario.PF_MISSION_OCP
     dt = cfg["dt"]
-    m = scenario.make_pf_missions(B, seed)
+    m = scenario.make_pf_missions(B, seed, moving=moving)
     ocp = usv_models.make_ocp("usv_model_pf_ca", N * dt, N, K)
     ocp.solver_options.sim_method_num_steps = cfg["sim_steps"]
     s = BatchOcpSolver(ocp, B)
@@ -44,7 +48,9 @@ def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False):
     s.set_all("x", np.tile(m["x0"][:, None, :], (1, N + 1, 1)))        # acados' own initial iterate: x_k = x0, u = 0
     s.set_all("u", np.zeros((B, N, 2)))
     fe.reset(m["waypoints"])
-    fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"])
+    if moving and not predict:
+        s.set_option("pf_predict", 0)
+    fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"], vel=m["world_vel"] if moving else None)
     npts = m["waypoints"].shape[1]
     fails = np.zeros(ticks, dtype=int)
     active0 = None
@@ -100,5 +106,7 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--plant-steps", type=int, default=None,
                     help="integrate the plant in this many RK4 steps per tick (default: the plant is the controller's prediction x_1)")
+    ap.add_argument("--moving", action="store_true", help="the obstacles drift at constant velocities")
+    ap.add_argument("--no-predict", action="store_true", help="with --moving: the world is held still inside the horizon (option \"pf_predict\" 0)")
     a = ap.parse_args()
-    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps)
+    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps, moving=a.moving, predict=not a.no_predict)

@@ -369,13 +369,35 @@ int usvmpc_guidance_state(usvmpc_handle *h, int *wp_index, float *past_psied);
  *             call only enqueues, otherwise it synchronises the stream.
  *   state   : wp_index [B], finish_tick [B] (prepares since reset, from 0, at the first one that found the mission over; -1 before),
  *             min_clearance [B] (smallest distance - (R + 0.5) over the visible obstacles, any tick; 1e300 before the first update),
- *             yref_writes [1] (instance rewrites of yref since reset).  Any may be NULL. */
+ *             yref_writes [1] (instance rewrites of yref since reset).  Any may be NULL.
+ * A MOVING WORLD: every entry of the world list has a constant velocity, and a mission tick stays prepare -> solve -> publish -> advance.
+ *   world_vel : vel [B][n_world][2], NED m/s, for the list last given to usvmpc_pf_world.  Non-NULL: the world moves - "static_obstacles" goes
+ *             off and every following prepare, having selected the nearest K on the CURRENT positions exactly as above, writes the predicted
+ *             set of every stage for the K it chose: p[k][2 slot + c] = X_c + ((double)k * dt) * v_c, k = 0 .. N (unfused, the arithmetic of the
+ *             obstacle tracks: csrc/obstacle_tracks.hpp; stage 0 is the world's coordinates), lh[k][slot] = (R + 0.5) + margin, k = 0 .. N-1; an
+ *             unused slot stays (1000, 1000), lh 0 at every stage.  Instances whose mission is over keep their p and lh; switch ticks write.
+ *             NULL: back to a world at rest, "static_obstacles" on again - the front end behaves exactly as described above.
+ *             USVMPC_E_ARG with a message: another model; no world list yet; an entry that is not finite; option "obstacle_tracks" on (and
+ *             switching "obstacle_tracks" on while the world moves is refused likewise: both would own p).
+ *             usvmpc_pf_world on a handle whose world moves replaces the positions and KEEPS the velocities when n_world is unchanged; with
+ *             another n_world the new list is at rest until its velocities are given.
+ *   world_step: enqueues world[i][c] += T * vel[i][c] (unfused; R untouched) on the handle's stream; refused while the world is at rest.  While
+ *             the world moves usvmpc_advance calls it with dt and usvmpc_advance_sim with the plant's period, behind their own kernel, unless
+ *             option "obstacle_step_on_advance" is 0 (one meaning for tracks and front end: the world is the caller's to move).
+ *   world_read: what the device holds - world [B][n_world][3], vel [B][n_world][2] (zeros for a world at rest); either may be NULL.
+ *   option "pf_predict" (default 1) - 0: the world moves between ticks but is held still inside the horizon: "static_obstacles" stays on and a
+ *             prepare writes stage 0 only, as for a world at rest (what the obstacle tracks do under "static_obstacles"; the baseline that shows
+ *             what prediction buys).
+ *   min_clearance, finish_tick, yref_writes and the yref rule are those of a world at rest. */
 int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts);
 int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius);
 int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pose);
 int usvmpc_pf_publish(usvmpc_handle *h, double *thr_port, double *thr_stbd, double *Tx, double *Tz, float *e_u, float *e_ye, double *speed,
                       int *active);
 int usvmpc_pf_state(usvmpc_handle *h, int *wp_index, int *finish_tick, double *min_clearance, long long *yref_writes);
+int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel);
+int usvmpc_pf_world_step(usvmpc_handle *h, double T);
+int usvmpc_pf_world_read(usvmpc_handle *h, double *world, double *vel);
 /* Profiling aid: stream `nplanes` workspace planes with the solver kernels' access instruction
  * (kernel usv_calib_stream) and report the exact byte counts, to calibrate HBM PMC counters.
  * Overwrites solver scratch; the next usvmpc_solve re-initialises it. */

@@ -68,7 +68,8 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval",
            "usvmpc_sim_create", "usvmpc_sim_destroy", "usvmpc_sim_set", "usvmpc_sim_solve", "usvmpc_sim_get", "usvmpc_sim_get_device_ptr",
            "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step",
-           "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state"]
+           "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state",
+           "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read"]
 
 
 _libs = {}
@@ -134,6 +135,9 @@ def load(path):
     L.usvmpc_pf_prepare.argtypes = [C.c_void_p, _dp, _dp]
     L.usvmpc_pf_publish.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _fp, _dp, _ip]
     L.usvmpc_pf_state.argtypes = [C.c_void_p, _ip, _ip, _dp, C.POINTER(C.c_longlong)]
+    L.usvmpc_pf_world_vel.argtypes = [C.c_void_p, _dp]
+    L.usvmpc_pf_world_step.argtypes = [C.c_void_p, C.c_double]
+    L.usvmpc_pf_world_read.argtypes = [C.c_void_p, _dp, _dp]
     L.usvmpc_debug_model_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_obstacle_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_sim_create.argtypes = [C.POINTER(SimDesc), C.POINTER(C.c_void_p)]

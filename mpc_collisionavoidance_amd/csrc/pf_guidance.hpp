@@ -17,6 +17,8 @@
 
 #include <cmath>
 
+#include "obstacle_tracks.hpp"
+
 #ifndef USV_HD
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define USV_HD __host__ __device__ inline
@@ -48,6 +50,9 @@ struct PfPtrs {
     const double *world; // [B][nworld][3] NED (X, Y, R)
     int nworld;
     double max_radius, margin;
+    const double *wvel;  // [B][nworld][2] NED m/s: the world moves and prepare writes every stage; null: a world at rest (stage 0 only)
+    double *trk_pv;      // [B][K][4] (X, Y, vX, vY) } the slot tracks of the last moving prepare: written by its decide step,
+    double *trk_lh;      // [B][K]                   } read by its streaming step
     const double *vel;   // [B][3] u, v, r     } host-fed; both null: the vessel's state is read from the handle's x0
     const double *pose;  // [B][3] nedx, nedy, psi
     int *k, *phase, *finish_tick; // [B] state: waypoint index, PF_* of the last prepare, tick of the first PF_OVER prepare (-1: none yet)
@@ -134,16 +139,12 @@ USV_HD double pf_lh(double R, double margin)
     return (R + PF_BOAT_RADIUS) + margin;
 }
 
-// Stage 0 of p ([2K]) and lh ([K]) from the world list w ([L][3]): the K visible obstacles with the smallest d, in that order, ties by list
-// index; the rest of the slots parked.  d: scratch of L entries, entry i at d[i * stride] (the kernel keeps it in LDS, one column per lane).
-// Returns the smallest d (1e300: nothing visible); chosen (optional, [K]): the list index behind each slot, -1 for a parked one.
-USV_HD double pf_select(const double *w, int L, int K, double nedx, double nedy, double max_radius, double margin, double *d, int stride,
-                        double *p, double *lh, int *chosen)
+// The selection over the world list w ([L][3]): the K visible obstacles with the smallest d, ties by list index.  d: scratch of L entries,
+// entry i at d[i * stride] (the kernel keeps it in LDS, one column per lane).  place(slot, i): list entry i takes slot `slot` (each slot
+// at most once, in list order, not in slot order).  Returns the smallest d (1e300: nothing visible).
+template <class Place>
+USV_HD double pf_rank(const double *w, int L, int K, double nedx, double nedy, double max_radius, double *d, int stride, Place place)
 {
-    for (int i = 0; i < K; i++) {
-        p[2 * i] = PF_FAR; p[2 * i + 1] = PF_FAR; lh[i] = 0.0;
-        if (chosen) chosen[i] = -1;
-    }
     double dmin = 1e300;
     for (int i = 0; i < L; i++) {
         double di;
@@ -159,13 +160,55 @@ USV_HD double pf_select(const double *w, int L, int K, double nedx, double nedy,
             const double dj = d[j * stride];
             rank += (dj < di || (dj == di && j < i)) ? 1 : 0;
         }
-        if (rank < K) {
-            p[2 * rank] = w[3 * i]; p[2 * rank + 1] = w[3 * i + 1]; // (the world's coordinates, bit for bit)
-            lh[rank] = pf_lh(w[3 * i + 2], margin);
-            if (chosen) chosen[rank] = i;
-        }
+        if (rank < K) place(rank, i);
     }
     return dmin;
+}
+
+// Stage 0 of p ([2K]) and lh ([K]) from the world list: the chosen ones in rank order, the rest of the slots parked.
+// chosen (optional, [K]): the list index behind each slot, -1 for a parked one.
+USV_HD double pf_select(const double *w, int L, int K, double nedx, double nedy, double max_radius, double margin, double *d, int stride,
+                        double *p, double *lh, int *chosen)
+{
+    for (int i = 0; i < K; i++) {
+        p[2 * i] = PF_FAR; p[2 * i + 1] = PF_FAR; lh[i] = 0.0;
+        if (chosen) chosen[i] = -1;
+    }
+    return pf_rank(w, L, K, nedx, nedy, max_radius, d, stride, [&](int slot, int i) {
+        p[2 * slot] = w[3 * i]; p[2 * slot + 1] = w[3 * i + 1]; // (the world's coordinates, bit for bit)
+        lh[slot] = pf_lh(w[3 * i + 2], margin);
+        if (chosen) chosen[slot] = i;
+    });
+}
+
+// ---- a moving world: list entry i also has a constant velocity wv[i] = (vX, vY), NED m/s.  The selection is the same, on the current
+// positions; each slot gets a TRACK instead of a point - pv [K][4] = (X, Y, vX, vY), lh [K]; a parked slot (1000, 1000) with velocity 0 and
+// lh 0 - from which every stage follows (obstacle_tracks.hpp: the tracks' arithmetic, not a second copy of it):
+//     p[k][2 slot + c] = track_predict(pv[slot][c], pv[slot][2 + c], k, dt)   k = 0 .. N   (stage 0: the world's coordinates, (0 dt) v = 0;
+//     lh[k][slot]      = lh[slot]                                             k = 0 .. N-1  a parked slot: 1000.0 at every stage)
+// and the world moves on by T with track_step, R untouched.
+USV_HD double pf_select_tracks(const double *w, const double *wv, int L, int K, double nedx, double nedy, double max_radius, double margin,
+                               double *d, int stride, double *pv, double *lh, int *chosen)
+{
+    for (int i = 0; i < K; i++) {
+        pv[4 * i] = PF_FAR; pv[4 * i + 1] = PF_FAR; pv[4 * i + 2] = 0.0; pv[4 * i + 3] = 0.0; lh[i] = 0.0;
+        if (chosen) chosen[i] = -1;
+    }
+    return pf_rank(w, L, K, nedx, nedy, max_radius, d, stride, [&](int slot, int i) {
+        pv[4 * slot] = w[3 * i]; pv[4 * slot + 1] = w[3 * i + 1]; pv[4 * slot + 2] = wv[2 * i]; pv[4 * slot + 3] = wv[2 * i + 1];
+        lh[slot] = pf_lh(w[3 * i + 2], margin);
+        if (chosen) chosen[slot] = i;
+    });
+}
+
+// coordinate c (0, 1) of a slot's track (pv: its four entries) at stage k
+USV_HD double pf_stage(const double *pv, int c, int k, double dt) { return track_predict(pv[c], pv[2 + c], k, dt); }
+
+// one world entry w = (X, Y, R) with velocity wv = (vX, vY) after a step of T
+USV_HD void pf_world_step(double *w, const double *wv, double T)
+{
+    w[0] = track_step(w[0], wv[0], T);
+    w[1] = track_step(w[1], wv[1], T);
 }
 
 // ---- output side, control :347-376, for an instance whose tick was PF_ACTIVE: the thrusters are x_1's (the thrust is a state), the errors

@@ -410,6 +410,15 @@ static __global__ void usv_pf_reset(PfPtrs F, int B)
 //    reference rewrites it every tick).  All 256 threads walk it in 16-byte stores, thread t the t-th pair of each 4 KiB pass (a wave's stores
 //    cover 1 KiB without gaps), skipping the instances that keep their rows; 256 % 8 == 0, so a thread always holds the same pair of a row and
 //    only its instance moves on.  yref_e (7 pairs per instance) likewise.  No thread walks an instance's rows alone.
+// A moving world (F.wvel: usvmpc_pf_world_vel, option "pf_predict" 1): the decide step selects as ever, on the current positions, but leaves each
+// slot's TRACK (position pair, velocity pair, lh) in the [B][K] scratch F.trk_pv / F.trk_lh instead of writing stage 0, and between the two
+// steps above comes
+// 1b. Stream p and lh: the workgroup's instances own one contiguous run of p (PF_GROUP * (N + 1) * K pairs) and one of lh
+//    (PF_GROUP * N * K doubles).  All 256 threads walk each in 16-byte stores, thread t the t-th pair of every 4 KiB pass, looking its slot's
+//    track up again as (instance, stage, slot) moves on (K need not divide 256); the tracks of a wave's pass are a few hundred bytes the
+//    workgroup itself has just written.  Instances whose mission is over keep their p and lh; switch ticks write.  A pair of lh that
+//    straddles two instances of which one keeps its rows is stored as single doubles.
+// With F.wvel null the kernel's stores are those of a world at rest: stage 0 only, by the deciding lane.
 __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int tick, int stale)
 {
     const DevSpec &S = *P.spec;
@@ -418,11 +427,13 @@ __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int t
     __shared__ double s_ref[PF_GROUP][3];
     __shared__ int s_write[PF_GROUP];
     __shared__ unsigned s_count;
+    __shared__ int s_obs[PF_GROUP]; // (a moving world: the instance's p / lh are written this tick)
+    __shared__ unsigned s_nobs;
     const int t = (int)threadIdx.x;
     const long b0 = (long)blockIdx.x * PF_GROUP;
     const int cnt = (int)((long)B - b0 < (long)PF_GROUP ? (long)B - b0 : (long)PF_GROUP);
-    if (t == 0) s_count = 0u;
-    if (t < PF_GROUP) s_write[t] = 0;
+    if (t == 0) { s_count = 0u; s_nobs = 0u; }
+    if (t < PF_GROUP) { s_write[t] = 0; s_obs[t] = 0; }
     __syncthreads();
     if (t < cnt) {
         const long b = b0 + t;
@@ -444,8 +455,16 @@ __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int t
         if (phase == PF_OVER && F.finish_tick[b] < 0) F.finish_tick[b] = tick;
         if (phase != PF_OVER) {
             const int L = F.nworld < PF_LMAX ? F.nworld : PF_LMAX;
-            const double dmin = pf_select(F.world + b * 3 * F.nworld, L, K, nedx, nedy, F.max_radius, F.margin, s_d + t, PF_GROUP,
-                                          const_cast<double *>(P.p) + b * (long)(N + 1) * 2 * K, const_cast<double *>(P.lh) + b * (long)N * K, nullptr);
+            double dmin;
+            if (F.wvel) {
+                dmin = pf_select_tracks(F.world + b * 3 * F.nworld, F.wvel + b * 2 * F.nworld, L, K, nedx, nedy, F.max_radius, F.margin, s_d + t,
+                                        PF_GROUP, F.trk_pv + b * 4 * K, F.trk_lh + b * K, nullptr);
+                s_obs[t] = 1;
+                atomicAdd(&s_nobs, 1u);
+            } else {
+                dmin = pf_select(F.world + b * 3 * F.nworld, L, K, nedx, nedy, F.max_radius, F.margin, s_d + t, PF_GROUP,
+                                 const_cast<double *>(P.p) + b * (long)(N + 1) * 2 * K, const_cast<double *>(P.lh) + b * (long)N * K, nullptr);
+            }
             if (dmin < F.min_clear[b]) F.min_clear[b] = dmin;
         }
         if (phase == PF_ACTIVE) {
@@ -463,6 +482,46 @@ __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int t
         }
     }
     __syncthreads();
+    if (s_nobs != 0u && K > 0) {
+        const double dt = S.dt;
+        const double2 *pv = reinterpret_cast<const double2 *>(F.trk_pv) + b0 * 2 * K; // [cnt][K][2]: (X, Y), (vX, vY)
+        {
+            double2 *row = reinterpret_cast<double2 *>(const_cast<double *>(P.p)) + b0 * (long)(N + 1) * K;
+            const int per = (N + 1) * K, total = cnt * per; // pairs per instance / of the workgroup
+            int inst = 0, rem = t;                          // j = inst * per + rem
+            while (rem >= per) { rem -= per; inst++; }
+            for (int j = t; j < total; j += 256) {
+                if (s_obs[inst]) {
+                    const int k = rem / K, slot = rem - k * K;
+                    const double2 q = pv[(inst * K + slot) * 2], v = pv[(inst * K + slot) * 2 + 1];
+                    double2 o;
+                    o.x = track_predict(q.x, v.x, k, dt);
+                    o.y = track_predict(q.y, v.y, k, dt);
+                    row[j] = o;
+                }
+                rem += 256;
+                while (rem >= per) { rem -= per; inst++; }
+            }
+        }
+        {
+            double *row = const_cast<double *>(P.lh) + b0 * (long)N * K;
+            const double *tl = F.trk_lh + b0 * K;
+            const int per = N * K, total = cnt * per; // doubles per instance / of the workgroup
+            int inst = 0, rem = 2 * t;                // e = 2 j = inst * per + rem: the pair's first double
+            while (rem >= per) { rem -= per; inst++; }
+            for (int e = 2 * t; e < total; e += 512) {
+                int inst1 = inst, rem1 = rem + 1;     // its second
+                if (rem1 == per) { rem1 = 0; inst1++; }
+                const bool w0 = s_obs[inst] != 0, w1 = e + 1 < total && s_obs[inst1] != 0;
+                const double a = w0 ? tl[inst * K + rem % K] : 0.0, c = w1 ? tl[inst1 * K + rem1 % K] : 0.0;
+                if (w0 && w1) *reinterpret_cast<double2 *>(row + e) = double2{a, c};
+                else if (w0) row[e] = a;
+                else if (w1) row[e + 1] = c;
+                rem += 512;
+                while (rem >= per) { rem -= per; inst++; }
+            }
+        }
+    }
     const unsigned nwrite = s_count;
     if (nwrite == 0u) return;
     if (t == 0) atomicAdd(F.yref_writes, (unsigned long long)nwrite);
@@ -494,6 +553,14 @@ __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int t
             row[j] = o;
         }
     }
+}
+
+// usv_pf_world_step: the front end's world moves on by T, one thread per world entry (R is untouched)
+__global__ void __launch_bounds__(256) usv_pf_world_step(double *world, const double *wvel, long n, double T)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    pf_world_step(world + 3 * i, wvel + 2 * i, T);
 }
 
 // usv_pf_publish: the node's outputs after the solve, one lane per instance (a dozen scalars each).  An active instance reads the thrusters
@@ -667,6 +734,13 @@ struct usvmpc_handle {
     size_t pf_world_cap;      // doubles
     double pf_margin;         // option "pf_lh_margin"
     double *pf_vel, *pf_pose; // [B][3] staging of the host-fed mode
+    // A moving world (usvmpc_pf_world_vel): velocities per world entry; prepare then writes every stage of p / lh ("static_obstacles" off)
+    // unless option "pf_predict" is 0, and usvmpc_advance / _advance_sim move the world (option "obstacle_step_on_advance")
+    double *pf_wvel;          // [B][nworld][2]
+    size_t pf_wvel_cap;       // doubles
+    bool pf_world_set;        // usvmpc_pf_world has been called
+    bool pf_moving;           // velocities are set for the current list
+    bool pf_predict;          // option "pf_predict"
     bool sort_enabled;
     bool sort_two;            // sort key: the larger of the last two iteration counts instead of the last one (option, default off)
     bool merge_rows;
@@ -2054,6 +2128,7 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     std::memset(&h->pf, 0, sizeof(h->pf));
     h->pf_alloc = false; h->pf_ready = false; h->pf_stale = true; h->pf_tick = 0; h->pf_npts_cap = 0; h->pf_world_cap = 0; h->pf_margin = 0.2;
     h->pf_vel = nullptr; h->pf_pose = nullptr;
+    h->pf_wvel = nullptr; h->pf_wvel_cap = 0; h->pf_world_set = false; h->pf_moving = false; h->pf_predict = true;
     h->gd_ready = false; h->gd_npts_cap = 0; h->gd_psi = nullptr; h->gd_world = nullptr; h->gd_world_cap = 0;
     std::memset(&h->gd, 0, sizeof(h->gd));
     TRY_C(dev_alloc(h, &P.ws, (N + 1) * (size_t)ws_planes(h->nx, h->nu, h->kch, h->soft, model_mat_planes(h->desc.model), h->spec.any_bsoft != 0) * stride, true));
@@ -2422,6 +2497,8 @@ int usvmpc_last_kernel_ms(usvmpc_handle *h, float *linearize_ms, float *qp_ms)
     return usvmpc_kernel_ms(h, 1, linearize_ms, qp_ms);
 }
 
+static int pf_apply_static(usvmpc_handle *h);
+
 int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
 {
     if (!h) return USVMPC_E_ARG;
@@ -2435,6 +2512,7 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
                        h->instance_offset);
     HIP_TRY(h, hipGetLastError());
     if (h->tracks_on && h->step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
+    if (h->pf_moving && h->step_on_advance) return usvmpc_pf_world_step(h, h->spec.dt); // (the front end's world likewise)
     return 0;
 }
 
@@ -2489,6 +2567,7 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     }
     HIP_TRY(h, hipGetLastError());
     if (h->tracks_on && h->step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
+    if (h->pf_moving && h->step_on_advance) return usvmpc_pf_world_step(h, plant->T);
     return 0;
 }
 
@@ -2503,11 +2582,17 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         if (h->K == 0) { h->err = "obstacle_tracks: this model has no obstacle rows (K = 0)"; return USVMPC_E_ARG; }
         if (!h->tracks_pos_set) { h->err = "obstacle_tracks: set \"obs_pos\" before switching the option on"; return USVMPC_E_ARG; }
         if (h->pf_ready) { h->err = "obstacle_tracks: the path-following front end owns p on this handle"; return USVMPC_E_ARG; }
+        if (h->pf_moving) { h->err = "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle"; return USVMPC_E_ARG; }
         h->tracks_on = true;
         h->tracks_dirty = true;
         return 0;
     }
     if (s == "obstacle_step_on_advance") { h->step_on_advance = value != 0.0; return 0; }
+    if (s == "pf_predict") { // a moving world inside the horizon: 1 predicted per stage, 0 held still (stage 0 only, "static_obstacles" on)
+        if (value != 0.0 && value != 1.0) { h->err = "pf_predict: 0 or 1"; return USVMPC_E_ARG; }
+        h->pf_predict = value != 0.0;
+        return h->pf_ready ? pf_apply_static(h) : 0;
+    }
     if (s == "pf_lh_margin") { // the path-following front end's lh = (R + boat radius) + margin (scripts/usv_pf_ca/main.py:126: 0.2)
         if (!(value >= 0.0) || value - value != 0.0) { h->err = "pf_lh_margin must be finite and non-negative"; return USVMPC_E_ARG; }
         h->pf_margin = value;
@@ -2799,6 +2884,14 @@ static int pf_check(usvmpc_handle *h)
     return 0;
 }
 
+// "static_obstacles" as the front end needs it: off only while the world moves AND is predicted per stage (prepare then writes all stages)
+static int pf_apply_static(usvmpc_handle *h)
+{
+    const bool want = !(h->pf_moving && h->pf_predict);
+    if ((h->spec.p_static != 0) == want) return 0;
+    return usvmpc_set_option(h, "static_obstacles", want ? 1.0 : 0.0);
+}
+
 static int pf_alloc(usvmpc_handle *h)
 {
     if (h->pf_alloc) return 0;
@@ -2842,8 +2935,7 @@ int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->pf_ready = true; h->pf_stale = true; h->pf_tick = 0;
-    if (!h->spec.p_static) return usvmpc_set_option(h, "static_obstacles", 1.0);
-    return 0;
+    return pf_apply_static(h);
 }
 
 int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
@@ -2869,8 +2961,77 @@ int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double m
     }
     if (need) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.world), world, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const bool same = h->pf_world_set && F.nworld == n_world;
     F.nworld = n_world;
     F.max_radius = max_radius;
+    h->pf_world_set = true;
+    if (h->pf_moving && !same) { // (velocities belong to a list: another n_world is at rest until its own are given)
+        h->pf_moving = false;
+        return h->pf_ready ? pf_apply_static(h) : 0;
+    }
+    return 0;
+}
+
+int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!vel) { // back to a world at rest
+        h->pf_moving = false;
+        return h->pf_ready ? pf_apply_static(h) : 0;
+    }
+    if (!h->pf_world_set) { h->err = "pf_world_vel: no world list yet (usvmpc_pf_world first)"; return USVMPC_E_ARG; }
+    if (h->tracks_on) { h->err = "pf_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    PfPtrs &F = h->pf;
+    const size_t need = (size_t)h->B * (size_t)F.nworld * 2;
+    for (size_t i = 0; i < need; i++)
+        if (vel[i] - vel[i] != 0.0) { h->err = "pf_world_vel: entry " + std::to_string(i) + " is not finite"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step that reads the old velocities may be in flight)
+    if (need > h->pf_wvel_cap || !h->pf_wvel) { // (an empty list moves too: a non-null pointer is what tells prepare so)
+        dev_free(h, h->pf_wvel, h->pf_wvel_cap * sizeof(double));
+        h->pf_wvel = nullptr; h->pf_wvel_cap = 0;
+        if (dev_alloc(h, &h->pf_wvel, need, false)) return USVMPC_E_HIP;
+        h->pf_wvel_cap = need;
+    }
+    if (!F.trk_pv && (dev_alloc(h, &F.trk_pv, (size_t)h->B * (size_t)(h->K ? h->K : 1) * 4, true) ||
+                      dev_alloc(h, &F.trk_lh, (size_t)h->B * (size_t)(h->K ? h->K : 1), true)))
+        return USVMPC_E_HIP;
+    if (need) HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, vel, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->pf_moving = true;
+    return h->pf_ready ? pf_apply_static(h) : 0;
+}
+
+int usvmpc_pf_world_step(usvmpc_handle *h, double T)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_moving) { h->err = "pf_world_step: the world is at rest (usvmpc_pf_world_vel first)"; return USVMPC_E_ARG; }
+    if (T - T != 0.0) { h->err = "pf_world_step: T is not finite"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const long n = (long)h->B * h->pf.nworld;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(usv_pf_world_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, const_cast<double *>(h->pf.world),
+                       (const double *)h->pf_wvel, n, T);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int usvmpc_pf_world_read(usvmpc_handle *h, double *world, double *vel)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_world_set) { h->err = "pf_world_read: no world list yet (usvmpc_pf_world first)"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->B * (size_t)h->pf.nworld;
+    if (world && n) HIP_TRY(h, hipMemcpyAsync(world, h->pf.world, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (vel && n && h->pf_moving) HIP_TRY(h, hipMemcpyAsync(vel, h->pf_wvel, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (vel && !h->pf_moving) std::fill(vel, vel + n * 2, 0.0); // (a world at rest)
     return 0;
 }
 
@@ -2888,6 +3049,7 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     if (rc) return rc;
     PfPtrs F = h->pf;
     F.margin = h->pf_margin;
+    F.wvel = (h->pf_moving && h->pf_predict) ? h->pf_wvel : nullptr; // (held still inside the horizon: the prepare of a world at rest)
     const size_t B = h->B;
     if (vel_uvr) {
         HIP_TRY(h, hipMemcpyAsync(h->pf_vel, vel_uvr, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));

@@ -113,6 +113,25 @@ def _as_world(world, B, lmax=64):
     return np.ascontiguousarray(w)
 
 
+def _as_world_vel(vel, B, L):
+    """World velocities (vX, vY), NED m/s, for a world list of L entries: [B, L, 2] or one [L, 2] list for every instance -> contiguous
+    [B, L, 2]."""
+    v = np.asarray(vel, dtype=np.float64)
+    if v.size == 0 and L == 0:
+        return np.zeros((B, 0, 2))
+    if v.shape[-1:] != (2,) or v.ndim not in (2, 3):
+        raise Exception("world velocities: expected [%d, %d, 2] or [%d, 2] rows of (vX, vY), got %s" % (B, L, L, list(v.shape)))
+    if v.ndim == 2:
+        v = np.tile(v[None], (B, 1, 1))
+    if v.shape[0] != B:
+        raise Exception("world velocities: expected %d instances, got %d" % (B, v.shape[0]))
+    if v.shape[1] != L:
+        raise Exception("world velocities: the world list has %d obstacles per instance, got %d velocities" % (L, v.shape[1]))
+    if not np.isfinite(v).all():
+        raise Exception("world velocities contain NaN or infinity")
+    return np.ascontiguousarray(v)
+
+
 class PathFollowingFrontEnd:
     """Batched counterpart of the reference's path-following ROS node around the solver (class NMPC,
     catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp = nmpc_pf_ca.cpp) for usv_model_pf_ca: waypoint manager, x0 and reference assembly, nearest-K
@@ -135,12 +154,30 @@ class PathFollowingFrontEnd:
         w = _as_waypoints(waypoints, self.B)
         self.s._check(self._lib.usvmpc_pf_reset(self.s._h, w.ctypes.data_as(_capi._dp), w.shape[1] // 2))
 
-    def set_world(self, world, max_radius=100.0, margin=None):
-        """The obstacle field (X, Y, R) in NED: [B, L, 3] or [L, 3] for all, L <= 64; uploaded once.  margin: lh = (R + 0.5) + margin."""
+    def set_world(self, world, max_radius=100.0, margin=None, vel=None):
+        """The obstacle field (X, Y, R) in NED: [B, L, 3] or [L, 3] for all, L <= 64; uploaded once.  margin: lh = (R + 0.5) + margin.
+        vel: [B, L, 2] or [L, 2] (vX, vY) in NED m/s - the world moves: prepare() writes the predicted obstacle set of every stage and
+        advance / advance_sim move the world along (option "obstacle_step_on_advance").  None: a world at rest."""
         w = _as_world(world, self.B)
+        v = None if vel is None else _as_world_vel(vel, self.B, w.shape[1])
         if margin is not None:
             self.s.set_option("pf_lh_margin", float(margin))
         self.s._check(self._lib.usvmpc_pf_world(self.s._h, w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius)))
+        self.s._check(self._lib.usvmpc_pf_world_vel(self.s._h, None if v is None else v.ctypes.data_as(_capi._dp)))
+        self._L = w.shape[1]
+
+    def step_world(self, T):
+        """The world moves on by T seconds (enqueued; a moving world only)."""
+        self.s._check(self._lib.usvmpc_pf_world_step(self.s._h, float(T)))
+
+    def world(self):
+        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest."""
+        L = getattr(self, "_L", None)
+        if L is None:
+            raise Exception("world: no world list yet (set_world first)")
+        w, v = np.zeros((self.B, L, 3)), np.zeros((self.B, L, 2))
+        self.s._check(self._lib.usvmpc_pf_world_read(self.s._h, w.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp)))
+        return w, v
 
     def prepare(self, vel_uvr=None, pose=None):
         """vel_uvr [B,3] = (u, v, r), pose [B,3] = (nedx, nedy, psi); both None: device-resident (enqueues and returns)."""

@@ -295,16 +295,24 @@ PF_MISSION_WAYPOINTS = np.array([[4.0, -5.0], [4.0, 1.0], [8.0, 5.0]])
 PF_MISSION_OCP = dict(N=40, dt=0.05, sim_steps=5, K=4, max_radius=100.0, margin=0.2)
 
 
-def make_pf_missions(B, seed=0):
+# moving=True: obstacle i drifts at a constant velocity, U(-PF_DRIFT_ALONG, PF_DRIFT_ALONG) m/s along its own leg and
+# U(-PF_DRIFT_ACROSS, PF_DRIFT_ACROSS) m/s along the leg's normal (the vessel cruises at 0.7 m/s).  Settled with tools/pf_mission_oracle.py.
+PF_DRIFT_ALONG, PF_DRIFT_ACROSS = 0.15, 0.05
+
+
+def make_pf_missions(B, seed=0, moving=False):
     """B missions, instance b drawn from numpy.random.default_rng(seed + b) - an instance does not depend on the batch it is in.
     Returns dict(waypoints [B,3,2], world [B,4,3] = (X, Y, R), x0 [B,14]).  Obstacle i lies beside leg i % 2: a point t ~ U(0.25, 0.8)
     along the leg, moved 0.9 .. 1.6 m along the leg's unit normal (-dy, dx) / |.| to either side, radius 0.1 .. 0.4 m (keep-out radius
     R + 0.5 + 0.2: the path stays free by 0.1 m at least, the vessel has to swerve for the nearer ones).  Nearer obstacles (0.5 .. 0.9 m)
     leave a third of the missions stuck in front of a hard row: this spacing is deliberate.  The vessel starts at (4 +- 1, -5), heading
-    pi/2 +- 0.3, u = 0.001, everything else 0."""
+    pi/2 +- 0.3, u = 0.001, everything else 0.
+    moving=True adds world_vel [B,4,2] (vX, vY), drawn from a stream of its own, default_rng([seed + b, 1]): every other field is the
+    same bits with either value of `moving`."""
     w = PF_MISSION_WAYPOINTS
     world = np.zeros((B, 4, 3))
     x0 = np.zeros((B, 14))
+    vel = np.zeros((B, 4, 2))
     for b in range(B):
         rng = np.random.default_rng(seed + b)
         for i in range(4):
@@ -320,4 +328,30 @@ def make_pf_missions(B, seed=0):
         psi0 = np.pi / 2 + rng.uniform(-0.3, 0.3)
         nedx = 4.0 + rng.uniform(-1.0, 1.0)
         x0[b, 0], x0[b, 3], x0[b, 10], x0[b, 11] = psi0, 0.001, nedx, -5.0
-    return dict(waypoints=np.tile(w[None], (B, 1, 1)), world=world, x0=x0)
+        if moving:
+            rv = np.random.default_rng([seed + b, 1])
+            for i in range(4):
+                d = w[i % 2 + 1] - w[i % 2]
+                e = d / np.hypot(d[0], d[1])
+                n = np.array([-e[1], e[0]])
+                vel[b, i] = rv.uniform(-PF_DRIFT_ALONG, PF_DRIFT_ALONG) * e + rv.uniform(-PF_DRIFT_ACROSS, PF_DRIFT_ACROSS) * n
+    out = dict(waypoints=np.tile(w[None], (B, 1, 1)), world=world, x0=x0)
+    if moving:
+        out["world_vel"] = vel
+    return out
+
+
+def predict_world(world, vel, chosen, N, dt, margin=PF_MISSION_OCP["margin"]):
+    """The per-stage obstacle set a moving-world prepare writes (csrc/pf_guidance.hpp), in numpy: world [B,L,3], vel [B,L,2], chosen [B,K]
+    (list index behind each slot, -1: parked) -> p [B,N+1,2K], lh [B,N,K].  p[k] = pos + ((double)k * dt) * vel, every product and sum rounded
+    on its own; a parked slot is (1000, 1000) with velocity 0 and lh 0."""
+    world, vel, chosen = np.asarray(world, dtype=float), np.asarray(vel, dtype=float), np.asarray(chosen, dtype=int)
+    B, K = chosen.shape
+    pos, v, lh0 = np.full((B, K, 2), 1000.0), np.zeros((B, K, 2)), np.zeros((B, K))
+    bb, ss = np.nonzero(chosen >= 0)
+    ii = chosen[bb, ss]
+    pos[bb, ss], v[bb, ss] = world[bb, ii, :2], vel[bb, ii]
+    lh0[bb, ss] = (world[bb, ii, 2] + 0.5) + margin
+    kdt = (np.arange(N + 1, dtype=float) * dt)[None, :, None, None]
+    p = (pos[:, None] + kdt * v[:, None]).reshape(B, N + 1, 2 * K)
+    return p, np.tile(lh0[:, None], (1, N, 1))

@@ -8,11 +8,16 @@ scenario.make_pf_missions (N = 40, K = 4, 5 RK4 steps):
             of yref, so the lineariser runs inside the solve)
   hostfed   x0 read back, prepare(vel, pose) from it, solve_async, publish(fetch=False), advance: the host-fed front end
 
+With --moving the world of `resident` and `hostfed` moves (scenario.make_pf_missions(moving=True)): prepare writes p / lh of every stage and
+advance steps the world; the extra mode `held` is `resident` with option "pf_predict" 0 (the world moves between ticks, stage 0 only) and `static` is `resident` over
+a world at rest whatever --moving says, so that one invocation alternates the three.
+
 Median over --ticks timed ticks after --warmup warm-up ticks (a host clock around the tick and a final sync), `--runs` alternating runs, one
 JSON line each, with the lineariser's and the QP launch's kernel times of the same ticks (HIP events) and the bytes a full yref rewrite
 streams.
 
     python tools/pf_frontend_probe.py --batch 65536
+    python tools/pf_frontend_probe.py --batch 65536 --moving --modes static,resident,held
     rocprofv3 --kernel-trace --stats -- python tools/pf_frontend_probe.py --batch 65536 --modes resident --runs 1 --ticks 4 --warmup 1
 """
 import argparse
@@ -29,15 +34,15 @@ import torch  # noqa: F401,E402  (before the solver library: one HIP runtime for
 from mpc_collisionavoidance_amd import BatchOcpSolver, scenario, usv_models  # noqa: E402
 from mpc_collisionavoidance_amd.guidance import PathFollowingFrontEnd  # noqa: E402
 
-MODES = ("plain", "resident", "hostfed")
+MODES = ("plain", "resident", "hostfed")   # and "held", "static" (see above)
 _missions = {}
 
 
-def run(mode, B, ticks, warmup, seed=0):
+def run(mode, B, ticks, warmup, seed=0, moving=False):
     cfg = scenario.PF_MISSION_OCP
     N, K, dt = cfg["N"], cfg["K"], cfg["dt"]
     if (B, seed) not in _missions:
-        _missions[(B, seed)] = scenario.make_pf_missions(B, seed)
+        _missions[(B, seed)] = scenario.make_pf_missions(B, seed, moving=True)   # (every other field is the same with either value)
     m = _missions[(B, seed)]
     ocp = usv_models.make_ocp("usv_model_pf_ca", N * dt, N, K)
     ocp.solver_options.sim_method_num_steps = cfg["sim_steps"]
@@ -47,14 +52,17 @@ def run(mode, B, ticks, warmup, seed=0):
     s.set_all("x", np.tile(m["x0"][:, None, :], (1, N + 1, 1)))
     s.set_all("u", np.zeros((B, N, 2)))
     fe.reset(m["waypoints"])
-    fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"])
+    if mode == "held":
+        s.set_option("pf_predict", 0)
+    moves = mode == "held" or (moving and mode in ("resident", "hostfed"))
+    fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"], vel=m["world_vel"] if moves else None)
     if mode == "plain":
         fe.prepare()                      # the first tick's inputs, once
     s.sync()
     times = []
     for t in range(warmup + ticks):
         t0 = time.perf_counter()
-        if mode == "resident":
+        if mode in ("resident", "held", "static"):
             fe.prepare()
         elif mode == "hostfed":
             x0 = s.get("x0", 0)
@@ -72,7 +80,8 @@ def run(mode, B, ticks, warmup, seed=0):
     out = dict(mode=mode, batch=B, N=N, K=K, ticks=ticks, warmup=warmup, tick_ms_median=statistics.median(timed), tick_ms_min=min(timed),
                tick_ms_max=max(timed), linearize_ms_median=float(np.median(lin)), qp_ms_median=float(np.median(qp)),
                pipelined_linearisations_used=int(used), yref_writes=st["yref_writes"], yref_full_rewrite_bytes=B * (N * 16 + 14) * 8,
-               failed_last_tick=int(s.fail_counts(1)[0]))
+               failed_last_tick=int(s.fail_counts(1)[0]), moving=bool(moves),
+               p_lh_full_rewrite_bytes=B * ((N + 1) * 2 * K + N * K) * 8 if moves and mode != "held" else 0)
     s.close()
     return out
 
@@ -84,9 +93,10 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--modes", default=",".join(MODES))
+    ap.add_argument("--moving", action="store_true", help="the world of the front-end modes moves (every stage of p / lh per tick)")
     a = ap.parse_args()
     for r in range(a.runs):
         for mode in a.modes.split(","):
-            line = run(mode, a.batch, a.ticks, a.warmup)
+            line = run(mode, a.batch, a.ticks, a.warmup, moving=a.moving)
             line["run"] = r
             print(json.dumps(line), flush=True)
