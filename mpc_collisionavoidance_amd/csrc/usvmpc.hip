@@ -10,7 +10,8 @@
 //
 // Build parts.  The QP kernel templates are what takes minutes to compile, and one (model, obstacle chunks) pair has nothing in common
 // with another: __graft_entry__.build() therefore compiles THIS file several times in parallel, -DUSV_PART=0 for the C ABI, the handle
-// bookkeeping, the launch policy and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
+// bookkeeping, the launches (launch_qp carries out the plan of qp_plan.hpp, where the launch policy lives as a host-only function of plain
+// numbers: tests/test_qp_plan.py) and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
 // kernels_for<M, KCH, SOFT> (explicit instantiation in its part, extern template in part 0, which calls it) - and links the objects.
 // Without USV_PART everything is one translation unit (the generated-model libraries of genbuild.py).
 #ifndef USV_PART
@@ -27,6 +28,7 @@
 #include "obstacle_tracks.hpp"
 #include "pf_guidance.hpp"
 #include "qp_ipm.hpp"
+#include "qp_plan.hpp"
 #include "sim.hpp"
 #include "cond_launch.hpp"
 #ifdef USV_GEN_MODEL_HEADER // a model generated from a symbolic definition (codegen.py): struct ModelGen
@@ -215,8 +217,7 @@ using group_kernel_t = void (*)(DevPtrs, long); // (the lineariser, the multipli
 // The kernels of one (model, obstacle chunks) pair for the handle's current row layout (kernels_for), and what the launch policy needs to
 // know about them.  A null kernel: that mapping does not exist for the layout.
 struct Kernels {
-    qp_kernel_t qp, qp_lds, qp_aux;              // four instances per wave: planes in HBM / the workspace in LDS / the aux plane in LDS
-    qp_kernel_t wide_lds1, wide_hbm1, wide_lds4, wide_hbm4; // the latency mapping: [planes in LDS, in HBM] x [one wave, four waves per instance]
+    qp_kernel_t qp[SLOT_QP_KERNELS];             // by QpSlot (qp_plan.hpp): four instances per wave, the latency mapping
     qp_resume_t resume, resume_lds;              // the follow-up launch of a hand-over: over the planes in HBM / after copying them into LDS
     qp_resume_co_t resume_co;                    // ... and its co-resident form (usv_qp_resume_co)
     int nplw, ex_lds, ex_hbm;                    // planes per stage an instance keeps in LDS; planes of the exchange area (qp_ipm.hpp NPLW, EX_N)
@@ -234,10 +235,10 @@ void set_wide(Kernels &k)
     using WL = WsLayout<M, KCH, SOFT, SOFTBOX>;
     constexpr bool packed = KCH > 0 && !SOFTBOX && !UNPACKED; // (the packed layouts leave the four box planes out of the LDS map)
     constexpr bool resumes = !(SOFTBOX || (UNPACKED && KCH > 0));
-    k.wide_lds1 = wide_kernel<M, KCH, SOFT, MERGE, true, 1, SOFTBOX, UNPACKED>();
-    k.wide_hbm1 = wide_kernel<M, KCH, SOFT, MERGE, false, 1, SOFTBOX, UNPACKED>();
-    k.wide_lds4 = wide_kernel<M, KCH, SOFT, MERGE, true, 4, SOFTBOX, UNPACKED>();
-    k.wide_hbm4 = wide_kernel<M, KCH, SOFT, MERGE, false, 4, SOFTBOX, UNPACKED>();
+    k.qp[SLOT_WIDE_LDS1] = wide_kernel<M, KCH, SOFT, MERGE, true, 1, SOFTBOX, UNPACKED>();
+    k.qp[SLOT_WIDE_HBM1] = wide_kernel<M, KCH, SOFT, MERGE, false, 1, SOFTBOX, UNPACKED>();
+    k.qp[SLOT_WIDE_LDS4] = wide_kernel<M, KCH, SOFT, MERGE, true, 4, SOFTBOX, UNPACKED>();
+    k.qp[SLOT_WIDE_HBM4] = wide_kernel<M, KCH, SOFT, MERGE, false, 4, SOFTBOX, UNPACKED>();
     k.resume = resumes ? resume_kernel<M, KCH, SOFT, MERGE>() : nullptr;
     k.resume_lds = resumes ? resume_kernel<M, KCH, SOFT, MERGE, true>() : nullptr;
     k.resume_co = resumes ? resume_co_kernel<M, KCH, SOFT, MERGE>() : nullptr;
@@ -746,32 +747,26 @@ struct usvmpc_handle {
     bool merge_rows;
     bool dynamic_rows;        // QP kernel as a persistent launch whose rows pull instances from a queue (option "dynamic_rows")
     int lds_mode;             // workspace of the QP kernel in LDS: -1 when the batch is small enough (default), 0 never, 1 whenever it fits
-    long lds_cap;             // waves an LDS-workspace launch holds at once (0: not yet known)
     int wide_mode;            // the latency mapping (one instance per wave, QpIpm WIDE): -1 for small batches (default), 0 never, 1 whenever it applies
-    long wide_cap;            // waves a launch of the wide kernel holds at once (0: not yet known, -1: does not fit)
-    long wide_hbm_cap;        // the same for the wide kernel over planes in HBM (horizons that do not fit LDS)
     int wide_waves;           // waves per instance of the latency mapping: -1 (default) four for soft-row OCPs and two obstacle chunks while the batch is at most one instance per CU, else one; 1; 4
-    long wide4_cap, wide4_hbm_cap; // workgroups of four waves a launch holds at once (0: not yet known, -1: does not fit)
     int last_wide;            // the last RTI launch ran on the wide kernel
     int handover_iter;        // option "handover_iter": IPM iterations after which a row of a drained launch hands its instance to the follow-up launch (0: never)
     int *d_susp_count, *d_susp_list; // [RING] instances each of the last launches handed over / [B] their groups
     double *d_susp_rec;       // [B][4] (DevPtrs::susp_rec)
-    long resume_cap;          // workgroups of the follow-up launch (0: not yet known, -1: the kernel cannot be launched)
     // the follow-up kernel beside the draining launch (usv_qp_resume_co; option "handover_co": -1 = when the follow-up works in LDS, 0 never, 1 the same)
     int handover_co;
     int co_spin_limit;        // polls of ~1 us a co-resident workgroup waits for its entry before it gives up (option "handover_co_spin")
-    long co_wgs;              // workgroups of the co-resident launch (option "handover_co_wgs"; 0: one per CU - launch_qp says why)
+    long co_wgs;              // workgroups of the co-resident launch (option "handover_co_wgs"; 0: one per CU - qp_plan.hpp says why)
     bool co_ready;            // co_stream, ev_co_pre / ev_co_end and d_co_ctl exist (made together on first use: co_prepare)
     hipStream_t co_stream;
     hipEvent_t ev_co_pre, ev_co_end;
     int *d_co_ctl;            // [RING][8] DevPtrs::co_ctl of the last launches
     bool ev3_set[RING];       // ev[.][3] was recorded for that solve
-    bool resume_lds, handover_lds; // the follow-up launch copies the planes into LDS (chosen with resume_cap) / option "handover_lds"
+    bool handover_lds;        // option "handover_lds": the follow-up launch copies the planes into LDS when the horizon fits
     long max_waves;           // cap on the persistent waves of the QP kernel (0: as many as the device holds)
     int ncu;                  // compute units of the device
-    long qp_cap;              // groups a full-occupancy launch of the QP kernel holds at once (0: not yet known)
+    QpCaps caps;              // what the occupancy queries said about the QP kernels (qp_plan.hpp)
     bool aux_lds;             // option "aux_in_lds": the aux plane of an RTI solve in the waves' LDS when the horizon fits (default on)
-    long aux_cap;             // the same for the aux-in-LDS instantiation (0: not yet known, -1: does not fit / would cost a wave)
     bool map_changed;         // the group -> instance map differs from the one the workspace's multipliers were written under
     unsigned noise_mask;      // states usvmpc_advance disturbs (option "disturbance_mask"; default: all)
     long long instance_offset; // global index of the handle's first instance (option "instance_offset"): keys the disturbance
@@ -871,10 +866,10 @@ Kernels kernels_for(const usvmpc_handle *h)
                               : pack ? &usv_qp_export<M, KCH, SOFT, CANPACK, false> : &usv_qp_export<M, KCH, SOFT, false, false>;
     k.npt_hard = WsLayout<M, KCH, SOFT, false>::NPT; k.npt_soft = WsLayout<M, KCH, SOFT, true>::NPT;
     k.kch = KCH; k.soft = SOFT;
-    auto qp = [&k](qp_kernel_t q, qp_kernel_t q_lds = nullptr, qp_kernel_t q_aux = nullptr) { k.qp = q; k.qp_lds = q_lds; k.qp_aux = q_aux; };
+    auto qp = [&k](qp_kernel_t q, qp_kernel_t q_lds = nullptr, qp_kernel_t q_aux = nullptr) { k.qp[SLOT_QP] = q; k.qp[SLOT_QP_LDS] = q_lds; k.qp[SLOT_QP_AUX] = q_aux; };
     // (one row pass when every box row rides in a slot lane: qp_ipm.hpp, MERGE)
     const bool merge = pack && h->merge_rows && !S.box_dense;
-#ifdef USV_BENCH_ONLY // development builds (tools/dev_build.sh): only the instantiation the bench workload runs (k.qp null for any other layout)
+#ifdef USV_BENCH_ONLY // development builds (tools/dev_build.sh): only the instantiation the bench workload runs (k.qp[SLOT_QP] null for any other layout)
     if (!(S.hdiag && pack && !S.any_bsoft)) return k;
     if (merge) {
         qp(&usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, false, CANPACK>, &usv_qp_rti<M, KCH, SOFT, true, CANPACK, false, true, CANPACK>,
@@ -975,14 +970,6 @@ void dev_free(usvmpc_handle *h, void *p, size_t nbytes)
     (void)hipStreamSynchronize(h->stream);
     (void)hipFree(p);
     h->bytes -= nbytes;
-}
-
-// Forget what the occupancy queries said about the QP kernels: whatever changes WHICH kernel a launch takes (row layout, mapping,
-// wave cap, workspace placement) makes launch_qp ask again - for every kernel of the handle's table.
-void reset_caps(usvmpc_handle *h)
-{
-    h->qp_cap = 0; h->lds_cap = 0; h->aux_cap = 0;
-    h->wide_cap = 0; h->wide_hbm_cap = 0; h->wide4_cap = 0; h->wide4_hbm_cap = 0; h->resume_cap = 0;
 }
 
 struct Field {
@@ -1350,13 +1337,11 @@ void cond_release(usvmpc_handle *h)
 
 // Workgroups of `block` threads a CU holds of `kern` with `dyn` bytes of dynamic LDS (the kernel's limit raised to that first); 0: it does
 // not fit - static and dynamic LDS over a CU's 160 KB - or a call failed
-template <class F>
-int blocks_per_cu(F kern, int block, size_t dyn)
+int blocks_per_cu(const void *f, int block, size_t dyn)
 {
-    const void *f = (const void *)kern;
     hipFuncAttributes fa;
     int nb = 0;
-    if (f == nullptr || hipFuncGetAttributes(&fa, f) != hipSuccess || fa.sharedSizeBytes + dyn > 160u * 1024u || set_dynamic_lds(f, dyn) != hipSuccess ||
+    if (f == nullptr || hipFuncGetAttributes(&fa, f) != hipSuccess || fa.sharedSizeBytes + dyn > (size_t)CU_LDS_BYTES || set_dynamic_lds(f, dyn) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, block, dyn) != hipSuccess)
         return 0;
     return nb;
@@ -1388,217 +1373,71 @@ bool co_prepare(usvmpc_handle *h)
     return ok;
 }
 
-// An RTI solve is ONE launch of as many waves as the device holds at once; their rows start on the first groups and
-// pull the remaining ones from a queue as they finish (qp_ipm.hpp).  The full SQP keeps one group per row: its later
-// iterations find their multipliers in the group's part of the workspace.
-// Small batches: the planes of every instance in flight fit in LDS (160 KB per CU), and a solve whose sweeps wait for
-// HBM at every stage - nothing else runs on the CU to hide it - becomes a solve on LDS.  rows_lds instances per wave
-// (as many whole horizons as fit), one wave per CU at a time; further instances come through the same queue.
+// The QP launches of an RTI solve or of one iteration of the full SQP, as qp_plan.hpp's plan_qp lays them out for the handle's sizes, options and kernel table (every threshold of
+// the mapping lives there, with the measurement behind it); here: the occupancy queries it asks, the buffers of a first hand-over, the
+// launches.
 int launch_qp(usvmpc_handle *h, const Kernels &k, int phase)
 {
-    const int qp_block = 64;
-    const long qp_groups = h->Bp;
-    hipEvent_t *ev = h->ev[h->nsolves % usvmpc_handle::RING];
-    const long lds_inst = (long)(h->N + 1) * h->spec.npt * 128;
-    h->last_wide = 0;
-    h->ptrs.susp_count = nullptr; h->ptrs.susp_list = nullptr; h->ptrs.susp_rec = nullptr; h->ptrs.handover_iter = 0; h->ptrs.co_ctl = nullptr; // (set by the path that hands over)
-    // Four waves per instance (qp_ipm.hpp, WW): a workgroup = a whole CU shares out the row work of 16 consecutive stages - for the
-    // single instance and batches of at most one instance per CU.
-    if (k.wide_lds4 != nullptr && phase == 0 && h->wide_mode != 0 && h->wide_waves != 1 && h->ncu > 0) {
-        const size_t pl = (size_t)(h->N + 1) * (size_t)k.nplw * 128;
-        const size_t b4 = pl + (size_t)16 * k.ex_lds * 128 + 128, x4 = (size_t)16 * k.ex_hbm * 128 + 128;
-        const long win_bytes = (long)std::min(h->N + 1, 16) * h->Bp * h->spec.npt * 128; // (the window of a block of 16 stages: 32-bit offsets)
-        if (h->wide4_cap == 0) h->wide4_cap = blocks_per_cu(k.wide_lds4, 4 * qp_block, b4) > 0 ? (long)h->ncu : -1;
-        if (h->wide4_cap < 0 && h->wide4_hbm_cap == 0)
-            h->wide4_hbm_cap = (win_bytes < (1L << 32) && blocks_per_cu(k.wide_hbm4, 4 * qp_block, x4) > 0) ? (long)h->ncu : -1;
-        const bool lds = h->wide4_cap > 0;
-        long cap = lds ? h->wide4_cap : h->wide4_hbm_cap;
-        if (cap > 0 && h->max_waves > 0) cap = std::max<long>(1, std::min(cap, h->max_waves / 4)); // option "max_waves" counts wavefronts
-        // default: where the row work is the larger share - the soft-row OCPs and two obstacle chunks (measured, one instance / 256 instances
-        // per tick: usv_model_guidance_ca1 N = 100 / K = 8 1.78 -> 1.59 / 5.6 -> 5.0 ms, N = 40 / K = 10 0.94 -> 0.86 / 2.05 -> 1.87, N = 80 / K = 20
-        // 4.00 -> 3.00 / 8.1 -> 6.2; usv_model_pf_ca N = 80 / K = 20 6.95 -> 6.22 / 10.4 -> 9.6, with ONE chunk of hard rows 0 - 7 % SLOWER: there
-        // the recursion dominates and pays the barriers)
-        // Up to one instance per CU; with the queue and a horizon of 40 or more up to two (tools/latency_probe.py over 13 shapes x 7 batch sizes,
-        // profiles/r05_f_policy_audit.txt: 512 instances 6 - 8 % under one wave each; at N = 20 the second round costs more than the row work saves)
-        const long reach = (h->dynamic_rows && h->N >= 40) ? 2 * cap : cap;
-        // (round 6, profiles/r06_b_policy_audit.txt: ONE chunk of hard rows also gains 2 - 4 % from four waves when the rows are many and the
-        // horizon long - usv_model_pf_ca N = 40 / K = 10: one instance 2.50 -> 2.40 ms, 64: 5.84 -> 5.63, 256: 4.03 -> 3.94; N = 100 / K = 8,
-        // 64: 9.62 -> 9.34; with K = 3 or 4 it loses - up to one instance per CU)
-        const bool hard_many = !k.soft && k.kch == 1 && h->K >= 8 && h->N >= 40 && (long)h->B <= cap;
-        if (cap > 0 && (h->wide_waves == 4 || ((k.soft || k.kch == 2) && (long)h->B <= reach) || hard_many)) {
-            long nw = (long)h->B;
-            int q0 = -1;
-            if (h->dynamic_rows && nw > cap) { nw = cap; q0 = (int)nw; }
-            if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-            hipLaunchKernelGGL(lds ? k.wide_lds4 : k.wide_hbm4, dim3((unsigned)nw), dim3(4 * qp_block), lds ? b4 : x4, h->stream, h->ptrs, nw, phase, q0, 1);
-            h->last_wide = 4;
-            return 0;
+    static_assert(QP_GROUP_LANES == LANES, "qp_plan.hpp sizes the grid of the throughput mapping");
+    QpIn in = {};
+    in.B = h->B; in.Bp = h->Bp; in.N = h->N; in.K = h->K;
+    in.npt = h->spec.npt; in.nu = h->nu; in.aux_dense4 = h->spec.aux_dense4; in.kch = h->kch; in.phase = phase; in.ncu = h->ncu;
+    in.wide_mode = h->wide_mode; in.wide_waves = h->wide_waves; in.lds_mode = h->lds_mode; in.dynamic_rows = h->dynamic_rows;
+    in.max_waves = h->max_waves; in.aux_lds = h->aux_lds; in.handover_iter = h->handover_iter; in.handover_lds = h->handover_lds;
+    in.handover_co = h->handover_co; in.co_wgs = h->co_wgs; in.own_stream = h->own_stream;
+    for (int s = 0; s < SLOT_QP_KERNELS; s++) in.has[s] = k.qp[s] != nullptr;
+    in.has[SLOT_RESUME] = k.resume != nullptr; in.has[SLOT_RESUME_LDS] = k.resume_lds != nullptr; in.has_resume_co = k.resume_co != nullptr;
+    in.nplw = k.nplw; in.ex_lds = k.ex_lds; in.ex_hbm = k.ex_hbm; in.k_kch = k.kch; in.k_soft = k.soft;
+    struct {
+        const Kernels &k;
+        const void *kernel(QpSlot s) const
+        {
+            return s < SLOT_QP_KERNELS ? (const void *)k.qp[s] : s == SLOT_RESUME ? (const void *)k.resume : (const void *)k.resume_lds;
         }
-    }
-    // The latency mapping: ONE instance per wave (qp_ipm.hpp, WIDE) - planes in LDS, the four rows share out the stage-local row
-    // work.  A wave then finishes an instance 1.4x (hard rows) to 1.8x (soft rows) sooner and the device holds a quarter of the instances at once: it pays while
-    // the batch leaves SIMDs idle anyway (a solve of the batch then lasts as long as its hardest instance on a lone wave).
-    if (k.wide_lds1 != nullptr && h->wide_mode != 0 && h->ncu > 0) {
-        if (phase == 0) { // (the launches of a full SQP find their multipliers in the group's planes in HBM: the variant over planes in HBM below)
-            // (in LDS: the planes the solve writes - WsLayout's up to L_zu less the four box planes the packed layouts leave unused)
-            const size_t bytes = (size_t)(h->N + 1) * (size_t)k.nplw * 128 + (size_t)4 * k.ex_lds * 128;
-            if (h->wide_cap == 0) {
-                const int nb = blocks_per_cu(k.wide_lds1, qp_block, bytes);
-                h->wide_cap = nb > 0 ? (long)std::min(nb, 4) * h->ncu : -1; // (one wave per SIMD at most: the point is a lone wave's issue rate)
-                if (h->wide_cap > 0 && h->max_waves > 0) h->wide_cap = std::min(h->wide_cap, h->max_waves); // option "max_waves"
-            }
-            // default: while the batch fits the SIMDs twice over (the queue hands the second half to the waves that finish first)
-            if (h->wide_cap > 0 && (h->wide_mode > 0 || (long)h->B <= 2 * h->wide_cap)) {
-                // (without the queue every instance needs its wave at launch: still correct, later workgroups wait)
-                long nw = (long)h->B;
-                int q0 = -1;
-                if (h->dynamic_rows && nw > h->wide_cap) { nw = h->wide_cap; q0 = (int)nw; }
-                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-                hipLaunchKernelGGL(k.wide_lds1, dim3((unsigned)nw), dim3(qp_block), bytes, h->stream, h->ptrs, nw, phase, q0, 1);
-                h->last_wide = 1;
-                return 0;
-            }
+        int blocks(QpSlot s, int block, size_t dyn) const { return blocks_per_cu(kernel(s), block, dyn); }
+        long static_lds(QpSlot s) const
+        {
+            hipFuncAttributes fa;
+            return hipFuncGetAttributes(&fa, kernel(s)) == hipSuccess ? (long)fa.sharedSizeBytes : 0;
         }
-        // The horizon's planes do not fit a CU's LDS (the reference node's own N = 100: nmpc_guidance_ca1.cpp:64), or the launch belongs to a
-        // full SQP: the same sweeps over the planes in HBM / L2 - the four rows of a wave address the four stages of a block through one
-        // window, the next block's row planes and the next stage's recursion planes are in flight ahead of their use.
-        const long win_bytes = (long)std::min(h->N + 1, 4) * h->Bp * h->spec.npt * 128; // (the window of a block of four stages: 32-bit offsets)
-        if ((h->wide_cap < 0 || phase != 0) && k.wide_hbm1 != nullptr && win_bytes < (1L << 32)) {
-            const size_t xbytes = (size_t)4 * k.ex_hbm * 128;
-            if (h->wide_hbm_cap == 0) {
-                const int nb = blocks_per_cu(k.wide_hbm1, qp_block, xbytes);
-                h->wide_hbm_cap = nb > 0 ? (long)std::min(nb, 4) * h->ncu : -1;
-                if (h->wide_hbm_cap > 0 && h->max_waves > 0) h->wide_hbm_cap = std::min(h->wide_hbm_cap, h->max_waves);
-            }
-            // default: an RTI solve while the batch fits the resident waves twice over, as with the planes in LDS (measured at 2 048 instances, N = 80 / 100:
-            // 1.2 - 1.3x the throughput mapping; at 4 096 the throughput mapping is ahead); the launches of a full SQP once (no queue there)
-            const long reach = (phase == 0 && h->dynamic_rows) ? 2 * h->wide_hbm_cap : h->wide_hbm_cap;
-            if (h->wide_hbm_cap > 0 && (h->wide_mode > 0 || (long)h->B <= reach)) {
-                long nw = (long)h->B;
-                int q0 = -1;
-                // (full SQP: one group per workgroup for the whole call - its multipliers persist in the group's planes)
-                if (h->dynamic_rows && phase == 0 && nw > h->wide_hbm_cap) { nw = h->wide_hbm_cap; q0 = (int)nw; }
-                if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-                hipLaunchKernelGGL(k.wide_hbm1, dim3((unsigned)nw), dim3(qp_block), xbytes, h->stream, h->ptrs, nw, phase, q0, 1);
-                h->last_wide = 1;
-                return 0;
-            }
-        }
+    } probe = {k};
+    const QpPlan p = plan_qp(in, h->caps, probe);
+    const int slot_now = (int)(h->nsolves % usvmpc_handle::RING);
+    hipEvent_t *ev = h->ev[slot_now];
+    h->last_wide = p.mapping;
+    h->ptrs.susp_count = nullptr; h->ptrs.susp_list = nullptr; h->ptrs.susp_rec = nullptr; h->ptrs.handover_iter = 0; h->ptrs.co_ctl = nullptr; // (set below when the launch hands over)
+    if (p.q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
+    if (p.hand_ready && !h->d_susp_list) {
+        if (dev_alloc(h, &h->d_susp_count, (size_t)usvmpc_handle::RING, true) || dev_alloc(h, &h->d_susp_list, (size_t)h->B, false) ||
+            dev_alloc(h, &h->d_susp_rec, (size_t)h->B * 4, false))
+            return USVMPC_E_HIP;
     }
-    // (the kernel's own static LDS - exchange area, parked constants - comes out of the same 160 KB)
-    long lds_static = 0;
-    if (k.qp_lds != nullptr) {
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, (const void *)k.qp_lds) == hipSuccess) lds_static = (long)fa.sharedSizeBytes;
+    if (p.hand) {
+        h->ptrs.susp_count = h->d_susp_count + slot_now;
+        h->ptrs.susp_list = h->d_susp_list;
+        h->ptrs.susp_rec = h->d_susp_rec;
+        h->ptrs.handover_iter = p.hand_iter;
     }
-    const int rows_lds = (int)std::min<long>(4, (160L * 1024 - lds_static) / lds_inst);
-    bool use_lds = phase == 0 && h->lds_mode != 0 && k.qp_lds != nullptr && rows_lds >= 1 && h->ncu > 0;
-    // by default only while one round of workgroups covers the batch: measured on usv_model_pf_ca, N = 20 / K = 3, the solve
-    // of 512 instances takes 5.9 ms with the planes in LDS against 6.5 ms in HBM, at 1024 (two rounds) 7.5 against 7.1
-    if (use_lds && h->lds_mode < 0) use_lds = (long)h->B <= (long)rows_lds * h->ncu;
-    if (use_lds) {
-        const size_t bytes = (size_t)rows_lds * lds_inst;
-        if (h->lds_cap == 0) {
-            const int nb = blocks_per_cu(k.qp_lds, qp_block, bytes);
-            h->lds_cap = nb > 0 ? (long)nb * h->ncu : -1;
-        }
-        if (h->lds_cap > 0) {
-            long nw = ((long)h->B + rows_lds - 1) / rows_lds;
-            int q0 = -1;
-            if (h->dynamic_rows && nw > h->lds_cap) { nw = h->lds_cap; q0 = (int)(nw * rows_lds); }
-            if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-            hipLaunchKernelGGL(k.qp_lds, dim3((unsigned)nw), dim3(qp_block), bytes, h->stream, h->ptrs, nw * rows_lds, phase, q0, rows_lds);
-            return 0;
-        }
-    }
-    long ng = qp_groups;
-    int q0 = -1;
-    if (h->dynamic_rows && phase == 0 && h->qp_cap == 0) {
-        const int nb = blocks_per_cu(k.qp, qp_block, 0);
-        h->qp_cap = (nb > 0 && h->ncu > 0) ? 4L * nb * h->ncu : -1;
-    }
-    // The aux plane in LDS (qp_ipm.hpp, AUXLDS): 4 rows x (N + 1) stages x at most ten values beside the kernel's static LDS - taken
-    // when it does not cost a resident wave (usv_model_pf_ca at N = 40, K = 10: 13.1 KB + 6.7 KB of the 20 KB a wave may have)
-    size_t aux_bytes = 0;
-    if (phase == 0 && k.qp_aux != nullptr && h->aux_lds && h->dynamic_rows && h->qp_cap > 0) {
-        aux_bytes = (size_t)4 * (h->N + 1) * (size_t)(h->spec.aux_dense4 + (h->kch > 0 ? 2 : 0) + 2 * h->nu) * sizeof(double);
-        if (h->aux_cap == 0) {
-            const long cap = 4L * blocks_per_cu(k.qp_aux, qp_block, aux_bytes) * h->ncu;
-            h->aux_cap = cap >= h->qp_cap ? cap : -1;
-        }
-        if (h->aux_cap < 0) aux_bytes = 0;
-    }
-    const qp_kernel_t kern = aux_bytes ? k.qp_aux : k.qp;
-    if (h->dynamic_rows && phase == 0) {
-        long cap = aux_bytes ? std::min(h->aux_cap, h->qp_cap) : h->qp_cap;
-        if (h->max_waves > 0 && 4L * h->max_waves < cap) cap = 4L * h->max_waves; // option "max_waves": fewer resident waves
-        if (cap > 0 && cap < qp_groups) { ng = cap; q0 = (int)ng; }
-    }
-    if (q0 >= 0) HIP_TRY(h, hipMemsetAsync(h->ptrs.queue, 0, sizeof(int), h->stream));
-    // Hand-over of long runners (qp_ipm.hpp, QpIpm::suspend): a launch that refills from the queue ends with a few rows finishing
-    // instances of 30 - 50 iterations on an idling device; past "handover_iter" iterations those go to a follow-up launch on the
-    // latency mapping (one instance per wave over the same planes: 1.6x per pass for usv_model_pf_ca at N = 40).  Scheduling only.
-    bool hand = false;
-    size_t xbytes = (size_t)4 * k.ex_hbm * 128;
-    qp_resume_t kern_resume = k.resume;
-    int hand_it = 0;
-    if (phase == 0 && h->handover_iter != 0 && k.resume != nullptr && (long)std::min(h->N + 1, 4) * h->Bp * h->spec.npt * 128 < (1L << 32)) {
-        const size_t lbytes = (size_t)(h->N + 1) * (size_t)k.nplw * 128 + (size_t)4 * k.ex_lds * 128;
-        if (h->resume_cap == 0) {
-            // (planes in LDS when the horizon fits - option "handover_lds", default on -, else over the planes in HBM)
-            const int nb_lds = (h->handover_lds && h->ncu > 0) ? blocks_per_cu(k.resume_lds, qp_block, lbytes) : 0;
-            const int nb = nb_lds > 0 ? nb_lds : blocks_per_cu(k.resume, qp_block, xbytes);
-            h->resume_lds = nb_lds > 0;
-            h->resume_cap = (nb > 0 && h->ncu > 0) ? (long)std::min(nb, 4) * h->ncu : -1;
-        }
-        if (h->resume_lds) { kern_resume = k.resume_lds; xbytes = lbytes; }
-        if (h->resume_cap > 0 && !h->d_susp_list) {
-            if (dev_alloc(h, &h->d_susp_count, (size_t)usvmpc_handle::RING, true) || dev_alloc(h, &h->d_susp_list, (size_t)h->B, false) ||
-                dev_alloc(h, &h->d_susp_rec, (size_t)h->B * 4, false))
-                return USVMPC_E_HIP;
-        }
-        // default (-1): past 20 iterations when the follow-up works in LDS AND the batch is at most three times what the device holds at once
-        // (re-measured in round 6 under the default QP solver profile, whose solves are shorter - profiles/r06_handover_co.txt: with the
-        // follow-up kernel beside the launch -18 % per tick at 4 096 instances, -13 % at 8 192, -4 % at 16 384, 0 at 32 768, +1 % at
-        // 65 536; with it only behind the launch nothing is gained any more at any size), never when it would run over the planes in HBM (a
-        // loss: profiles/r05_handover.txt)
-        const bool small = h->qp_cap > 0 && (long)h->B <= 3 * h->qp_cap;
-        hand_it = h->handover_iter > 0 ? h->handover_iter : ((h->resume_lds && small) ? 20 : 0);
-        hand = h->resume_cap > 0 && hand_it > 0;
-    }
-    h->ptrs.susp_count = hand ? h->d_susp_count + h->nsolves % usvmpc_handle::RING : nullptr;
-    h->ptrs.susp_list = hand ? h->d_susp_list : nullptr;
-    h->ptrs.susp_rec = hand ? h->d_susp_rec : nullptr;
-    h->ptrs.handover_iter = hand ? hand_it : 0;
-    const dim3 qg((unsigned)((ng * LANES + qp_block - 1) / qp_block)), qb(qp_block);
-    // The follow-up kernel BESIDE the draining launch (usv_qp_resume_co): on a stream of its own, eligible together with the main launch;
-    // what it does not get to is done by the follow-up launch behind the main one.  With the planes copied into LDS only (the form that pays).
-    const bool co = hand && h->handover_co != 0 && h->resume_lds && k.resume_co != nullptr && h->own_stream && co_prepare(h);
+    // (when its stream cannot be made the option goes off for the handle and the launch goes on without it: co_prepare)
+    const bool co = p.co && co_prepare(h);
     if (co) {
-        HIP_TRY(h, set_dynamic_lds((const void *)k.resume_co, xbytes));
-        h->ptrs.co_ctl = h->d_co_ctl + 8 * (h->nsolves % usvmpc_handle::RING);
+        HIP_TRY(h, set_dynamic_lds((const void *)k.resume_co, p.hand_bytes));
+        h->ptrs.co_ctl = h->d_co_ctl + 8 * slot_now;
         HIP_TRY(h, hipMemsetAsync(h->ptrs.co_ctl, 0, 8 * sizeof(int), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->d_susp_list, 0xff, (size_t)h->B * sizeof(int), h->stream)); // (-1: no entry yet)
         HIP_TRY(h, hipEventRecord(h->ev_co_pre, h->stream));
     }
-    hipLaunchKernelGGL(kern, qg, qb, aux_bytes, h->stream, h->ptrs, ng, phase, q0, 4);
+    hipLaunchKernelGGL(k.qp[p.slot], dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, h->stream, h->ptrs, p.ngroups, phase, p.q0, p.rows);
     if (co) {
         hipLaunchKernelGGL(usv_co_done, dim3(1), dim3(1), 0, h->stream, h->ptrs.co_ctl);
         HIP_TRY(h, hipStreamWaitEvent(h->co_stream, h->ev_co_pre, 0));
-        // One follow-up workgroup per CU unless the caller asks otherwise (option "handover_co_wgs"): what finds room BESIDE the main launch's
-        // workgroups at once (75 KB of LDS next to their eight times 10 KB).  With two per CU - what fits once the main launch has left - some
-        // of them wait to be placed while the main launch runs, and about one tick in 1 500 then stalled until their waits ran out: the main
-        // launch took 410 ms instead of 9 (tools/co_soak.py, docs/rounds/r06.md section 8: 0 stalls in 16 000 ticks with one per CU, same pace).
-        long nco = std::min<long>(h->resume_cap, (long)h->B);
-        nco = std::min<long>(nco, h->co_wgs > 0 ? (long)h->co_wgs : (long)std::max(h->ncu, 1));
-        hipLaunchKernelGGL(k.resume_co, dim3((unsigned)nco), dim3(qp_block), xbytes, h->co_stream, h->ptrs, (int)qg.x, (int)h->B, h->co_spin_limit);
+        hipLaunchKernelGGL(k.resume_co, dim3((unsigned)p.co_wgs), dim3(QP_BLOCK), p.hand_bytes, h->co_stream, h->ptrs, (int)p.grid, (int)h->B, h->co_spin_limit);
         HIP_TRY(h, hipEventRecord(h->ev_co_end, h->co_stream));
     }
-    if (hand) {
+    if (p.hand) {
         HIP_TRY(h, hipEventRecord(ev[3], h->stream));
-        h->ev3_set[h->nsolves % usvmpc_handle::RING] = true;
-        const long nwg = std::min<long>(h->resume_cap, (long)h->B);
-        hipLaunchKernelGGL(kern_resume, dim3((unsigned)nwg), dim3(qp_block), xbytes, h->stream, h->ptrs);
+        h->ev3_set[slot_now] = true;
+        hipLaunchKernelGGL(p.hand_lds ? k.resume_lds : k.resume, dim3((unsigned)p.hand_wgs), dim3(QP_BLOCK), p.hand_bytes, h->stream, h->ptrs);
     }
     if (co) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_co_end, 0)); // (the tick's QPs are solved when both kernels are through)
     return 0;
@@ -1740,7 +1579,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         h->err = "workspace layout mismatch between host and kernels";
         return USVMPC_E_ARG;
     }
-    if (!cond && k.qp == nullptr) { h->err = "development build: bench instantiation only"; return USVMPC_E_ARG; }
+    if (!cond && k.qp[SLOT_QP] == nullptr) { h->err = "development build: bench instantiation only"; return USVMPC_E_ARG; }
     const int rcq = cond ? launch_cond(h) : launch_qp(h, k, phase);
     if (rcq) return rcq;
     HIP_TRY(h, hipGetLastError());
@@ -2032,15 +1871,13 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->step_on_advance = true; h->clear_reset = false;
     h->cond_N2 = 0; h->d_cond_dims = nullptr; h->d_cond_scratch = nullptr; h->cond_teams = 0; h->cond_lds = 0;
     h->dynamic_rows = true;
-    h->qp_cap = 0;
+    h->caps.reset();
     h->aux_lds = true;
-    h->aux_cap = 0;
     h->lds_mode = -1;
-    h->lds_cap = 0;
-    h->wide_mode = -1; h->wide_cap = 0; h->wide_hbm_cap = 0; h->last_wide = 0;
-    h->wide_waves = -1; h->wide4_cap = 0; h->wide4_hbm_cap = 0;
+    h->wide_mode = -1; h->last_wide = 0;
+    h->wide_waves = -1;
     h->handover_co = -1; h->co_spin_limit = 200000; h->co_wgs = 0; h->co_ready = false; h->co_stream = nullptr; h->ev_co_pre = nullptr; h->ev_co_end = nullptr; h->d_co_ctl = nullptr;
-    h->handover_iter = -1; for (bool &e : h->ev3_set) e = false; h->resume_lds = false; h->handover_lds = true; h->d_susp_count = nullptr; h->d_susp_list = nullptr; h->d_susp_rec = nullptr; h->resume_cap = 0;
+    h->handover_iter = -1; for (bool &e : h->ev3_set) e = false; h->handover_lds = true; h->d_susp_count = nullptr; h->d_susp_list = nullptr; h->d_susp_rec = nullptr;
     h->max_waves = 0;
     {
         hipDeviceProp_t prop;
@@ -2608,7 +2445,7 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         if (!h->sort_enabled && h->ptrs.perm) { h->ptrs.perm = nullptr; h->map_changed = true; }
         return 0;
     }
-    if (s == "max_waves") { h->max_waves = (long)value; reset_caps(h); cond_release(h); return 0; }
+    if (s == "max_waves") { h->max_waves = (long)value; h->caps.reset(); cond_release(h); return 0; }
     if (s == "keep_multipliers") { // create the "lam" / "t" buffers now (a partially condensed solve fills them only if they exist)
         if (value == 0.0) return 0;
         DevPtrs &P = h->ptrs;
@@ -2646,25 +2483,25 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         h->lin_pairs = (int)value;
         return 0;
     }
-    if (s == "aux_in_lds") { h->aux_lds = value != 0.0; reset_caps(h); return 0; }
+    if (s == "aux_in_lds") { h->aux_lds = value != 0.0; h->caps.reset(); return 0; }
     if (s == "lds_workspace") { // -1: when the batch is small (default), 0: never, 1: whenever an instance's planes fit in LDS
         h->lds_mode = value < 0.0 ? -1 : (value > 0.0 ? 1 : 0);
-        reset_caps(h);
+        h->caps.reset();
         return 0;
     }
     if (s == "wide") { // the latency mapping, one instance per wave: -1 for batches that leave SIMDs idle (default), 0 never, 1 whenever it applies
         h->wide_mode = value < 0.0 ? -1 : (value > 0.0 ? 1 : 0);
-        reset_caps(h);
+        h->caps.reset();
         return 0;
     }
     if (s == "wide_waves") { // waves per instance of the latency mapping: -1 (default) four for soft-row OCPs / two obstacle chunks up to one instance per CU, else one; 1; 4
         h->wide_waves = value < 0.0 ? -1 : (value >= 4.0 ? 4 : 1);
-        reset_caps(h);
+        h->caps.reset();
         return 0;
     }
     if (s == "dynamic_rows") { // 0: one group per row for the whole launch (the rows of a wave wait for its slowest)
         h->dynamic_rows = value != 0.0;
-        reset_caps(h);
+        h->caps.reset();
         return 0;
     }
     if (s == "cond_pred_corr" || s == "cpc_factor" || s == "hpipm_mode") {
@@ -2687,10 +2524,10 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
     }
     if (s == "handover_iter") { // IPM iterations after which a row of a drained launch hands its instance over to the follow-up launch; 0: never
         if (value > 1e6) { h->err = "handover_iter out of range"; return USVMPC_E_ARG; }
-        h->handover_iter = value < 0.0 ? -1 : (int)value;   // (-1: the default - launch_qp: past 20 for small batches when the follow-up works in LDS, else never)
+        h->handover_iter = value < 0.0 ? -1 : (int)value;   // (-1: the default - qp_plan.hpp: past 20 for small batches when the follow-up works in LDS, else never)
         return 0;
     }
-    if (s == "handover_lds") { h->handover_lds = value != 0.0; reset_caps(h); return 0; }
+    if (s == "handover_lds") { h->handover_lds = value != 0.0; h->caps.reset(); return 0; }
     if (s == "handover_co") { h->handover_co = value < 0.0 ? -1 : (value != 0.0 ? 1 : 0); return 0; } // the follow-up kernel beside the draining launch (default) or only behind it
     if (s == "handover_co_spin") { if (!(value >= 1.0 && value <= 2e9)) { h->err = "handover_co_spin out of range"; return USVMPC_E_ARG; } h->co_spin_limit = (int)value; return 0; }
     if (s == "handover_co_wgs") { if (!(value >= 0.0 && value <= 1e6)) { h->err = "handover_co_wgs out of range"; return USVMPC_E_ARG; } h->co_wgs = (long)value; return 0; } // the follow-up launch with the planes copied into LDS when the horizon fits (default), or always over the planes in HBM
@@ -2708,7 +2545,7 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
     }
     if (s == "merge_box_rows") { // 1 (default): box rows processed in their slot lanes when all of them ride there
         h->merge_rows = value != 0.0;   // (another set of kernels: merged / two-pass instantiations, wide ones included)
-        reset_caps(h);
+        h->caps.reset();
         return 0;
     }
     if (s == "host_mirror") { // 0: drop the pinned host mirror of the caller-visible arrays (every set / get then goes to the device)
@@ -2725,7 +2562,7 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
     }
     if (s == "static_obstacles" || s == "pack_box_rows") {
         if (s == "static_obstacles") { h->spec.p_static = value != 0.0; h->tracks_dirty = true; } // (the stages the prediction writes change)
-        else { h->spec.boxpack = (value != 0.0 && h->spec.boxpack_ok) ? 1 : 0; reset_caps(h); h->layout_dirty = true; }
+        else { h->spec.boxpack = (value != 0.0 && h->spec.boxpack_ok) ? 1 : 0; h->caps.reset(); h->layout_dirty = true; }
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipMemcpyAsync(h->d_spec, &h->spec, sizeof(DevSpec), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));

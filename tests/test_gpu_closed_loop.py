@@ -230,7 +230,7 @@ def test_two_handles_on_shards_equal_unsharded(name, B):
 @pytest.mark.parametrize("name,N,K,G,world", [("usv_model_pf_ca", 20, 3, 4096, 8), ("usv_model_guidance_ca1", 20, 3, 4096, 8),
                                                ("usv_model_pf_ca", 40, 10, 3000, 6)])
 def test_shards_that_land_on_the_other_mapping_equal_the_unsharded_batch(name, N, K, G, world):
-    """The mapping is chosen from the size of the handle's batch (usvmpc.hip launch_qp: the latency mapping while the batch leaves SIMDs idle):
+    """The mapping is chosen from the size of the handle's batch (csrc/qp_plan.hpp plan_qp: the latency mapping while the batch leaves SIMDs idle):
     4096 instances in one handle run four per wavefront, the same instances as 8 shards of 512 run one per wavefront (or, soft-row OCP,
     one per workgroup of four).  An instance's result must not depend on which: bit for bit, over a closed loop (VERDICT r04
     weak 2 - the mappings used to agree to rounding only, amplified to 5e-3 by the hard-row model)."""

@@ -105,7 +105,7 @@ def test_full_sqp_kernels_match_oracle(oracle, emu, name, K):
 
 @pytest.mark.parametrize("name,K", [("usv_model", 0), ("usv_model_guidance_ca1", 4), ("usv_model_pf_ca", 3), ("usv_model_pf_ca", 10), ("usv_model_pf_ca", 20)])
 def test_full_sqp_on_the_latency_mapping_equals_the_16_lane_sweeps(emu, name, K):
-    """The launches of a full SQP on the one-instance-per-wave sweeps over planes in HBM (round 5: usvmpc.hip launch_qp takes them for small
+    """The launches of a full SQP on the one-instance-per-wave sweeps over planes in HBM (round 5: csrc/qp_plan.hpp plan_qp takes them for small
     batches; the multipliers persist in the group's planes between the launches of a call, as with the 16-lane sweeps): every output of the
     run equals the 16-lane run's bit for bit - iterate, statuses, SQP iteration counts, NLP residuals; a second call from the converged
     point solves no QP."""
