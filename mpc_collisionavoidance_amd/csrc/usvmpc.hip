@@ -11,7 +11,8 @@
 // Build parts.  The QP kernel templates are what takes minutes to compile, and one (model, obstacle chunks) pair has nothing in common
 // with another: __graft_entry__.build() therefore compiles THIS file several times in parallel, -DUSV_PART=0 for the C ABI, the handle
 // bookkeeping, the launches (launch_qp carries out the plan of qp_plan.hpp, where the launch policy lives as a host-only function of plain
-// numbers: tests/test_qp_plan.py) and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
+// numbers: tests/test_qp_plan.py; launch_solve likewise the plan of lin_plan.hpp - the lineariser's schedule, maps and grids:
+// tests/test_lin_plan.py) and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
 // kernels_for<M, KCH, SOFT> (explicit instantiation in its part, extern template in part 0, which calls it) - and links the objects.
 // Without USV_PART everything is one translation unit (the generated-model libraries of genbuild.py).
 #ifndef USV_PART
@@ -23,6 +24,7 @@
 
 #include "guidance.hpp"
 #include "host_spec.hpp"
+#include "lin_plan.hpp"
 #include "linearize.hpp"
 #include "models.hpp"
 #include "obstacle_tracks.hpp"
@@ -42,6 +44,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 using namespace usv;
@@ -61,8 +64,7 @@ using namespace usv;
 // are the same and n counts ROWS for MODE 0 - 3: 0, 1, 2 the pairs in the same stage-major order, two to a row; 3 the rows of the retire
 // order, padded to whole waves (lin_order.hpp: a wave takes 8 items, the two of a row from one instance); 4 groups as before, the marked
 // stages shared out over the wave's eight halves.
-constexpr int LIN_MODES = 5;
-constexpr int lin_block(int mode) { return mode == 3 ? 64 : 256; }
+// (LIN_MODES, lin_block and the grids: lin_plan.hpp)
 template <class M, int KCH, bool SOFT, bool MULTI, bool PAIR = false, int MODE = 0>
 __global__ void __launch_bounds__(lin_block(MODE), USV_LIN_BLOCKS) usv_linearize(DevPtrs P, long n)
 {
@@ -789,25 +791,15 @@ struct usvmpc_handle {
     bool inflight;            // a copy between mirror and arena may still be running on the stream
     bool out_valid;           // the mirror's [x | u | status] is what the device holds (or newer)
     bool extern_access;       // a device pointer was handed out: the device arrays may change behind the mirror
-    // Pipelined lineariser (option "pipeline_linearize"): the lineariser of tick t + 1 is launched on a second stream right behind the
-    // QP launch of tick t; its workgroups are dispatched as that launch's persistent waves leave, i.e. it runs in the launch's tail
-    // (profiles/r03_tail.txt: the last ~14 ms of a 76 ms launch run on a device that is being vacated).  An instance is linearised
-    // there only when its own results AND those of the instance still owning the target planes are final (DevPtrs::epoch); the few
-    // that were not are redone by a fix-up pass in front of the next QP launch.  The queue order of a tick is then fixed one tick
-    // earlier (from the counts of two solves back).  Scheduling only: results are bit-identical.
+    // Pipelined lineariser (option "pipeline_linearize"): the lineariser of tick t + 1 runs on a second stream beside the QP launch of tick t.
+    // When, under which map and whether what it made still stands is lin_plan.hpp's: the state machine LinSched (no field of it is assigned
+    // in this file - spec_cancel, copy_field, usvmpc_sync and launch_solve call its methods) and the per-solve plan plan_lin, both host-only
+    // and checked on the CPU by tests/test_lin_plan.py.  Here: the option, the HIP objects and the two map buffers the plan names.
     bool pipeline;            // option; used for RTI solves of handles without a host mirror
     hipStream_t aux_stream;   // nullptr until first used
     hipEvent_t ev_pre, ev_spec;
-    int *d_epoch, *d_redo, *d_perm2, *d_inv;
-    long spec_for;            // solve number the outstanding / finished speculative linearisation was made for (-1: none)
-    bool spec_valid;          // ... and nothing it read has been changed by the caller since
-    bool spec_outstanding;    // the second stream may still be writing the lineariser's planes
-    int spec_quiet;           // RTI solves in a row whose ahead-of-time linearisation (had there been one) no caller write invalidated: the
-                              // lineariser runs ahead only from SPEC_QUIET_MIN on - a caller that sets yref / x / u every tick (the reference's
-                              // protocol: scripts/usv_guidance_ca1/main.py:123-130) never pays for a speculative pass that is thrown away
-    long spec_hits, spec_misses; // ahead-of-time linearisations used / discarded (usvmpc_pipeline_stats)
-    const int *spec_perm;     // the group -> instance map it used (= the map the solve spec_for must use)
-    bool spec_fine;           // ... made by usv_linearize MODE 3 (its fix-up is MODE 4) instead of MODE 1 (MODE 2): launch_solve
+    int *d_epoch, *d_redo, *d_perm2, *d_inv; // (d_perm / d_perm2: LinMap MAP_A / MAP_B)
+    LinSched sched;
     // Option "lin_force_modes" (tests): a solve that would run the whole-batch lineariser runs the pipeline's kernels MODE 3 + MODE 4 in its
     // place, on the main stream - 1: the speculative form with every instance final, then the fix-up (which finds nothing); 2: with no instance final (it
     // marks everything), then the fix-up (which does everything).  Work order as in the pipeline, with the identity as the "running" map.
@@ -843,6 +835,13 @@ struct usvmpc_handle {
     std::vector<void *> allocs;
 };
 
+// Kernels::lin / lin_pair: usv_linearize for one and several RK4 steps (MULTI), every MODE
+template <class M, int KCH, bool SOFT, bool PAIR, int... MODE>
+void set_lin(group_kernel_t (&t)[2][LIN_MODES], std::integer_sequence<int, MODE...>)
+{
+    ((t[0][MODE] = &usv_linearize<M, KCH, SOFT, false, PAIR, MODE>, t[1][MODE] = &usv_linearize<M, KCH, SOFT, true, PAIR, MODE>), ...);
+}
+
 // The kernel table of one (model, obstacle chunks) pair for the handle's current row layout.  (External linkage: a split build defines
 // each instantiation in a translation unit of its own - see "Build parts" at the top.)
 template <class M, int KCH, bool SOFT>
@@ -852,16 +851,8 @@ Kernels kernels_for(const usvmpc_handle *h)
     const DevSpec &S = h->spec;
     const bool pack = CANPACK && S.boxpack != 0;
     Kernels k = {};
-    k.lin[0][0] = &usv_linearize<M, KCH, SOFT, false, false, 0>; k.lin[0][1] = &usv_linearize<M, KCH, SOFT, false, false, 1>; k.lin[0][2] = &usv_linearize<M, KCH, SOFT, false, false, 2>;
-    k.lin[0][3] = &usv_linearize<M, KCH, SOFT, false, false, 3>; k.lin[0][4] = &usv_linearize<M, KCH, SOFT, false, false, 4>;
-    k.lin[1][0] = &usv_linearize<M, KCH, SOFT, true, false, 0>; k.lin[1][1] = &usv_linearize<M, KCH, SOFT, true, false, 1>; k.lin[1][2] = &usv_linearize<M, KCH, SOFT, true, false, 2>;
-    k.lin[1][3] = &usv_linearize<M, KCH, SOFT, true, false, 3>; k.lin[1][4] = &usv_linearize<M, KCH, SOFT, true, false, 4>;
-    if constexpr (PairCols<M>::ENABLED) {
-        k.lin_pair[0][0] = &usv_linearize<M, KCH, SOFT, false, true, 0>; k.lin_pair[0][1] = &usv_linearize<M, KCH, SOFT, false, true, 1>; k.lin_pair[0][2] = &usv_linearize<M, KCH, SOFT, false, true, 2>;
-        k.lin_pair[0][3] = &usv_linearize<M, KCH, SOFT, false, true, 3>; k.lin_pair[0][4] = &usv_linearize<M, KCH, SOFT, false, true, 4>;
-        k.lin_pair[1][0] = &usv_linearize<M, KCH, SOFT, true, true, 0>; k.lin_pair[1][1] = &usv_linearize<M, KCH, SOFT, true, true, 1>; k.lin_pair[1][2] = &usv_linearize<M, KCH, SOFT, true, true, 2>;
-        k.lin_pair[1][3] = &usv_linearize<M, KCH, SOFT, true, true, 3>; k.lin_pair[1][4] = &usv_linearize<M, KCH, SOFT, true, true, 4>;
-    }
+    set_lin<M, KCH, SOFT, false>(k.lin, std::make_integer_sequence<int, LIN_MODES>{});
+    if constexpr (PairCols<M>::ENABLED) set_lin<M, KCH, SOFT, true>(k.lin_pair, std::make_integer_sequence<int, LIN_MODES>{});
     k.qp_export = S.any_bsoft ? &usv_qp_export<M, KCH, SOFT, false, true>
                               : pack ? &usv_qp_export<M, KCH, SOFT, CANPACK, false> : &usv_qp_export<M, KCH, SOFT, false, false>;
     k.npt_hard = WsLayout<M, KCH, SOFT, false>::NPT; k.npt_soft = WsLayout<M, KCH, SOFT, true>::NPT;
@@ -1014,12 +1005,9 @@ int ensure_export(usvmpc_handle *h); // (below: needs the kernel dispatch)
 // the speculative lineariser of the second stream: wait for it and forget what it made (something it read or wrote is about to change)
 int spec_cancel(usvmpc_handle *h)
 {
-    h->spec_valid = false;
-    h->spec_quiet = 0;
-    if (h->spec_outstanding) {
+    if (h->sched.cancel()) {
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipStreamSynchronize(h->aux_stream));
-        h->spec_outstanding = false;
     }
     return 0;
 }
@@ -1265,13 +1253,13 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
             else { h->dirty_lo[fi] = std::min(h->dirty_lo[fi], lo); h->dirty_hi[fi] = std::max(h->dirty_hi[fi], hi); }
         }
         if (set && (fi == usvmpc_handle::F_X || fi == usvmpc_handle::F_U || fi == usvmpc_handle::F_YREF || fi == usvmpc_handle::F_YREF_E))
-            h->spec_quiet = 0;
+            h->sched.caller_wrote();
         return 0;
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if (set) { // (a lineariser that ran ahead may have read what is being replaced - it reads x, u, yref: the next solve linearises again)
         const std::string fs(field ? field : "");
-        if (fs == "x" || fs == "u" || fs == "yref" || fs == "yref_e") { h->spec_valid = false; h->spec_quiet = 0; }
+        if (fs == "x" || fs == "u" || fs == "yref" || fs == "yref_e") h->sched.caller_wrote();
     }
     if (!set) { rc = mirror_flush(h); if (rc) return rc; } // (a get of a field with pending writes sees them)
     if (stage < 0 || f.stages == 1) {
@@ -1443,10 +1431,61 @@ int launch_qp(usvmpc_handle *h, const Kernels &k, int phase)
     return 0;
 }
 
-// One solve's launches on the handle's stream: sort, lineariser (pipelined: see usvmpc_handle), the QP (launch_qp, or the partially
-// condensed QP: launch_cond), the count of unconverged QPs and the copy of the results into the host mirror.
+// counting sort of the previous solve's iteration counts into a group -> instance map
+int sort_into(usvmpc_handle *h, int *dst, int *inv)
+{
+    const int B = h->B;
+    const int *prev2 = h->sort_two ? h->d_iter_prev : h->ptrs.qp_iter; // (option "sort_two_ticks" = 0: the last count alone)
+    hipLaunchKernelGGL(usv_sort_hist, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_hist);
+    hipLaunchKernelGGL(usv_sort_scan, dim3(1), dim3(64), 0, h->stream, h->d_hist, h->d_cursor);
+    hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst, inv);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// The pipelined lineariser's stream (lowest priority: lin_plan.hpp says why), events and buffers, made together on first use
+int pipe_prepare(usvmpc_handle *h)
+{
+    const size_t B = (size_t)h->B;
+    int prio_least = 0, prio_greatest = 0;
+    HIP_TRY(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    HIP_TRY(h, hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, prio_least));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));
+    if (dev_alloc(h, &h->d_epoch, B, false) || dev_alloc(h, &h->d_redo, B * redo_words(h->N), true) ||
+        dev_alloc(h, &h->d_perm2, B, true) || dev_alloc(h, &h->d_inv, B, true))
+        return USVMPC_E_HIP;
+    HIP_TRY(h, hipMemsetAsync(h->d_epoch, 0xff, B * sizeof(int), h->stream)); // -1: nothing is final yet
+    return 0;
+}
+
+// Option "lin_force_modes" (usvmpc_handle::lin_force): the arguments of a forced pair of launches - epoch and redo words of their own, filled
+// here, and the inverse of the running map
+int force_prepare(usvmpc_handle *h, int epoch, DevPtrs &Pf)
+{
+    const int B = h->B;
+    const size_t nredo = (size_t)B * h->ptrs.redo_words;
+    if (!h->d_force_epoch && (dev_alloc(h, &h->d_force_epoch, (size_t)B, false) || dev_alloc(h, &h->d_force_redo, nredo, false) ||
+                              dev_alloc(h, &h->d_force_inv, (size_t)B, false)))
+        return USVMPC_E_HIP;
+    Pf = h->ptrs;
+    Pf.epoch = h->d_force_epoch;
+    Pf.redo = h->d_force_redo;
+    HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->d_force_epoch, epoch, (size_t)B, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_force_redo, 0, nredo * sizeof(int), h->stream));
+    if (Pf.perm) {
+        hipLaunchKernelGGL(usv_invert_map, dim3((B + 255) / 256), dim3(256), 0, h->stream, Pf.perm, B, h->d_force_inv);
+        Pf.inv_next = h->d_force_inv;
+    }
+    return 0;
+}
+
+// One solve's launches on the handle's stream: sort, lineariser, the QP (launch_qp, or the partially condensed QP: launch_cond), the count
+// of unconverged QPs and the copy of the results into the host mirror.  What the lineariser does, under which map and whether the next
+// tick's runs ahead is lin_plan.hpp's plan_lin over the handle's LinSched: this function fills LinIn and carries the plan out.
 int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
 {
+    static_assert(LIN_GROUP_LANES == LANES, "lin_plan.hpp sizes the lineariser's grids");
     {   // pending host writes go up first; the results come back below
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
@@ -1457,123 +1496,62 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         const int rct = tracks_predict(h);
         if (rct) return rct;
     }
-    // the lineariser's grids (usv_linearize): (group, stage) pairs - or work items -, groups for MODE 4; two pairs per row (option "lin_pairs"): rows
-    const long lin_groups = (long)(h->N + 1) * h->Bp;
     const bool pairs = h->lin_pairs != 0;
     if (pairs && k.lin_pair[0][0] == nullptr) { h->err = "lin_pairs: the model does not declare the columns to integrate"; return USVMPC_E_ARG; }
-    auto lin_count = [&](int mode) {
-        if (mode == 4) return (long)h->Bp;
-        if (!pairs) return lin_groups;
-        return mode == 3 ? lin_pair_retire_rows(h->N, (long)h->Bp) : lin_pair_plain_rows(h->N, (long)h->Bp);
-    };
-    auto lin_grid = [&](int mode) {
-        const long per_block = mode == 4 ? lin_block(mode) / 64 : lin_block(mode) / LANES;
-        return dim3((unsigned)((lin_count(mode) + per_block - 1) / per_block));
-    };
-    hipEvent_t *ev = h->ev[h->nsolves % usvmpc_handle::RING];
-    const int B = h->B;
-    // counting sort of the previous solve's iteration counts into a group -> instance map
-    auto sort_into = [&](int *dst, int *inv) {
-        const int *prev2 = h->sort_two ? h->d_iter_prev : h->ptrs.qp_iter; // (option "sort_two_ticks" = 0: the last count alone)
-        hipLaunchKernelGGL(usv_sort_hist, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_hist);
-        hipLaunchKernelGGL(usv_sort_scan, dim3(1), dim3(64), 0, h->stream, h->d_hist, h->d_cursor);
-        hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst, inv);
-    };
     const group_kernel_t *lin = (pairs ? k.lin_pair : k.lin)[h->spec.sim_steps > 1 ? 1 : 0]; // [MODE]
-    // Pipelined lineariser (see usvmpc_handle): RTI solves of large handles
     const bool cond = phase == 0 && h->cond_N2 > 0; // RTI solve on the partially condensed QP (cond_ipm.hpp)
-    const bool pipe = phase == 0 && h->pipeline && !h->mirror && !h->extern_access && h->dynamic_rows && h->B >= 16384 && !cond;
-    if (pipe && !h->aux_stream) {
-        // (lowest priority: when this stream's lineariser and the main stream's QP launch become eligible together, the QP
-        // launch's workgroups are placed first and the lineariser gets the compute units that launch vacates)
-        int prio_least = 0, prio_greatest = 0;
-        HIP_TRY(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        HIP_TRY(h, hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, prio_least));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));
-        if (dev_alloc(h, &h->d_epoch, (size_t)B, false) || dev_alloc(h, &h->d_redo, (size_t)B * ((h->N + 32) / 32), true) ||
-            dev_alloc(h, &h->d_perm2, (size_t)B, true) || dev_alloc(h, &h->d_inv, (size_t)B, true))
-            return USVMPC_E_HIP;
-        HIP_TRY(h, hipMemsetAsync(h->d_epoch, 0xff, (size_t)B * sizeof(int), h->stream)); // -1: nothing is final yet
+    const int B = h->B;
+    const int slot = (int)(h->nsolves % usvmpc_handle::RING); // this solve's place in the per-solve rings
+    hipEvent_t *ev = h->ev[slot];
+    auto map_buf = [h](LinMap m) { return m == MAP_A ? h->d_perm : m == MAP_B ? h->d_perm2 : nullptr; };
+    LinIn in = {};
+    in.phase = phase; in.nsolves = h->nsolves; in.B = B; in.Bp = h->Bp; in.N = h->N;
+    in.pipeline = h->pipeline; in.dynamic_rows = h->dynamic_rows; in.sort_enabled = h->sort_enabled; in.sort_two = h->sort_two;
+    in.lin_force = h->lin_force; in.pairs = pairs; in.cond = h->cond_N2 > 0;
+    in.mirror = h->mirror != nullptr; in.extern_access = h->extern_access;
+    in.cur_map = !h->ptrs.perm ? MAP_NONE : h->ptrs.perm == h->d_perm ? MAP_A : MAP_B;
+    const LinPlan p = plan_lin(in, h->sched);
+    if (p.pipe && !h->aux_stream) {
+        const int rcp = pipe_prepare(h);
+        if (rcp) return rcp;
     }
-    // whatever this solve does with the lineariser's planes comes after a speculative linearisation that may still be writing them
-    if (h->spec_outstanding) {
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_spec, 0));
-        h->spec_outstanding = false;
-    }
-    const bool had_spec = pipe && h->spec_for == h->nsolves;
-    const bool use_spec = had_spec && h->spec_valid;
-    if (had_spec) (use_spec ? h->spec_hits : h->spec_misses)++;
-    h->spec_valid = false;
-    if (use_spec) {
-        // the map this tick was linearised under (made one tick ago from the counts of the solve before)
-        h->ptrs.perm = h->spec_perm;
-        h->map_changed = true;
-    } else if (h->sort_enabled && h->nsolves > 0 && phase != 2) {
-        // (the later iterations of a full SQP read the multipliers the previous launch left in the group-indexed workspace: the
-        // group -> instance map must not change inside one SQP call; a phase-1 launch re-sorts BEFORE its QP writes the multipliers:
-        // map and workspace stay consistent)
-        if (phase == 0) h->map_changed = true;
-        sort_into(h->d_perm, nullptr);
-        HIP_TRY(h, hipGetLastError());
-        h->ptrs.perm = h->d_perm;
-    }
-    constexpr int SPEC_QUIET_MIN = 2;
-    if (pipe) h->spec_quiet++; // (reset by every caller write that would invalidate a linearisation made ahead of time)
-    const bool spec_next = pipe && h->spec_quiet >= SPEC_QUIET_MIN; // the next tick's lineariser runs ahead, beside this solve's QP launch
-    h->ptrs.epoch = spec_next ? h->d_epoch : nullptr;
-    h->ptrs.redo = pipe ? h->d_redo : nullptr;
-    h->ptrs.redo_words = (h->N + 32) / 32;
+    if (p.wait_ahead) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_spec, 0));
+    if (p.map_changed) h->map_changed = true;
+    if (p.map_from == LinPlan::SORT && sort_into(h, map_buf(p.map), nullptr)) return USVMPC_E_HIP;
+    if (p.map_from != LinPlan::KEEP) h->ptrs.perm = map_buf(p.map);
+    h->ptrs.epoch = p.spec_next ? h->d_epoch : nullptr;
+    h->ptrs.redo = p.redo ? h->d_redo : nullptr;
+    h->ptrs.redo_words = redo_words(h->N);
     h->ptrs.perm_cur = nullptr;
     h->ptrs.inv_next = nullptr;
     h->ptrs.tick = (int)h->nsolves;
-    h->ev3_set[h->nsolves % usvmpc_handle::RING] = false;
+    h->ev3_set[slot] = false;
     HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    // (MODE 2 / 4: only what the speculative pass had to skip)
-    const int lin_mode = use_spec ? (h->spec_fine ? 4 : 2) : 0;
-    if (h->lin_force != 0 && lin_mode == 0 && phase == 0) { // (usvmpc_handle::lin_force)
-        const size_t nredo = (size_t)B * h->ptrs.redo_words;
-        if (!h->d_force_epoch && (dev_alloc(h, &h->d_force_epoch, (size_t)B, false) || dev_alloc(h, &h->d_force_redo, nredo, false) ||
-                                  dev_alloc(h, &h->d_force_inv, (size_t)B, false)))
-            return USVMPC_E_HIP;
-        DevPtrs Pf = h->ptrs;
-        Pf.epoch = h->d_force_epoch;
-        Pf.redo = h->d_force_redo;
-        HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->d_force_epoch, h->lin_force == 1 ? Pf.tick : -1, (size_t)B, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_force_redo, 0, nredo * sizeof(int), h->stream));
-        if (Pf.perm) {
-            hipLaunchKernelGGL(usv_invert_map, dim3((B + 255) / 256), dim3(256), 0, h->stream, Pf.perm, B, h->d_force_inv);
-            Pf.inv_next = h->d_force_inv;
-        }
-        hipLaunchKernelGGL(lin[3], lin_grid(3), dim3(lin_block(3)), 0, h->stream, Pf, lin_count(3));
-        hipLaunchKernelGGL(lin[4], lin_grid(4), dim3(lin_block(4)), 0, h->stream, Pf, lin_count(4));
-        if (pairs) h->lin_pair_launches += 2;
-    } else {
-        hipLaunchKernelGGL(lin[lin_mode], lin_grid(lin_mode), dim3(lin_block(lin_mode)), 0, h->stream, h->ptrs, lin_count(lin_mode));
-        if (pairs) h->lin_pair_launches++;
+    const DevPtrs *Pl = &h->ptrs;
+    DevPtrs Pf;
+    if (p.forced) {
+        const int rcf = force_prepare(h, p.force_epoch, Pf);
+        if (rcf) return rcf;
+        Pl = &Pf;
     }
+    for (int i = 0; i < p.nlaunch; i++) {
+        const LinLaunch &l = p.launch[i];
+        hipLaunchKernelGGL(lin[l.mode], dim3((unsigned)l.blocks), dim3(l.block), 0, h->stream, *Pl, l.count);
+    }
+    h->lin_pair_launches += p.pair_launches;
     HIP_TRY(h, hipGetLastError());
-    if (pipe) HIP_TRY(h, hipMemsetAsync(h->d_redo, 0, (size_t)B * ((h->N + 32) / 32) * sizeof(int), h->stream));
+    if (p.clear_redo) HIP_TRY(h, hipMemsetAsync(h->d_redo, 0, (size_t)B * redo_words(h->N) * sizeof(int), h->stream));
     HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-    h->ptrs.fail_count = h->d_fail_ring + h->nsolves % usvmpc_handle::RING;
+    h->ptrs.fail_count = h->d_fail_ring + slot;
     HIP_TRY(h, hipMemsetAsync(h->ptrs.fail_count, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_unconv_ring + h->nsolves % usvmpc_handle::RING, 0, sizeof(int), h->stream));
-    if (h->d_susp_count) HIP_TRY(h, hipMemsetAsync(h->d_susp_count + h->nsolves % usvmpc_handle::RING, 0, sizeof(int), h->stream)); // (hand-over count of this launch)
-    const int *next_perm = nullptr;
-    if (spec_next) {
-        // the NEXT tick's map, from the counts this launch is about to overwrite, into the buffer this tick does not use
-        if (h->sort_enabled) {
-            int *dst = (h->ptrs.perm == h->d_perm) ? h->d_perm2 : h->d_perm;
-            // (d_inv: read by the speculative lineariser only, which every later sort of this stream comes behind - ev_spec above)
-            sort_into(dst, h->d_inv);
-            HIP_TRY(h, hipGetLastError());
-            next_perm = dst;
-        }
+    HIP_TRY(h, hipMemsetAsync(h->d_unconv_ring + slot, 0, sizeof(int), h->stream));
+    if (h->d_susp_count) HIP_TRY(h, hipMemsetAsync(h->d_susp_count + slot, 0, sizeof(int), h->stream)); // (hand-over count of this launch)
+    if (p.spec_next) {
+        // (d_inv: read by the speculative lineariser only, which every later sort of this stream comes behind - ev_spec above)
+        if (p.sort_next && sort_into(h, map_buf(p.next_map), h->d_inv)) return USVMPC_E_HIP;
         HIP_TRY(h, hipEventRecord(h->ev_pre, h->stream));
     }
-    // (the counts of the solve before this one: the second half of the next sort key - copied after every sort of THIS solve has read
-    // the pair (qp_iter, d_iter_prev), the pipelined map's included, and before the QP launch overwrites qp_iter)
-    if (h->sort_enabled && h->sort_two && phase == 0)
+    if (p.copy_iter_prev)
         HIP_TRY(h, hipMemcpyAsync(h->d_iter_prev, h->ptrs.qp_iter, (size_t)h->B * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
     if (h->spec.npt != (h->spec.any_bsoft ? k.npt_soft : k.npt_hard)) {
         h->err = "workspace layout mismatch between host and kernels";
@@ -1586,32 +1564,21 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
     HIP_TRY(h, hipEventRecord(ev[2], h->stream));
     if (phase == 0) { // (an RTI solve: one QP per instance)
         hipLaunchKernelGGL(usv_count_unconverged, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_status, B,
-                           h->d_unconv_ring + h->nsolves % usvmpc_handle::RING, h->d_unconv_total);
+                           h->d_unconv_ring + slot, h->d_unconv_total);
         HIP_TRY(h, hipGetLastError());
     }
-    if (spec_next) {
-        // the next tick's lineariser, behind this launch on the second stream, under the map made above.  (Its stream has the lowest
-        // priority: when both become eligible the QP launch's workgroups are placed first; groups it reaches before their instance is
-        // final are marked and redone by the fix-up pass - measured on the bench workload: 0.35 of 7.4 ms, ~5 % of the groups.)
+    if (p.spec_next) { // the next tick's lineariser, behind this launch on the second stream, under the map made above
         HIP_TRY(h, hipStreamWaitEvent(h->aux_stream, h->ev_pre, 0));
         DevPtrs Pn = h->ptrs;
-        Pn.perm = next_perm;
+        Pn.perm = map_buf(p.next_map);
         Pn.perm_cur = h->ptrs.perm;
-        Pn.inv_next = next_perm ? h->d_inv : nullptr;
-        // Which form: in the retire order, by one-wave workgroups (MODE 3, fix-up MODE 4), when this QP launch hands nothing over.  A launch
-        // that does (batches up to three times the resident rows) needs the slots its leaving waves free for its follow-up workgroups, a
-        // large share of its instances is still running when the lineariser arrives, and the fix-up has a large share to redo: measured
-        // at 16 384 instances the fine form cost 0.6 ms of QP launch and 0.35 ms of fix-up per 21 ms tick; at 65 536 it saves 1.4 of 71.5 ms.
-        h->spec_fine = h->ptrs.susp_count == nullptr;
-        const int spec_mode = h->spec_fine ? 3 : 1;
-        hipLaunchKernelGGL(lin[spec_mode], lin_grid(spec_mode), dim3(lin_block(spec_mode)), 0, h->aux_stream, Pn, lin_count(spec_mode));
+        Pn.inv_next = Pn.perm ? h->d_inv : nullptr;
+        // (launch_qp has just said whether this launch hands instances over: DevPtrs::susp_count)
+        const LinLaunch l = lin_launch(h->sched.launched_ahead(h->ptrs.susp_count != nullptr, p.next_map), pairs, h->N, h->Bp);
+        hipLaunchKernelGGL(lin[l.mode], dim3((unsigned)l.blocks), dim3(l.block), 0, h->aux_stream, Pn, l.count);
         if (pairs) h->lin_pair_launches++;
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->ev_spec, h->aux_stream));
-        h->spec_for = h->nsolves + 1;
-        h->spec_valid = true;
-        h->spec_outstanding = true;
-        h->spec_perm = next_perm;
     }
     h->nsolves++;
     h->layout_dirty = false;
@@ -1859,11 +1826,9 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     h->pipeline = true;
     h->aux_stream = nullptr; h->ev_pre = nullptr; h->ev_spec = nullptr;
     h->d_epoch = nullptr; h->d_redo = nullptr; h->d_perm2 = nullptr; h->d_inv = nullptr;
-    h->spec_fine = false;
     h->lin_pairs = model_has_pairs(h->desc.model) ? 1 : 0; h->lin_pair_launches = 0;
     h->lin_force = 0; h->d_force_epoch = nullptr; h->d_force_redo = nullptr; h->d_force_inv = nullptr;
-    h->spec_for = -1; h->spec_valid = false; h->spec_outstanding = false; h->spec_perm = nullptr;
-    h->spec_quiet = 0; h->spec_hits = 0; h->spec_misses = 0;
+    h->sched.reset();
     h->noise_mask = ~0u;
     h->instance_offset = 0;
     h->d_obs_pos = nullptr; h->d_obs_vel = nullptr; h->d_clear = nullptr; h->d_clear_min = nullptr;
@@ -2033,9 +1998,9 @@ int usvmpc_sync(usvmpc_handle *h)
     if (!h) return USVMPC_E_ARG;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->spec_outstanding) { // (the lineariser that runs a tick ahead is part of the work enqueued so far)
+    if (h->sched.outstanding) { // (the lineariser that runs a tick ahead is part of the work enqueued so far)
         HIP_TRY(h, hipStreamSynchronize(h->aux_stream));
-        h->spec_outstanding = false;
+        h->sched.synced();
     }
     h->inflight = false;
     return 0;
@@ -2310,8 +2275,8 @@ int usvmpc_handover_co_counts(usvmpc_handle *h, int n, int *finished, int *timeo
 int usvmpc_pipeline_stats(usvmpc_handle *h, long *used, long *discarded)
 {
     if (!h) return USVMPC_E_ARG;
-    if (used) *used = h->spec_hits;
-    if (discarded) *discarded = h->spec_misses;
+    if (used) *used = h->sched.hits;
+    if (discarded) *discarded = h->sched.misses;
     return 0;
 }
 
