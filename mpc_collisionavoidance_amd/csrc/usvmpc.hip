@@ -12,7 +12,8 @@
 // with another: __graft_entry__.build() therefore compiles THIS file several times in parallel, -DUSV_PART=0 for the C ABI, the handle
 // bookkeeping, the launches (launch_qp carries out the plan of qp_plan.hpp, where the launch policy lives as a host-only function of plain
 // numbers: tests/test_qp_plan.py; launch_solve likewise the plan of lin_plan.hpp - the lineariser's schedule, maps and grids:
-// tests/test_lin_plan.py) and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
+// tests/test_lin_plan.py; copy_field the field table and the host mirror's bookkeeping of field_plan.hpp: tests/test_field_plan.py)
+// and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
 // kernels_for<M, KCH, SOFT> (explicit instantiation in its part, extern template in part 0, which calls it) - and links the objects.
 // Without USV_PART everything is one translation unit (the generated-model libraries of genbuild.py).
 #ifndef USV_PART
@@ -33,6 +34,7 @@
 #include "qp_plan.hpp"
 #include "sim.hpp"
 #include "cond_launch.hpp"
+#include "field_plan.hpp"
 #ifdef USV_GEN_MODEL_HEADER // a model generated from a symbolic definition (codegen.py): struct ModelGen
 #include USV_GEN_MODEL_HEADER
 #endif
@@ -776,21 +778,14 @@ struct usvmpc_handle {
     int *d_unconv_ring;       // [RING] instances whose QP did not converge to the tolerances (qp_status != 0), one slot per solve
     unsigned long long *d_unconv_total; // [1] ... summed over every RTI solve of the handle (usvmpc_unconverged_total)
     // Caller-visible arrays live in ONE device arena, in the order [x | u | status | x0 | yref | yref_e | p | lh] (256-byte aligned
-    // pieces).  Small handles (the single-instance drop-in faces: AcadosOcpSolver, the acados C shim) also keep a pinned host
-    // MIRROR of it: usvmpc_set then writes the mirror and marks the field dirty - no HIP call, no synchronisation - and the next
-    // launch uploads what is dirty (the reference protocol's 3N+4 setters per tick become ONE asynchronous copy: the dirty
-    // fields are adjacent); after a solve [x | u | status] comes back in ONE copy and usvmpc_get "x" / "u" is served from it.
-    enum { F_X = 0, F_U, F_STATUS, F_X0, F_YREF, F_YREF_E, F_P, F_LH, F_COUNT };
+    // pieces: field_plan.hpp, arena_layout).  Small handles also keep a pinned host MIRROR of it.  Which names a caller may set and get, where
+    // the pieces lie, what the mirror holds newer than the device and whom it may answer is field_plan.hpp's: the field table and the state
+    // machine HostMirror (no field of it is assigned in this file - copy_field, mirror_flush, launch_solve and the few callers that wait,
+    // hand a pointer out or give the mirror up call its methods), host-only and checked on the CPU by tests/test_field_plan.py.  Here: the
+    // two base pointers its offsets apply to.
+    HostMirror hm;            // (hm.lay: the arena's layout)
     char *arena;              // device
-    char *mirror;             // pinned host copy of the arena, or nullptr (arena larger than MIRROR_MAX)
-    size_t arena_bytes, f_off[F_COUNT + 1], f_len[F_COUNT];
-    size_t dirty_lo[F_COUNT], dirty_hi[F_COUNT]; // byte range inside each field that the mirror holds newer than the device (lo >= hi: none)
-    // one stage of several instances set at a time (the reference protocol on a small multi-instance handle): the rows of that stage are not
-    // contiguous, so they are remembered per (field, stage) and go up at the next launch as 2-D copies of runs of consecutive stages
-    std::vector<char> dirty_stage[F_COUNT];
-    bool inflight;            // a copy between mirror and arena may still be running on the stream
-    bool out_valid;           // the mirror's [x | u | status] is what the device holds (or newer)
-    bool extern_access;       // a device pointer was handed out: the device arrays may change behind the mirror
+    char *mirror;             // pinned host copy of the arena, or nullptr (hm.on false: arena larger than MIRROR_MAX, or given up)
     // Pipelined lineariser (option "pipeline_linearize"): the lineariser of tick t + 1 runs on a second stream beside the QP launch of tick t.
     // When, under which map and whether what it made still stands is lin_plan.hpp's: the state machine LinSched (no field of it is assigned
     // in this file - spec_cancel, copy_field, usvmpc_sync and launch_solve call its methods) and the per-solve plan plan_lin, both host-only
@@ -963,41 +958,21 @@ void dev_free(usvmpc_handle *h, void *p, size_t nbytes)
     h->bytes -= nbytes;
 }
 
-struct Field {
-    double *base;   // device pointer
-    int n;          // per-stage length
-    int stages;     // number of stages in the array
-    int stage_off;  // caller stage that maps to slot 0
-};
-
-// caller-visible field table; `set` = writable by the caller
-int lookup(usvmpc_handle *h, const char *f, int stage, bool set, Field &o)
+// the device array behind a row of the field table (field_plan.hpp): the only place where names meet pointers
+void *field_ptr(usvmpc_handle *h, FieldId id)
 {
-    const std::string s(f ? f : "");
-    DevPtrs &P = h->ptrs;
-    const int N = h->N;
-    if (s == "x") o = {P.x, h->nx, N + 1, 0};
-    else if (s == "u") o = {P.u, h->nu, N, 0};
-    else if (s == "x0") o = {const_cast<double *>(P.x0), h->nx, 1, 0};
-    else if (s == "yref") {
-        if (stage == N) o = {const_cast<double *>(P.yref_e), h->ny_e, 1, N};
-        else o = {const_cast<double *>(P.yref), h->ny, N, 0};
-    } else if (s == "yref_e") o = {const_cast<double *>(P.yref_e), h->ny_e, 1, 0};
-    else if (s == "p") o = {const_cast<double *>(P.p), 2 * h->K, N + 1, 0};
-    else if (s == "lh") o = {const_cast<double *>(P.lh), h->K, N, 0};
-    else if (!set && s == "pi") o = {P.pi, h->nx, N, 1};
-    else if (!set && s == "sl") o = {P.sl, h->K, N, 0};
-    else if (!set && s == "su") o = {P.su, h->K, N, 0};
-    else if (!set && s == "res") o = {P.res, 4, 1, 0};
-    else if (!set && s == "obs_tmin") o = {P.obs_tmin, 1, 1, 0};
-    else if (!set && s == "nlp_res") o = {P.nlp_res, 4, 1, 0};
-    else if (!set && s == "lam" && P.lam_out) o = {P.lam_out, P.nlam, N + 1, 0};
-    else if (!set && s == "t" && P.t_out) o = {P.t_out, P.nlam, N + 1, 0};
-    else {
-        h->err = "unknown field '" + s + "'";
-        return USVMPC_E_FIELD;
-    }
-    return 0;
+    const DevPtrs &P = h->ptrs;
+    const void *const by_id[] = {P.x, P.u, P.status, P.x0, P.yref, P.yref_e, P.p, P.lh, // (in FieldId's order)
+                                 P.pi, P.sl, P.su, P.res, P.obs_tmin, P.nlp_res, P.lam_out, P.t_out, P.qp_iter, P.qp_status, P.sqp_iter,
+                                 h->d_obs_pos, h->d_obs_vel, h->d_clear, h->d_clear_min};
+    static_assert(sizeof by_id / sizeof *by_id == FLD_COUNT && FLD_PI == 8 && FLD_QP_ITER == 16 && FLD_OBS_POS == 19, "one pointer per row of the field table");
+    return const_cast<void *>(by_id[id]);
+}
+
+static_assert(FIELD_E_UNKNOWN == USVMPC_E_FIELD, "field_plan.hpp restates the code");
+FieldDims field_dims(const usvmpc_handle *h)
+{
+    return FieldDims{h->N, h->nx, h->nu, h->ny, h->ny_e, h->K, h->ptrs.nlam, h->ptrs.lam_out && h->ptrs.t_out};
 }
 
 int ensure_export(usvmpc_handle *h); // (below: needs the kernel dispatch)
@@ -1012,66 +987,36 @@ int spec_cancel(usvmpc_handle *h)
     return 0;
 }
 
-constexpr size_t MIRROR_MAX = 1u << 20; // arenas up to 1 MiB are mirrored on the host
-
-int field_index(const std::string &s, int stage, int N)
-{
-    if (s == "x") return usvmpc_handle::F_X;
-    if (s == "u") return usvmpc_handle::F_U;
-    if (s == "x0") return usvmpc_handle::F_X0;
-    if (s == "yref") return stage == N ? usvmpc_handle::F_YREF_E : usvmpc_handle::F_YREF;
-    if (s == "yref_e") return usvmpc_handle::F_YREF_E;
-    if (s == "p") return usvmpc_handle::F_P;
-    if (s == "lh") return usvmpc_handle::F_LH;
-    return -1;
-}
-
 // wait for a mirror <-> arena copy that may still be running before the host touches the mirror
 int mirror_quiesce(usvmpc_handle *h)
 {
-    if (h->inflight) {
+    if (h->hm.must_wait()) {
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->inflight = false;
+        h->hm.synced();
     }
     return 0;
 }
 
-// upload what the mirror holds newer than the device: consecutive dirty fields go as one copy
+// the executor of a copy descriptor (field_plan.hpp), on the handle's stream: c.rows pieces of c.width bytes between device memory (pieces
+// c.pitch apart) and host memory (host_pitch apart), up or down
+int exec_copy(usvmpc_handle *h, char *dev, char *host, size_t host_pitch, const CopyDesc &c, bool up)
+{
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    if (c.rows == 1) HIP_TRY(h, hipMemcpyAsync(up ? dev : host, up ? host : dev, c.width, kind, h->stream));
+    else HIP_TRY(h, hipMemcpy2DAsync(up ? dev : host, up ? c.pitch : host_pitch, up ? host : dev, up ? host_pitch : c.pitch, c.width, c.rows, kind, h->stream));
+    return 0;
+}
+// ... between the arena and its mirror: the same bytes of both
+int mirror_copy(usvmpc_handle *h, const CopyDesc &c, bool up) { return exec_copy(h, h->arena + c.off, h->mirror + c.off, c.pitch, c, up); }
+
+// upload what the mirror holds newer than the device (HostMirror::next_upload: runs of dirty stages, consecutive dirty fields as one copy)
 int mirror_flush(usvmpc_handle *h)
 {
-    if (!h->mirror) return 0;
-    for (int fi = 0; fi < usvmpc_handle::F_COUNT; fi++) { // stage-wise sets of a multi-instance handle: runs of consecutive dirty stages
-        std::vector<char> &ds = h->dirty_stage[fi];
-        if (ds.empty()) continue;
-        const size_t stages = ds.size(), pitch = h->f_len[fi] / (size_t)h->B, row = pitch / stages;
-        for (size_t a = 0; a < stages;) {
-            if (!ds[a]) { a++; continue; }
-            size_t b = a;
-            while (b + 1 < stages && ds[b + 1]) b++;
-            // (a whole-field range that is dirty as well is uploaded below and covers these rows: same bytes, the order does not matter)
-            HIP_TRY(h, hipMemcpy2DAsync(h->arena + h->f_off[fi] + a * row, pitch, h->mirror + h->f_off[fi] + a * row, pitch, (b - a + 1) * row, (size_t)h->B,
-                                        hipMemcpyHostToDevice, h->stream));
-            h->inflight = true;
-            for (size_t i = a; i <= b; i++) ds[i] = 0;
-            a = b + 1;
-        }
-        ds.clear();
-    }
-    int f = 0;
-    while (f < usvmpc_handle::F_COUNT) {
-        if (h->dirty_lo[f] >= h->dirty_hi[f]) { f++; continue; }
-        size_t lo = h->f_off[f] + h->dirty_lo[f], hi = h->f_off[f] + h->dirty_hi[f];
-        // extend over the following fields while this one is dirty to its end and the next from its start
-        int g = f;
-        while (g + 1 < usvmpc_handle::F_COUNT && h->dirty_hi[g] == h->f_len[g] && h->dirty_lo[g + 1] == 0 && h->dirty_hi[g + 1] > 0) {
-            g++;
-            hi = h->f_off[g] + h->dirty_hi[g];
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->arena + lo, h->mirror + lo, hi - lo, hipMemcpyHostToDevice, h->stream));
-        h->inflight = true;
-        for (int i = f; i <= g; i++) { h->dirty_lo[i] = 1; h->dirty_hi[i] = 0; }
-        f = g + 1;
+    CopyDesc c;
+    while (h->hm.next_upload(c)) {
+        const int rc = mirror_copy(h, c, true);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -1093,8 +1038,6 @@ int tracks_alloc(usvmpc_handle *h)
     h->d_obs_pos = pos; h->d_obs_vel = vel; h->d_clear = cl; h->d_clear_min = clm;
     return 0;
 }
-
-bool is_tracks_field(const std::string &s) { return s == "obs_pos" || s == "obs_vel" || s == "clearance" || s == "clearance_min"; }
 
 // usvmpc_set / usvmpc_get of "obs_pos" / "obs_vel" ([B][2K]) and usvmpc_get of "clearance" / "clearance_min" ([B]); the stage is ignored
 int tracks_field(usvmpc_handle *h, const std::string &s, double *host, size_t n, bool set)
@@ -1175,113 +1118,69 @@ int tracks_step(usvmpc_handle *h, double T)
     return 0;
 }
 
+// usvmpc_set / usvmpc_get: the name resolved through the field table, validated once, then either a memcpy into / out of the pinned mirror
+// (HostMirror says whether, and what that leaves to upload) or one copy to / from the device, synchronised
 int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, size_t n, bool set)
 {
     if (!h) return USVMPC_E_ARG;
-    if (is_tracks_field(std::string(field ? field : "")) && h->K == 0) return tracks_field(h, field, host, n, set); // (the field error, whatever the buffer)
+    const FieldRow *row = find_field(field);
+    const unsigned flags = row ? row->flags : 0;
+    if ((flags & FF_TRACK) && h->K == 0) return tracks_field(h, field, host, n, set); // (the field error, whatever the buffer)
     if (!host) { h->err = "null buffer"; return USVMPC_E_ARG; }
-    {
-        const std::string fs(field ? field : "");
-        if (is_tracks_field(fs)) return tracks_field(h, fs, host, n, set);
-        if (set && h->tracks_on && fs == "p") {
-            h->err = "field 'p' is derived from the obstacle tracks while option \"obstacle_tracks\" is 1: set \"obs_pos\" / \"obs_vel\", or switch the option off";
-            return USVMPC_E_ARG;
-        }
+    if (flags & FF_TRACK) return tracks_field(h, field, host, n, set);
+    if (set && h->tracks_on && row && row->id == FLD_P) {
+        h->err = "field 'p' is derived from the obstacle tracks while option \"obstacle_tracks\" is 1: set \"obs_pos\" / \"obs_vel\", or switch the option off";
+        return USVMPC_E_ARG;
     }
-    if (!set && (std::string(field ? field : "") == "lam" || std::string(field ? field : "") == "t")) {
+    if (!set && (flags & FF_EXPORT)) {
         const int rce = ensure_export(h);
         if (rce) return rce;
     }
     Field f;
-    if (std::string(field ? field : "") == "res" || std::string(field ? field : "") == "nlp_res" ||
-        std::string(field ? field : "") == "obs_tmin" ||
-        std::string(field ? field : "") == "x0" ||
-        std::string(field ? field : "") == "yref_e")
-        stage = stage < 0 ? -1 : 0;
-    int rc = lookup(h, field, stage, set, f);
-    if (rc) return rc;
-    if (set && (std::string(field) == "yref" || std::string(field) == "yref_e")) h->pf_stale = true; // (the path-following front end rewrites its rows)
+    if (resolve(row, stage, field_dims(h), set, f)) {
+        h->err = std::string("unknown field '") + (field ? field : "") + "'";
+        return USVMPC_E_FIELD;
+    }
+    if (set && (f.row->flags & FF_PF)) h->pf_stale = true; // (the path-following front end rewrites its rows)
     if ((int)n != f.n) {
         h->err = std::string("mismatching dimension for field '") + field + "': expected " + std::to_string(f.n) +
                  ", got " + std::to_string(n);
         return USVMPC_E_SIZE;
     }
     if (f.n == 0) return 0;
-    const size_t B = (size_t)h->B;
-    const int fi = h->mirror ? field_index(std::string(field ? field : ""), stage, h->N) : -1;
-    if (fi >= 0 && (set || ((fi == usvmpc_handle::F_X || fi == usvmpc_handle::F_U) && h->out_valid && !h->extern_access))) {
+    if (const int bad = stage_check(f)) {
+        h->err = bad == 1 ? std::string("stage ") + std::to_string(f.stage) + " out of range for field '" + field + "'" : std::string("stage out of range");
+        return USVMPC_E_STAGE;
+    }
+    // (a lineariser that ran ahead may have read what is being replaced - it reads x, u, yref: the next solve linearises again)
+    if (set && (f.row->flags & FF_LIN)) h->sched.caller_wrote();
+    const CopyDesc span = field_span(f, (size_t)h->B);
+    const int slot = f.row->slot;
+    if (set ? h->hm.set_served(slot) : h->hm.get_served(slot)) {
         // ---- through the pinned mirror: no HIP call unless a copy is still in flight
-        const bool whole = stage < 0 || f.stages == 1;
-        if (!whole && (stage - f.stage_off < 0 || stage - f.stage_off >= f.stages)) {
-            h->err = std::string("stage ") + std::to_string(stage) + " out of range for field '" + field + "'";
-            return USVMPC_E_STAGE;
-        }
-        if (whole && stage >= 0 && stage - f.stage_off != 0) { h->err = "stage out of range"; return USVMPC_E_STAGE; }
-        rc = mirror_quiesce(h);
+        const int rc = mirror_quiesce(h);
         if (rc) return rc;
-        char *m = h->mirror + h->f_off[fi];
-        const size_t row = (size_t)f.n * sizeof(double), pitch = (size_t)f.stages * row;
-        const size_t first = whole ? 0 : (size_t)(stage - f.stage_off) * row;
-        if (whole) {
-            if (set) std::memcpy(m, host, B * pitch); else std::memcpy(host, m, B * pitch);
-        } else {
-            for (size_t b = 0; b < B; b++) {
-                if (set) std::memcpy(m + b * pitch + first, (const char *)host + b * row, row);
-                else std::memcpy((char *)host + b * row, m + b * pitch + first, row);
-            }
+        char *m = h->mirror + h->hm.lay.off[slot] + span.off;
+        for (size_t b = 0; b < span.rows; b++) {
+            if (set) std::memcpy(m + b * span.pitch, (const char *)host + b * span.width, span.width);
+            else std::memcpy((char *)host + b * span.width, m + b * span.pitch, span.width);
         }
-        if (set && !whole && B > 1) {
-            // one stage of several instances: the rows are not contiguous, and a dirty RANGE over them would later upload the mirror's
-            // copy of everything in between - stale where a device-side writer (the guidance kernels, a caller holding a device pointer)
-            // has written behind the mirror.  The stage is remembered; its rows go up with the next launch (mirror_flush), as one 2-D copy
-            // per run of consecutive dirty stages - no HIP call here (the immediate copy made the NEXT set synchronise)
-            // A caller that holds device pointers (usvmpc_get_device_ptr: extern_access) orders its own kernels against this set by the
-            // stream: for it the rows go up NOW, as before (a deferred upload would land on top of what the caller's kernel
-            // wrote to the same stage after the set, and a caller kernel reading the field before the solve would see the old rows).
-            if (h->extern_access) {
-                HIP_TRY(h, hipSetDevice(h->device));
-                HIP_TRY(h, hipMemcpy2DAsync(h->arena + h->f_off[fi] + first, pitch, m + first, pitch, row, B, hipMemcpyHostToDevice, h->stream));
-                h->inflight = true;
-            } else {
-                std::vector<char> &ds = h->dirty_stage[fi];
-                if (ds.size() != (size_t)f.stages) ds.assign((size_t)f.stages, 0);
-                ds[(size_t)(stage - f.stage_off)] = 1;
-            }
-        } else if (set) {
-            const size_t lo = first, hi = whole ? B * pitch : first + row;
-            if (h->dirty_lo[fi] >= h->dirty_hi[fi]) { h->dirty_lo[fi] = lo; h->dirty_hi[fi] = hi; }
-            else { h->dirty_lo[fi] = std::min(h->dirty_lo[fi], lo); h->dirty_hi[fi] = std::max(h->dirty_hi[fi], hi); }
+        CopyDesc now;
+        if (set && h->hm.wrote(slot, span, now)) { // (a strided stage under a handed-out device pointer goes up at once)
+            HIP_TRY(h, hipSetDevice(h->device));
+            return mirror_copy(h, now, true);
         }
-        if (set && (fi == usvmpc_handle::F_X || fi == usvmpc_handle::F_U || fi == usvmpc_handle::F_YREF || fi == usvmpc_handle::F_YREF_E))
-            h->sched.caller_wrote();
         return 0;
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    if (set) { // (a lineariser that ran ahead may have read what is being replaced - it reads x, u, yref: the next solve linearises again)
-        const std::string fs(field ? field : "");
-        if (fs == "x" || fs == "u" || fs == "yref" || fs == "yref_e") h->sched.caller_wrote();
+    if (!set) { // (a get of a field with pending writes sees them)
+        const int rc = mirror_flush(h);
+        if (rc) return rc;
     }
-    if (!set) { rc = mirror_flush(h); if (rc) return rc; } // (a get of a field with pending writes sees them)
-    if (stage < 0 || f.stages == 1) {
-        if (stage >= 0 && f.stages == 1 && stage - f.stage_off != 0) {
-            h->err = "stage out of range"; return USVMPC_E_STAGE;
-        }
-        const size_t nbytes = B * f.stages * f.n * sizeof(double);
-        if (set) HIP_TRY(h, hipMemcpyAsync(f.base, host, nbytes, hipMemcpyHostToDevice, h->stream));
-        else HIP_TRY(h, hipMemcpyAsync(host, f.base, nbytes, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        const int slot = stage - f.stage_off;
-        if (slot < 0 || slot >= f.stages) {
-            h->err = std::string("stage ") + std::to_string(stage) + " out of range for field '" + field + "'";
-            return USVMPC_E_STAGE;
-        }
-        const size_t row = (size_t)f.n * sizeof(double), pitch = (size_t)f.stages * row;
-        double *d = f.base + (size_t)slot * f.n;
-        if (set) HIP_TRY(h, hipMemcpy2DAsync(d, pitch, host, row, row, B, hipMemcpyHostToDevice, h->stream));
-        else HIP_TRY(h, hipMemcpy2DAsync(host, row, d, pitch, row, B, hipMemcpyDeviceToHost, h->stream));
-    }
+    const int rc = exec_copy(h, (char *)field_ptr(h, f.row->id) + span.off, (char *)host, span.width, span, set);
+    if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->inflight = false;
+    h->hm.synced();
     return 0;
 }
 
@@ -1508,7 +1407,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
     in.phase = phase; in.nsolves = h->nsolves; in.B = B; in.Bp = h->Bp; in.N = h->N;
     in.pipeline = h->pipeline; in.dynamic_rows = h->dynamic_rows; in.sort_enabled = h->sort_enabled; in.sort_two = h->sort_two;
     in.lin_force = h->lin_force; in.pairs = pairs; in.cond = h->cond_N2 > 0;
-    in.mirror = h->mirror != nullptr; in.extern_access = h->extern_access;
+    in.mirror = h->hm.on; in.extern_access = h->hm.extern_access;
     in.cur_map = !h->ptrs.perm ? MAP_NONE : h->ptrs.perm == h->d_perm ? MAP_A : MAP_B;
     const LinPlan p = plan_lin(in, h->sched);
     if (p.pipe && !h->aux_stream) {
@@ -1583,11 +1482,8 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
     h->nsolves++;
     h->layout_dirty = false;
     h->last_cond = cond;
-    if (h->mirror) { // [x | u | status] of this solve, one copy
-        HIP_TRY(h, hipMemcpyAsync(h->mirror, h->arena, h->f_off[usvmpc_handle::F_X0], hipMemcpyDeviceToHost, h->stream));
-        h->inflight = true;
-        h->out_valid = true;
-    }
+    CopyDesc back;
+    if (h->hm.read_back(back)) return mirror_copy(h, back, false); // [x | u | status] of this solve, one copy
     return 0;
 }
 
@@ -1876,34 +1772,24 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     TRY_C(dev_alloc(h, &h->d_spec, 1, false));
     HIP_C(hipMemcpy(h->d_spec, &h->spec, sizeof(DevSpec), hipMemcpyHostToDevice));
     P.spec = h->d_spec;
-    {   // the caller-visible arrays: one arena [x | u | status | x0 | yref | yref_e | p | lh]
-        const size_t len[usvmpc_handle::F_COUNT] = {B * (N + 1) * h->nx * sizeof(double), B * N * h->nu * sizeof(double), B * sizeof(int),
-                                                    B * h->nx * sizeof(double), B * N * h->ny * sizeof(double), B * h->ny_e * sizeof(double),
-                                                    B * (N + 1) * 2 * K * sizeof(double), B * N * K * sizeof(double)};
-        size_t off = 0;
-        for (int f = 0; f < usvmpc_handle::F_COUNT; f++) {
-            h->f_off[f] = off; h->f_len[f] = len[f];
-            off += (len[f] + 255) / 256 * 256;
-            h->dirty_lo[f] = 1; h->dirty_hi[f] = 0;
-        }
-        h->f_off[usvmpc_handle::F_COUNT] = off;
-        h->arena_bytes = off;
-        TRY_C(dev_alloc(h, &h->arena, off, true));
+    {   // the caller-visible arrays: one arena [x | u | status | x0 | yref | yref_e | p | lh] (field_plan.hpp)
+        const ArenaLayout lay = arena_layout(field_dims(h), B);
+        TRY_C(dev_alloc(h, &h->arena, lay.bytes(), true));
         char *a = h->arena;
-        P.x = (double *)(a + h->f_off[usvmpc_handle::F_X]);
-        P.u = (double *)(a + h->f_off[usvmpc_handle::F_U]);
-        P.status = (int *)(a + h->f_off[usvmpc_handle::F_STATUS]);
-        P.x0 = (double *)(a + h->f_off[usvmpc_handle::F_X0]);
-        P.yref = (double *)(a + h->f_off[usvmpc_handle::F_YREF]);
-        P.yref_e = (double *)(a + h->f_off[usvmpc_handle::F_YREF_E]);
-        P.p = (double *)(a + h->f_off[usvmpc_handle::F_P]);
-        P.lh = (double *)(a + h->f_off[usvmpc_handle::F_LH]);
+        P.x = (double *)(a + lay.off[FLD_X]);
+        P.u = (double *)(a + lay.off[FLD_U]);
+        P.status = (int *)(a + lay.off[FLD_STATUS]);
+        P.x0 = (double *)(a + lay.off[FLD_X0]);
+        P.yref = (double *)(a + lay.off[FLD_YREF]);
+        P.yref_e = (double *)(a + lay.off[FLD_YREF_E]);
+        P.p = (double *)(a + lay.off[FLD_P]);
+        P.lh = (double *)(a + lay.off[FLD_LH]);
         h->mirror = nullptr;
-        if (off <= MIRROR_MAX) {
-            HIP_C(hipHostMalloc((void **)&h->mirror, off, hipHostMallocDefault));
-            std::memset(h->mirror, 0, off);
+        if (lay.bytes() <= MIRROR_MAX) {
+            HIP_C(hipHostMalloc((void **)&h->mirror, lay.bytes(), hipHostMallocDefault));
+            std::memset(h->mirror, 0, lay.bytes());
         }
-        h->inflight = false; h->out_valid = false; h->extern_access = false;
+        h->hm.reset(lay, h->mirror != nullptr);
     }
     TRY_C(dev_alloc(h, &P.sl, B * N * K, true));
     TRY_C(dev_alloc(h, &P.su, B * N * K, true));
@@ -1976,12 +1862,10 @@ int usvmpc_get(usvmpc_handle *h, const char *field, int stage, double *out, size
 int usvmpc_get_int(usvmpc_handle *h, const char *field, int *out)
 {
     if (!h || !out) return USVMPC_E_ARG;
-    const std::string s(field ? field : "");
-    const int *src = s == "status" ? h->ptrs.status : s == "qp_iter" ? h->ptrs.qp_iter : s == "qp_status" ? h->ptrs.qp_status
-                     : s == "sqp_iter" ? h->ptrs.sqp_iter : nullptr;
-    if (!src) { h->err = "unknown integer field '" + s + "'"; return USVMPC_E_FIELD; }
+    const FieldRow *row = find_field(field);
+    if (!row || !(row->rights & R_GET_INT)) { h->err = std::string("unknown integer field '") + (field ? field : "") + "'"; return USVMPC_E_FIELD; }
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpyAsync(out, src, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, field_ptr(h, row->id), (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -2002,7 +1886,7 @@ int usvmpc_sync(usvmpc_handle *h)
         HIP_TRY(h, hipStreamSynchronize(h->aux_stream));
         h->sched.synced();
     }
-    h->inflight = false;
+    h->hm.synced();
     return 0;
 }
 
@@ -2014,7 +1898,7 @@ int usvmpc_solve(usvmpc_handle *h, int *status)
     if (rc) return rc;
     int worst = 0;
     if (status) {
-        if (h->mirror && h->out_valid) std::memcpy(status, h->mirror + h->f_off[usvmpc_handle::F_STATUS], (size_t)h->B * sizeof(int)); // (came back with x | u)
+        if (h->hm.get_served(FLD_STATUS)) std::memcpy(status, h->mirror + h->hm.lay.off[FLD_STATUS], (size_t)h->B * sizeof(int)); // (came back with x | u)
         else {
             rc = usvmpc_get_int(h, "status", status);
             if (rc) return rc;
@@ -2067,38 +1951,29 @@ int usvmpc_solve_sqp(usvmpc_handle *h, int *status)
 int usvmpc_get_device_ptr(usvmpc_handle *h, const char *field, void **dptr)
 {
     if (!h || !dptr) return USVMPC_E_ARG;
-    const std::string s(field ? field : "");
-    if (s == "obs_pos" || s == "obs_vel") {
+    const FieldRow *row = find_field(field);
+    if (!row || !(row->rights & R_DEV)) { h->err = std::string("unknown field '") + (field ? field : "") + "'"; return USVMPC_E_FIELD; }
+    if (row->flags & FF_TRACK) {
         // a track field: the caller's own kernels may move the obstacles behind the handle's back, so the prediction runs before every solve
         // from now on.  Nothing a lineariser reads is exposed: the pipeline keeps running.
         const int rca = tracks_alloc(h);
         if (rca) return rca;
         h->tracks_extern = true;
-        if (s == "obs_pos") h->tracks_pos_set = true;
-        *dptr = s == "obs_pos" ? h->d_obs_pos : h->d_obs_vel;
+        if (row->id == FLD_OBS_POS) h->tracks_pos_set = true;
+        *dptr = field_ptr(h, row->id);
         return 0;
     }
-    const DevPtrs &P = h->ptrs;
-    const void *p = s == "x" ? (const void *)P.x : s == "u" ? (const void *)P.u : s == "x0" ? (const void *)P.x0
-                  : s == "yref" ? (const void *)P.yref : s == "yref_e" ? (const void *)P.yref_e
-                  : s == "p" ? (const void *)P.p : s == "lh" ? (const void *)P.lh : s == "pi" ? (const void *)P.pi
-                  : s == "sl" ? (const void *)P.sl : s == "su" ? (const void *)P.su
-                  : s == "status" ? (const void *)P.status : s == "qp_iter" ? (const void *)P.qp_iter
-                  : s == "qp_status" ? (const void *)P.qp_status : s == "res" ? (const void *)P.res
-                  : s == "obs_tmin" ? (const void *)P.obs_tmin
-                  : s == "nlp_res" ? (const void *)P.nlp_res : s == "sqp_iter" ? (const void *)P.sqp_iter : nullptr;
-    if (!p) { h->err = "unknown field '" + s + "'"; return USVMPC_E_FIELD; }
-    if (s == "yref" || s == "yref_e") h->pf_stale = true; // (the caller may write the rows behind the path-following front end's back)
+    if (row->flags & FF_PF) h->pf_stale = true; // (the caller may write the rows behind the path-following front end's back)
     {   // the caller is about to read (or write) device memory directly: pending host writes go up, and the host mirror no longer
         // vouches for the device's x / u
         HIP_TRY(h, hipSetDevice(h->device));
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
-        h->extern_access = true;
+        h->hm.handed_out();
         const int rcs = spec_cancel(h); // (and no lineariser runs ahead on arrays the caller may write behind the library's back)
         if (rcs) return rcs;
     }
-    *dptr = const_cast<void *>(p);
+    *dptr = field_ptr(h, row->id);
     return 0;
 }
 
@@ -2520,7 +2395,7 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->inflight = false; h->out_valid = false;
+        h->hm.dropped();
         (void)hipHostFree(h->mirror);
         h->mirror = nullptr;
         return 0;
@@ -2942,7 +2817,7 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream)
         if (rcf) return rcf;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->inflight = false;
+    h->hm.synced();
     {
         const int rcs = spec_cancel(h);
         if (rcs) return rcs;

@@ -238,6 +238,38 @@ def test_host_mirror_staging_is_invisible(oracle):
         assert np.array_equal(p, q), i
 
 
+@pytest.mark.parametrize("name,K,B", [("usv_model_guidance_ca1", 2, 1), ("usv_model", 0, 1), ("usv_model_guidance_ca1", 2, 2)])
+def test_host_mirror_sparse_stage_sets_are_invisible(name, K, B):
+    """The staging at the smallest shapes the script above does not reach: one instance (a set dirties a byte RANGE of its field; with
+    usv_model p and lh are empty, so the merged upload ends with yref_e and a set of lh is a set of nothing) and two (the smallest strided
+    case: stages are marked).  Between solves only the sparse stages 1 and 3 of lh / yref are set; mirror on against mirror off, bit for bit."""
+    N = 4
+    ocp, wl = util.make(name, N, K, B, seed=17)
+    lh = wl["lh"] if K else np.zeros((B, N, 0))
+
+    def script(mirror):
+        s = BatchOcpSolver(ocp, B)
+        if not mirror:
+            s.set_option("host_mirror", 0)
+        scenario.load_into(s, wl)
+        out = [s.solve().copy(), s.get_all("x"), s.get_all("u")]
+        for tick in range(3):
+            for k in (3, 1):
+                s.set("lh", k, lh[:, k] * (0.9 - 0.1 * tick))
+                s.set("yref", k, wl["yref"][:, k] + 0.001 * (tick + 1))
+            if tick == 1:
+                s.set("x0", 0, s.get("x", 1))           # the host-side hand-over: x0 joins the upload
+            out.append(s.solve().copy())
+            out += [s.get("x", 1), s.get("u", 0), s.get_all("x"), s.get_all("yref"), s.get_all("lh")]
+        s.close()
+        return out
+
+    a, b = script(True), script(False)
+    assert len(a) == len(b)
+    for i, (p, q) in enumerate(zip(a, b)):
+        assert np.array_equal(p, q), i
+
+
 def test_batch_beyond_the_buffer_window_is_refused():
     """One stage of the workspace is addressed through a 32-bit buffer window: a batch whose stage exceeds 4 GiB is refused at
     creation (it used to wrap silently)."""
