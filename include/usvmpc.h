@@ -315,7 +315,16 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream);
  *       from the key (instance_offset + b) * nx + j, so a batch split over several handles (shards: set each handle's offset to the
  *       index of its first instance) draws the same noise as one handle over the whole batch.  0 leaves the draws as they were;
  *   "obstacle_tracks" (default 0), "obstacle_step_on_advance" (default 1) - p derived from the obstacle tracks, the world stepped by the
- *       hand-over: "Obstacle tracks" above. */
+ *       hand-over: "Obstacle tracks" above;
+ *   "pf_predict" (default 1), "pf_lh_margin" (default 0.2; finite, >= 0) - the path-following front end's moving world predicted per stage
+ *       or held still inside the horizon, and the margin it adds to every keep-out radius: "Path-following front end" below;
+ *   "keep_multipliers" (an action, no state) - a value != 0 creates the buffers behind usvmpc_get "lam" / "t" now instead of at the first
+ *       get (a partially condensed solve fills them only if they exist before it);
+ *   "max_waves" (default 0) - 0: as many persistent wavefronts of the QP kernel as the device holds; n > 0 caps them, and the teams of a
+ *       partially condensed solve (a measurement aid; a negative value behaves as 0).
+ * A refused value (USVMPC_E_ARG, usvmpc_last_error names the option) or an unknown name (USVMPC_E_FIELD) changes nothing.  Options kept
+ * as integers ("max_waves", "disturbance_mask", "qp_cond_N", "hpipm_mode", "instance_offset", "handover_iter", "handover_co_spin",
+ * "handover_co_wgs") refuse a NaN and a value their type does not hold. */
 int usvmpc_set_option(usvmpc_handle *h, const char *name, double value);
 /* ---- Guidance front end (model usv_model_guidance_ca1 only): the arithmetic either side of the solver
  * call in the reference's ROS node, batched on the device (class NMPC in

@@ -12,7 +12,8 @@
 // with another: __graft_entry__.build() therefore compiles THIS file several times in parallel, -DUSV_PART=0 for the C ABI, the handle
 // bookkeeping, the launches (launch_qp carries out the plan of qp_plan.hpp, where the launch policy lives as a host-only function of plain
 // numbers: tests/test_qp_plan.py; launch_solve likewise the plan of lin_plan.hpp - the lineariser's schedule, maps and grids:
-// tests/test_lin_plan.py; copy_field the field table and the host mirror's bookkeeping of field_plan.hpp: tests/test_field_plan.py)
+// tests/test_lin_plan.py; copy_field the field table and the host mirror's bookkeeping of field_plan.hpp: tests/test_field_plan.py;
+// usvmpc_set_option the option table of option_plan.hpp: tests/test_option_plan.py)
 // and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
 // kernels_for<M, KCH, SOFT> (explicit instantiation in its part, extern template in part 0, which calls it) - and links the objects.
 // Without USV_PART everything is one translation unit (the generated-model libraries of genbuild.py).
@@ -29,6 +30,7 @@
 #include "linearize.hpp"
 #include "models.hpp"
 #include "obstacle_tracks.hpp"
+#include "option_plan.hpp"
 #include "pf_guidance.hpp"
 #include "qp_ipm.hpp"
 #include "qp_plan.hpp"
@@ -718,7 +720,8 @@ struct usvmpc_handle {
     bool soft;
     int device;
     hipStream_t stream;
-    bool own_stream;
+    bool own_stream = true;
+    Options opt;              // the run-time options (option_plan.hpp: the table of their names, checks and effects; usvmpc_set_option)
     static constexpr int RING = 64;      // per-solve event triples, newest at (nsolves-1) % RING
     hipEvent_t ev[RING][4];   // start | lineariser done | QP phase done | main QP launch done (the follow-up launch of a hand-over comes after it)
     long nsolves;
@@ -733,11 +736,10 @@ struct usvmpc_handle {
     // Path-following front end (usvmpc_pf_*, model usv_model_pf_ca): device buffers on first use; pf_ready after usvmpc_pf_reset
     PfPtrs pf;
     bool pf_alloc, pf_ready;
-    bool pf_stale;            // the caller may have written yref / yref_e since the front end last did: the next prepare rewrites every active instance
+    bool pf_stale = true;     // the caller may have written yref / yref_e since the front end last did: the next prepare rewrites every active instance
     int pf_tick;              // prepares since the last reset
     int pf_npts_cap;
     size_t pf_world_cap;      // doubles
-    double pf_margin;         // option "pf_lh_margin"
     double *pf_vel, *pf_pose; // [B][3] staging of the host-fed mode
     // A moving world (usvmpc_pf_world_vel): velocities per world entry; prepare then writes every stage of p / lh ("static_obstacles" off)
     // unless option "pf_predict" is 0, and usvmpc_advance / _advance_sim move the world (option "obstacle_step_on_advance")
@@ -745,35 +747,19 @@ struct usvmpc_handle {
     size_t pf_wvel_cap;       // doubles
     bool pf_world_set;        // usvmpc_pf_world has been called
     bool pf_moving;           // velocities are set for the current list
-    bool pf_predict;          // option "pf_predict"
-    bool sort_enabled;
-    bool sort_two;            // sort key: the larger of the last two iteration counts instead of the last one (option, default off)
-    bool merge_rows;
-    bool dynamic_rows;        // QP kernel as a persistent launch whose rows pull instances from a queue (option "dynamic_rows")
-    int lds_mode;             // workspace of the QP kernel in LDS: -1 when the batch is small enough (default), 0 never, 1 whenever it fits
-    int wide_mode;            // the latency mapping (one instance per wave, QpIpm WIDE): -1 for small batches (default), 0 never, 1 whenever it applies
-    int wide_waves;           // waves per instance of the latency mapping: -1 (default) four for soft-row OCPs and two obstacle chunks while the batch is at most one instance per CU, else one; 1; 4
     int last_wide;            // the last RTI launch ran on the wide kernel
-    int handover_iter;        // option "handover_iter": IPM iterations after which a row of a drained launch hands its instance to the follow-up launch (0: never)
+    // hand-over of long runners to a follow-up launch (option "handover_iter")
     int *d_susp_count, *d_susp_list; // [RING] instances each of the last launches handed over / [B] their groups
     double *d_susp_rec;       // [B][4] (DevPtrs::susp_rec)
-    // the follow-up kernel beside the draining launch (usv_qp_resume_co; option "handover_co": -1 = when the follow-up works in LDS, 0 never, 1 the same)
-    int handover_co;
-    int co_spin_limit;        // polls of ~1 us a co-resident workgroup waits for its entry before it gives up (option "handover_co_spin")
-    long co_wgs;              // workgroups of the co-resident launch (option "handover_co_wgs"; 0: one per CU - qp_plan.hpp says why)
+    // the follow-up kernel beside the draining launch (usv_qp_resume_co; option "handover_co")
     bool co_ready;            // co_stream, ev_co_pre / ev_co_end and d_co_ctl exist (made together on first use: co_prepare)
     hipStream_t co_stream;
     hipEvent_t ev_co_pre, ev_co_end;
     int *d_co_ctl;            // [RING][8] DevPtrs::co_ctl of the last launches
     bool ev3_set[RING];       // ev[.][3] was recorded for that solve
-    bool handover_lds;        // option "handover_lds": the follow-up launch copies the planes into LDS when the horizon fits
-    long max_waves;           // cap on the persistent waves of the QP kernel (0: as many as the device holds)
     int ncu;                  // compute units of the device
     QpCaps caps;              // what the occupancy queries said about the QP kernels (qp_plan.hpp)
-    bool aux_lds;             // option "aux_in_lds": the aux plane of an RTI solve in the waves' LDS when the horizon fits (default on)
     bool map_changed;         // the group -> instance map differs from the one the workspace's multipliers were written under
-    unsigned noise_mask;      // states usvmpc_advance disturbs (option "disturbance_mask"; default: all)
-    long long instance_offset; // global index of the handle's first instance (option "instance_offset"): keys the disturbance
     int *d_fail_ring;         // [RING] instances with status != 0, one slot per solve
     int *d_unconv_ring;       // [RING] instances whose QP did not converge to the tolerances (qp_status != 0), one slot per solve
     unsigned long long *d_unconv_total; // [1] ... summed over every RTI solve of the handle (usvmpc_unconverged_total)
@@ -789,23 +775,14 @@ struct usvmpc_handle {
     // Pipelined lineariser (option "pipeline_linearize"): the lineariser of tick t + 1 runs on a second stream beside the QP launch of tick t.
     // When, under which map and whether what it made still stands is lin_plan.hpp's: the state machine LinSched (no field of it is assigned
     // in this file - spec_cancel, copy_field, usvmpc_sync and launch_solve call its methods) and the per-solve plan plan_lin, both host-only
-    // and checked on the CPU by tests/test_lin_plan.py.  Here: the option, the HIP objects and the two map buffers the plan names.
-    bool pipeline;            // option; used for RTI solves of handles without a host mirror
+    // and checked on the CPU by tests/test_lin_plan.py.  Here: the HIP objects and the two map buffers the plan names.
     hipStream_t aux_stream;   // nullptr until first used
     hipEvent_t ev_pre, ev_spec;
     int *d_epoch, *d_redo, *d_perm2, *d_inv; // (d_perm / d_perm2: LinMap MAP_A / MAP_B)
     LinSched sched;
-    // Option "lin_force_modes" (tests): a solve that would run the whole-batch lineariser runs the pipeline's kernels MODE 3 + MODE 4 in its
-    // place, on the main stream - 1: the speculative form with every instance final, then the fix-up (which finds nothing); 2: with no instance final (it
-    // marks everything), then the fix-up (which does everything).  Work order as in the pipeline, with the identity as the "running" map.
-    int lin_force;
-    // Option "lin_pairs": the lineariser's kernels that serve two (group, stage) pairs per 16-lane row (usv_linearize PAIR; same bits) - the default
-    // for a model that declares the columns to integrate (PairCols, params.hpp); 0: one pair per row
-    int lin_pairs;
-    long lin_pair_launches;   // launches of the paired kernels so far (usvmpc_lin_pair_launches)
-    int *d_force_epoch, *d_force_redo, *d_force_inv;
-    // partial condensing (option "qp_cond_N"): RTI solves condense the QP to cond_N2 stages first (0: off - the Riccati sweep over the N stages)
-    int cond_N2;
+    long lin_pair_launches;   // launches of the paired kernels (option "lin_pairs") so far (usvmpc_lin_pair_launches)
+    int *d_force_epoch, *d_force_redo, *d_force_inv; // option "lin_force_modes": epoch and redo words of a forced pair of launches, the running map's inverse
+    // partial condensing (option "qp_cond_N")
     CondDims cond_dims;       // sizes of the condensed QP (valid when d_cond_dims is set)
     CondDims *d_cond_dims;
     double *d_cond_scratch;   // [cond_teams][cond_dims.total]
@@ -816,13 +793,11 @@ struct usvmpc_handle {
     // the world clock nor the stages it writes changed since it last ran.  Buffers exist from the first set of a track field.
     double *d_obs_pos, *d_obs_vel;   // [B][2K] each
     double *d_clear, *d_clear_min;   // [B] clearance after the last world step / its minimum since the caller last set "obs_pos"
-    bool tracks_on;           // the option
     bool tracks_pos_set;      // "obs_pos" has been set (or its device pointer handed out)
     bool tracks_dirty;        // p on the device is not what the tracks predict
     bool tracks_extern;       // a device pointer to a track field was handed out: the prediction runs before every solve
-    bool step_on_advance;     // option "obstacle_step_on_advance": usvmpc_advance / _advance_sim move the world too
     bool clear_reset;         // the next world step starts the running minimum afresh (until then "clearance_min" reads 1e300)
-    long export_at;           // nsolves the multiplier read-back buffers (ptrs.lam_out / t_out) were filled at; -1: never
+    long export_at = -1;      // nsolves the multiplier read-back buffers (ptrs.lam_out / t_out) were filled at; -1: never
     bool last_cond;           // the last launch solved the partially condensed QP (its rows live in per-team scratch, not in the workspace)
     bool layout_dirty;        // the row layout option changed after the last solve: the workspace cannot be read back
     size_t bytes;
@@ -854,7 +829,7 @@ Kernels kernels_for(const usvmpc_handle *h)
     k.kch = KCH; k.soft = SOFT;
     auto qp = [&k](qp_kernel_t q, qp_kernel_t q_lds = nullptr, qp_kernel_t q_aux = nullptr) { k.qp[SLOT_QP] = q; k.qp[SLOT_QP_LDS] = q_lds; k.qp[SLOT_QP_AUX] = q_aux; };
     // (one row pass when every box row rides in a slot lane: qp_ipm.hpp, MERGE)
-    const bool merge = pack && h->merge_rows && !S.box_dense;
+    const bool merge = pack && h->opt.merge_rows && !S.box_dense;
 #ifdef USV_BENCH_ONLY // development builds (tools/dev_build.sh): only the instantiation the bench workload runs (k.qp[SLOT_QP] null for any other layout)
     if (!(S.hdiag && pack && !S.any_bsoft)) return k;
     if (merge) {
@@ -1128,7 +1103,7 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
     if ((flags & FF_TRACK) && h->K == 0) return tracks_field(h, field, host, n, set); // (the field error, whatever the buffer)
     if (!host) { h->err = "null buffer"; return USVMPC_E_ARG; }
     if (flags & FF_TRACK) return tracks_field(h, field, host, n, set);
-    if (set && h->tracks_on && row && row->id == FLD_P) {
+    if (set && h->opt.tracks_on && row && row->id == FLD_P) {
         h->err = "field 'p' is derived from the obstacle tracks while option \"obstacle_tracks\" is 1: set \"obs_pos\" / \"obs_vel\", or switch the option off";
         return USVMPC_E_ARG;
     }
@@ -1191,11 +1166,11 @@ int launch_cond(usvmpc_handle *h)
         CondDims D;
         size_t lds = 0;
         int nb = 0;
-        const int rcp = cond_prepare(h->desc.model, h->kch, h->spec, h->cond_N2, D, lds, nb, h->err);
+        const int rcp = cond_prepare(h->desc.model, h->kch, h->spec, h->opt.cond_N2, D, lds, nb, h->err);
         if (rcp) return rcp;
         if (nb < 1 || h->ncu < 1) { h->err = "partial condensing: the kernel cannot be launched with this much LDS"; return USVMPC_E_HIP; }
         long teams = std::min<long>(h->B, (long)nb * h->ncu);
-        if (h->max_waves > 0) teams = std::min<long>(teams, h->max_waves);
+        if (h->opt.max_waves > 0) teams = std::min<long>(teams, h->opt.max_waves);
         if (dev_alloc(h, &h->d_cond_dims, 1, false)) return USVMPC_E_HIP;
         if (dev_alloc(h, &h->d_cond_scratch, (size_t)teams * (size_t)D.total, true)) return USVMPC_E_HIP;
         HIP_TRY(h, hipMemcpyAsync(h->d_cond_dims, &D, sizeof(CondDims), hipMemcpyHostToDevice, h->stream));
@@ -1256,7 +1231,7 @@ bool co_prepare(usvmpc_handle *h)
                     hipEventCreateWithFlags(&h->ev_co_end, hipEventDisableTiming) == hipSuccess &&
                     dev_alloc(h, &h->d_co_ctl, (size_t)usvmpc_handle::RING * 8, true) == 0;
     if (ok) h->co_ready = true;
-    else { co_release(h); h->handover_co = 0; (void)hipGetLastError(); } // (handled here: the launch's own error check must not report it)
+    else { co_release(h); h->opt.handover_co = 0; (void)hipGetLastError(); } // (handled here: the launch's own error check must not report it)
     return ok;
 }
 
@@ -1269,9 +1244,9 @@ int launch_qp(usvmpc_handle *h, const Kernels &k, int phase)
     QpIn in = {};
     in.B = h->B; in.Bp = h->Bp; in.N = h->N; in.K = h->K;
     in.npt = h->spec.npt; in.nu = h->nu; in.aux_dense4 = h->spec.aux_dense4; in.kch = h->kch; in.phase = phase; in.ncu = h->ncu;
-    in.wide_mode = h->wide_mode; in.wide_waves = h->wide_waves; in.lds_mode = h->lds_mode; in.dynamic_rows = h->dynamic_rows;
-    in.max_waves = h->max_waves; in.aux_lds = h->aux_lds; in.handover_iter = h->handover_iter; in.handover_lds = h->handover_lds;
-    in.handover_co = h->handover_co; in.co_wgs = h->co_wgs; in.own_stream = h->own_stream;
+    in.wide_mode = h->opt.wide_mode; in.wide_waves = h->opt.wide_waves; in.lds_mode = h->opt.lds_mode; in.dynamic_rows = h->opt.dynamic_rows;
+    in.max_waves = h->opt.max_waves; in.aux_lds = h->opt.aux_lds; in.handover_iter = h->opt.handover_iter; in.handover_lds = h->opt.handover_lds;
+    in.handover_co = h->opt.handover_co; in.co_wgs = h->opt.co_wgs; in.own_stream = h->own_stream;
     for (int s = 0; s < SLOT_QP_KERNELS; s++) in.has[s] = k.qp[s] != nullptr;
     in.has[SLOT_RESUME] = k.resume != nullptr; in.has[SLOT_RESUME_LDS] = k.resume_lds != nullptr; in.has_resume_co = k.resume_co != nullptr;
     in.nplw = k.nplw; in.ex_lds = k.ex_lds; in.ex_hbm = k.ex_hbm; in.k_kch = k.kch; in.k_soft = k.soft;
@@ -1318,7 +1293,7 @@ int launch_qp(usvmpc_handle *h, const Kernels &k, int phase)
     if (co) {
         hipLaunchKernelGGL(usv_co_done, dim3(1), dim3(1), 0, h->stream, h->ptrs.co_ctl);
         HIP_TRY(h, hipStreamWaitEvent(h->co_stream, h->ev_co_pre, 0));
-        hipLaunchKernelGGL(k.resume_co, dim3((unsigned)p.co_wgs), dim3(QP_BLOCK), p.hand_bytes, h->co_stream, h->ptrs, (int)p.grid, (int)h->B, h->co_spin_limit);
+        hipLaunchKernelGGL(k.resume_co, dim3((unsigned)p.co_wgs), dim3(QP_BLOCK), p.hand_bytes, h->co_stream, h->ptrs, (int)p.grid, (int)h->B, h->opt.co_spin_limit);
         HIP_TRY(h, hipEventRecord(h->ev_co_end, h->co_stream));
     }
     if (p.hand) {
@@ -1334,7 +1309,7 @@ int launch_qp(usvmpc_handle *h, const Kernels &k, int phase)
 int sort_into(usvmpc_handle *h, int *dst, int *inv)
 {
     const int B = h->B;
-    const int *prev2 = h->sort_two ? h->d_iter_prev : h->ptrs.qp_iter; // (option "sort_two_ticks" = 0: the last count alone)
+    const int *prev2 = h->opt.sort_two ? h->d_iter_prev : h->ptrs.qp_iter; // (option "sort_two_ticks" = 0: the last count alone)
     hipLaunchKernelGGL(usv_sort_hist, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_hist);
     hipLaunchKernelGGL(usv_sort_scan, dim3(1), dim3(64), 0, h->stream, h->d_hist, h->d_cursor);
     hipLaunchKernelGGL(usv_sort_scatter, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->ptrs.qp_iter, prev2, B, h->d_cursor, dst, inv);
@@ -1358,7 +1333,7 @@ int pipe_prepare(usvmpc_handle *h)
     return 0;
 }
 
-// Option "lin_force_modes" (usvmpc_handle::lin_force): the arguments of a forced pair of launches - epoch and redo words of their own, filled
+// Option "lin_force_modes" (Options::lin_force): the arguments of a forced pair of launches - epoch and redo words of their own, filled
 // here, and the inverse of the running map
 int force_prepare(usvmpc_handle *h, int epoch, DevPtrs &Pf)
 {
@@ -1391,22 +1366,22 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
     }
     // option "obstacle_tracks": p is what the tracks predict (the lineariser - the pipelined one included - never reads p: nothing made ahead
     // of time is invalidated; skipped while tracks, world clock and the stages written are what they were - not under a caller's device pointer)
-    if (h->tracks_on && (h->tracks_dirty || h->tracks_extern)) {
+    if (h->opt.tracks_on && (h->tracks_dirty || h->tracks_extern)) {
         const int rct = tracks_predict(h);
         if (rct) return rct;
     }
-    const bool pairs = h->lin_pairs != 0;
+    const bool pairs = h->opt.lin_pairs != 0;
     if (pairs && k.lin_pair[0][0] == nullptr) { h->err = "lin_pairs: the model does not declare the columns to integrate"; return USVMPC_E_ARG; }
     const group_kernel_t *lin = (pairs ? k.lin_pair : k.lin)[h->spec.sim_steps > 1 ? 1 : 0]; // [MODE]
-    const bool cond = phase == 0 && h->cond_N2 > 0; // RTI solve on the partially condensed QP (cond_ipm.hpp)
+    const bool cond = phase == 0 && h->opt.cond_N2 > 0; // RTI solve on the partially condensed QP (cond_ipm.hpp)
     const int B = h->B;
     const int slot = (int)(h->nsolves % usvmpc_handle::RING); // this solve's place in the per-solve rings
     hipEvent_t *ev = h->ev[slot];
     auto map_buf = [h](LinMap m) { return m == MAP_A ? h->d_perm : m == MAP_B ? h->d_perm2 : nullptr; };
     LinIn in = {};
     in.phase = phase; in.nsolves = h->nsolves; in.B = B; in.Bp = h->Bp; in.N = h->N;
-    in.pipeline = h->pipeline; in.dynamic_rows = h->dynamic_rows; in.sort_enabled = h->sort_enabled; in.sort_two = h->sort_two;
-    in.lin_force = h->lin_force; in.pairs = pairs; in.cond = h->cond_N2 > 0;
+    in.pipeline = h->opt.pipeline; in.dynamic_rows = h->opt.dynamic_rows; in.sort_enabled = h->opt.sort_enabled; in.sort_two = h->opt.sort_two;
+    in.lin_force = h->opt.lin_force; in.pairs = pairs; in.cond = h->opt.cond_N2 > 0;
     in.mirror = h->hm.on; in.extern_access = h->hm.extern_access;
     in.cur_map = !h->ptrs.perm ? MAP_NONE : h->ptrs.perm == h->d_perm ? MAP_A : MAP_B;
     const LinPlan p = plan_lin(in, h->sched);
@@ -1501,6 +1476,12 @@ int model_mat_planes(int model)
 #endif
     }
     return 0;
+}
+
+// planes per stage of the handle's workspace (host_spec.hpp)
+int ws_planes(const usvmpc_handle *h)
+{
+    return usv::ws_planes(h->nx, h->nu, h->kch, h->soft, model_mat_planes(h->desc.model), h->spec.any_bsoft != 0);
 }
 
 // whether the model declares the columns the lineariser has to integrate (PairCols: the paired lineariser, option "lin_pairs")
@@ -1713,38 +1694,15 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
 #ifdef USV_GEN_MODEL_HEADER
     if (d->model == USVMPC_MODEL_GENERATED) { h->kch = USV_GEN_KCH; h->soft = USV_GEN_SOFT != 0; }
 #endif
+    // (new usvmpc_handle(): every member zero, nullptr or false unless its declaration says otherwise; the options' defaults: Options)
     h->device = d->device;
-    h->bytes = 0; h->nsolves = 0; h->own_stream = true;
-    h->map_changed = false;
-    h->export_at = -1;
-    h->layout_dirty = false;
-    h->last_cond = false;
-    h->pipeline = true;
-    h->aux_stream = nullptr; h->ev_pre = nullptr; h->ev_spec = nullptr;
-    h->d_epoch = nullptr; h->d_redo = nullptr; h->d_perm2 = nullptr; h->d_inv = nullptr;
-    h->lin_pairs = model_has_pairs(h->desc.model) ? 1 : 0; h->lin_pair_launches = 0;
-    h->lin_force = 0; h->d_force_epoch = nullptr; h->d_force_redo = nullptr; h->d_force_inv = nullptr;
+    h->opt = Options::defaults(model_has_pairs(h->desc.model));
     h->sched.reset();
-    h->noise_mask = ~0u;
-    h->instance_offset = 0;
-    h->d_obs_pos = nullptr; h->d_obs_vel = nullptr; h->d_clear = nullptr; h->d_clear_min = nullptr;
-    h->tracks_on = false; h->tracks_pos_set = false; h->tracks_dirty = false; h->tracks_extern = false;
-    h->step_on_advance = true; h->clear_reset = false;
-    h->cond_N2 = 0; h->d_cond_dims = nullptr; h->d_cond_scratch = nullptr; h->cond_teams = 0; h->cond_lds = 0;
-    h->dynamic_rows = true;
     h->caps.reset();
-    h->aux_lds = true;
-    h->lds_mode = -1;
-    h->wide_mode = -1; h->last_wide = 0;
-    h->wide_waves = -1;
-    h->handover_co = -1; h->co_spin_limit = 200000; h->co_wgs = 0; h->co_ready = false; h->co_stream = nullptr; h->ev_co_pre = nullptr; h->ev_co_end = nullptr; h->d_co_ctl = nullptr;
-    h->handover_iter = -1; for (bool &e : h->ev3_set) e = false; h->handover_lds = true; h->d_susp_count = nullptr; h->d_susp_list = nullptr; h->d_susp_rec = nullptr;
-    h->max_waves = 0;
     {
         hipDeviceProp_t prop;
         h->ncu = (hipGetDeviceProperties(&prop, d->device) == hipSuccess) ? prop.multiProcessorCount : 0;
     }
-    std::memset(&h->ptrs, 0, sizeof(h->ptrs));
     auto fail = [&](int rc) {
         std::fprintf(stderr, "usvmpc_create: %s\n", h->err.c_str());
         for (void *a : h->allocs) (void)hipFree(a);
@@ -1762,7 +1720,7 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     const size_t stride = (size_t)h->Bp * LANES;
     const size_t kch = h->kch ? h->kch : 1;
     DevPtrs &P = h->ptrs;
-    h->spec.npt = ws_planes(h->nx, h->nu, h->kch, h->soft, model_mat_planes(h->desc.model), h->spec.any_bsoft != 0);
+    h->spec.npt = ws_planes(h);
     // one stage of the workspace is addressed through ONE 32-bit buffer window (lanes::Planes: group * npt * 128 + ...)
     if ((size_t)h->Bp * (size_t)h->spec.npt * 128u > (size_t)UINT32_MAX - 16384u) { // (16 KB of headroom: a parked row addresses just past the window - qp_ipm.hpp)
         h->err = "batch too large for one handle: batch * " + std::to_string(h->spec.npt * 128) + " bytes per stage exceed the 4 GiB "
@@ -1784,7 +1742,6 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
         P.yref_e = (double *)(a + lay.off[FLD_YREF_E]);
         P.p = (double *)(a + lay.off[FLD_P]);
         P.lh = (double *)(a + lay.off[FLD_LH]);
-        h->mirror = nullptr;
         if (lay.bytes() <= MIRROR_MAX) {
             HIP_C(hipHostMalloc((void **)&h->mirror, lay.bytes(), hipHostMallocDefault));
             std::memset(h->mirror, 0, lay.bytes());
@@ -1810,16 +1767,7 @@ int usvmpc_create(const usvmpc_desc *d, usvmpc_handle **out)
     TRY_C(dev_alloc(h, &h->d_iter_prev, B, true));
     TRY_C(dev_alloc(h, &h->d_hist, SORT_BINS, true));
     TRY_C(dev_alloc(h, &h->d_cursor, SORT_BINS, true));
-    h->sort_enabled = true;
-    h->sort_two = false;
-    h->merge_rows = true;
-    std::memset(&h->pf, 0, sizeof(h->pf));
-    h->pf_alloc = false; h->pf_ready = false; h->pf_stale = true; h->pf_tick = 0; h->pf_npts_cap = 0; h->pf_world_cap = 0; h->pf_margin = 0.2;
-    h->pf_vel = nullptr; h->pf_pose = nullptr;
-    h->pf_wvel = nullptr; h->pf_wvel_cap = 0; h->pf_world_set = false; h->pf_moving = false; h->pf_predict = true;
-    h->gd_ready = false; h->gd_npts_cap = 0; h->gd_psi = nullptr; h->gd_world = nullptr; h->gd_world_cap = 0;
-    std::memset(&h->gd, 0, sizeof(h->gd));
-    TRY_C(dev_alloc(h, &P.ws, (N + 1) * (size_t)ws_planes(h->nx, h->nu, h->kch, h->soft, model_mat_planes(h->desc.model), h->spec.any_bsoft != 0) * stride, true));
+    TRY_C(dev_alloc(h, &P.ws, (N + 1) * (size_t)ws_planes(h) * stride, true));
     HIP_C(hipDeviceSynchronize());
 #undef TRY_C
 #undef HIP_C
@@ -2185,11 +2133,11 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
         if (rcf) return rcf;
     }
     const long n = (long)h->B * h->nx;
-    hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->noise_mask,
-                       h->instance_offset);
+    hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->opt.noise_mask,
+                       h->opt.instance_offset);
     HIP_TRY(h, hipGetLastError());
-    if (h->tracks_on && h->step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
-    if (h->pf_moving && h->step_on_advance) return usvmpc_pf_world_step(h, h->spec.dt); // (the front end's world likewise)
+    if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
+    if (h->pf_moving && h->opt.step_on_advance) return usvmpc_pf_world_step(h, h->spec.dt); // (the front end's world likewise)
     return 0;
 }
 
@@ -2226,171 +2174,85 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     switch (h->desc.model) {
 #ifndef USV_GEN_ONLY
     case USVMPC_MODEL_USV:
-        hipLaunchKernelGGL(usv_advance_sim<ModelM0>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        hipLaunchKernelGGL(usv_advance_sim<ModelM0>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->opt.noise_mask, h->opt.instance_offset);
         break;
     case USVMPC_MODEL_GUIDANCE_CA1:
-        hipLaunchKernelGGL(usv_advance_sim<ModelM1>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        hipLaunchKernelGGL(usv_advance_sim<ModelM1>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->opt.noise_mask, h->opt.instance_offset);
         break;
     case USVMPC_MODEL_PF_CA:
-        hipLaunchKernelGGL(usv_advance_sim<ModelM2>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        hipLaunchKernelGGL(usv_advance_sim<ModelM2>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->opt.noise_mask, h->opt.instance_offset);
         break;
 #endif
 #ifdef USV_GEN_MODEL_HEADER
     case USVMPC_MODEL_GENERATED:
-        hipLaunchKernelGGL(usv_advance_sim<ModelGen>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->noise_mask, h->instance_offset);
+        hipLaunchKernelGGL(usv_advance_sim<ModelGen>, grid, block, 0, h->stream, h->ptrs, plant->T, plant->num_steps, sigma, seed, h->opt.noise_mask, h->opt.instance_offset);
         break;
 #endif
     default: h->err = "advance_sim: no plant kernel for this model in this library"; return USVMPC_E_ARG;
     }
     HIP_TRY(h, hipGetLastError());
-    if (h->tracks_on && h->step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
-    if (h->pf_moving && h->step_on_advance) return usvmpc_pf_world_step(h, plant->T);
+    if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
+    if (h->pf_moving && h->opt.step_on_advance) return usvmpc_pf_world_step(h, plant->T);
     return 0;
 }
 
-int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
+// ---- the options: option_plan.hpp holds the table (names, checks, normalisation, where a value goes, what it invalidates) and judges a call
+// as far as the handle's sizes allow; here: the preconditions on other handle state, the store, the effects and the hooks
+static OptFacts option_facts(const usvmpc_handle *h)
 {
-    if (!h) return USVMPC_E_ARG;
-    const std::string s(name ? name : "");
-    // (the obstacle-track options come first: p is read by no lineariser, so a linearisation made ahead of time stays good across them)
-    if (s == "obstacle_tracks") {
-        if (value != 0.0 && value != 1.0) { h->err = "obstacle_tracks: 0 or 1"; return USVMPC_E_ARG; }
-        if (value == 0.0) { h->tracks_on = false; return 0; } // (p stays as it stands and is the caller's again)
-        if (h->K == 0) { h->err = "obstacle_tracks: this model has no obstacle rows (K = 0)"; return USVMPC_E_ARG; }
-        if (!h->tracks_pos_set) { h->err = "obstacle_tracks: set \"obs_pos\" before switching the option on"; return USVMPC_E_ARG; }
-        if (h->pf_ready) { h->err = "obstacle_tracks: the path-following front end owns p on this handle"; return USVMPC_E_ARG; }
-        if (h->pf_moving) { h->err = "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle"; return USVMPC_E_ARG; }
-        h->tracks_on = true;
-        h->tracks_dirty = true;
-        return 0;
+    return OptFacts{h->N, h->nx, h->nu, h->K, model_has_pairs(h->desc.model), h->spec.any_bsoft != 0, h->spec.boxpack_ok != 0};
+}
+
+static int upload_spec(usvmpc_handle *h)
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(h->d_spec, &h->spec, sizeof(DevSpec), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// FX_HOOK, before anything is done: what other state of the handle forbids (nullptr: nothing)
+static const char *option_refused(const usvmpc_handle *h, OptId id, double v)
+{
+    switch (id) {
+    case OPT_OBSTACLE_TRACKS: // (off: p stays as it stands and is the caller's again)
+        if (v == 0.0) break;
+        if (!h->tracks_pos_set) return "obstacle_tracks: set \"obs_pos\" before switching the option on";
+        if (h->pf_ready) return "obstacle_tracks: the path-following front end owns p on this handle";
+        if (h->pf_moving) return "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle";
+        break;
+    case OPT_HOST_MIRROR:
+        if (v != 0.0 && !h->mirror) return "host_mirror cannot be switched on again";
+        break;
+    default: break;
     }
-    if (s == "obstacle_step_on_advance") { h->step_on_advance = value != 0.0; return 0; }
-    if (s == "pf_predict") { // a moving world inside the horizon: 1 predicted per stage, 0 held still (stage 0 only, "static_obstacles" on)
-        if (value != 0.0 && value != 1.0) { h->err = "pf_predict: 0 or 1"; return USVMPC_E_ARG; }
-        h->pf_predict = value != 0.0;
-        return h->pf_ready ? pf_apply_static(h) : 0;
-    }
-    if (s == "pf_lh_margin") { // the path-following front end's lh = (R + boat radius) + margin (scripts/usv_pf_ca/main.py:126: 0.2)
-        if (!(value >= 0.0) || value - value != 0.0) { h->err = "pf_lh_margin must be finite and non-negative"; return USVMPC_E_ARG; }
-        h->pf_margin = value;
-        return 0;
-    }
-    {
-        const int rcs = spec_cancel(h); // (options change maps, layouts or launches: a lineariser that ran ahead is not trusted across them)
-        if (rcs) return rcs;
-    }
-    if (s == "pipeline_linearize") { h->pipeline = value != 0.0; return 0; }
-    if (s == "sort_by_difficulty") {
-        h->sort_enabled = value != 0.0;
-        if (!h->sort_enabled && h->ptrs.perm) { h->ptrs.perm = nullptr; h->map_changed = true; }
-        return 0;
-    }
-    if (s == "max_waves") { h->max_waves = (long)value; h->caps.reset(); cond_release(h); return 0; }
-    if (s == "keep_multipliers") { // create the "lam" / "t" buffers now (a partially condensed solve fills them only if they exist)
-        if (value == 0.0) return 0;
+    return nullptr;
+}
+
+// FX_HOOK, after the store
+static int option_hook(usvmpc_handle *h, OptId id, double v)
+{
+    switch (id) {
+    case OPT_OBSTACLE_TRACKS:
+        if (v != 0.0) h->tracks_dirty = true;
+        break;
+    case OPT_PF_PREDICT: return h->pf_ready ? pf_apply_static(h) : 0;
+    case OPT_SORT_BY_DIFFICULTY:
+        if (v == 0.0 && h->ptrs.perm) { h->ptrs.perm = nullptr; h->map_changed = true; }
+        break;
+    case OPT_KEEP_MULTIPLIERS: { // create the "lam" / "t" buffers now (a partially condensed solve fills them only if they exist)
         DevPtrs &P = h->ptrs;
-        if (!P.lam_out) {
-            HIP_TRY(h, hipSetDevice(h->device));
-            P.nlam = lam_len(h->spec, h->soft);
-            const size_t cnt = (size_t)h->B * (h->N + 1) * (size_t)(P.nlam > 0 ? P.nlam : 1);
-            if (dev_alloc(h, &P.lam_out, cnt, false)) return USVMPC_E_HIP;
-            if (dev_alloc(h, &P.t_out, cnt, false)) { P.lam_out = nullptr; return USVMPC_E_HIP; }
-            h->export_at = -1;
-        }
-        return 0;
-    }
-    if (s == "qp_cond_N") { // acados qp_solver_cond_N: stages of the partially condensed QP; 0 or N: no condensing (the default)
-        const int n2 = (int)value;
-        if (n2 < 0 || n2 > h->N) { h->err = "qp_cond_N must lie in 0..N"; return USVMPC_E_ARG; }
-        const int want = (n2 == 0 || n2 == h->N) ? 0 : n2;
-        if (want > 0) {
-            // (blocks as HPIPM partitions them: N / N2 stages each, the first N mod N2 one more; one block's variables must fit a wave)
-            if (h->nx + ((h->N + want - 1) / want) * h->nu > 64) { h->err = "qp_cond_N: a condensed stage may have at most 64 variables (nx + ceil(N / qp_cond_N) nu)"; return USVMPC_E_ARG; }
-            if (h->spec.any_bsoft) { h->err = "partial condensing (qp_cond_N) is not built for soft state bounds"; return USVMPC_E_ARG; }
-        }
-        if (want != h->cond_N2) { cond_release(h); h->cond_N2 = want; h->map_changed = true; }
-        return 0;
-    }
-    if (s == "sort_two_ticks") { h->sort_two = value != 0.0; return 0; }
-    if (s == "lin_force_modes") { // (tests: usvmpc_handle::lin_force)
-        if (value != 0.0 && value != 1.0 && value != 2.0) { h->err = "lin_force_modes: 0, 1 or 2"; return USVMPC_E_ARG; }
-        h->lin_force = (int)value;
-        return 0;
-    }
-    if (s == "lin_pairs") { // (usvmpc_handle::lin_pairs)
-        if (value != 0.0 && value != 1.0) { h->err = "lin_pairs: 0 or 1"; return USVMPC_E_ARG; }
-        if (value != 0.0 && !model_has_pairs(h->desc.model)) { h->err = "lin_pairs: the model does not declare the columns to integrate"; return USVMPC_E_ARG; }
-        h->lin_pairs = (int)value;
-        return 0;
-    }
-    if (s == "aux_in_lds") { h->aux_lds = value != 0.0; h->caps.reset(); return 0; }
-    if (s == "lds_workspace") { // -1: when the batch is small (default), 0: never, 1: whenever an instance's planes fit in LDS
-        h->lds_mode = value < 0.0 ? -1 : (value > 0.0 ? 1 : 0);
-        h->caps.reset();
-        return 0;
-    }
-    if (s == "wide") { // the latency mapping, one instance per wave: -1 for batches that leave SIMDs idle (default), 0 never, 1 whenever it applies
-        h->wide_mode = value < 0.0 ? -1 : (value > 0.0 ? 1 : 0);
-        h->caps.reset();
-        return 0;
-    }
-    if (s == "wide_waves") { // waves per instance of the latency mapping: -1 (default) four for soft-row OCPs / two obstacle chunks up to one instance per CU, else one; 1; 4
-        h->wide_waves = value < 0.0 ? -1 : (value >= 4.0 ? 4 : 1);
-        h->caps.reset();
-        return 0;
-    }
-    if (s == "dynamic_rows") { // 0: one group per row for the whole launch (the rows of a wave wait for its slowest)
-        h->dynamic_rows = value != 0.0;
-        h->caps.reset();
-        return 0;
-    }
-    if (s == "cond_pred_corr" || s == "cpc_factor" || s == "hpipm_mode") {
-        // HPIPM's conditional predictor-corrector (d_ocp_qp_ipm_arg.cond_pred_corr: on in every mode acados picks from - DESIGN.md section 2): a
-        // corrected step that leaves the duality measure above cpc_factor (2) x the predictor's mu_aff is replaced by the centring-only step.
-        // Changes the iteration path, i.e. results inside the exit tolerance ball.  Built into every kernel; the option switches the test.
-        // "hpipm_mode": the profile's values of mu0, alpha_min and cond_pred_corr (host_spec.hpp, hpipm_profile).
-        if (s == "cpc_factor") { if (!(value > 0.0)) { h->err = "cpc_factor must be positive"; return USVMPC_E_ARG; } h->spec.cpc_factor = value; }
-        else if (s == "hpipm_mode") {
-            usvmpc_desc d;
-            if (value != (double)(int)value || !hpipm_profile(d, (int)value)) { h->err = "hpipm_mode must be one of USVMPC_HPIPM_*"; return USVMPC_E_ARG; }
-            h->spec.mu0 = d.mu0; h->spec.alpha_min = d.alpha_min; h->spec.cpc = d.cond_pred_corr; h->spec.cpc_factor = d.cpc_factor;
-        } else {
-            h->spec.cpc = value != 0.0 ? 1 : 0;
-        }
+        if (v == 0.0 || P.lam_out) break;
         HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMemcpyAsync(h->d_spec, &h->spec, sizeof(DevSpec), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return 0;
+        P.nlam = lam_len(h->spec, h->soft);
+        const size_t cnt = (size_t)h->B * (h->N + 1) * (size_t)(P.nlam > 0 ? P.nlam : 1);
+        if (dev_alloc(h, &P.lam_out, cnt, false)) return USVMPC_E_HIP;
+        if (dev_alloc(h, &P.t_out, cnt, false)) { P.lam_out = nullptr; return USVMPC_E_HIP; }
+        h->export_at = -1;
+        break;
     }
-    if (s == "handover_iter") { // IPM iterations after which a row of a drained launch hands its instance over to the follow-up launch; 0: never
-        if (value > 1e6) { h->err = "handover_iter out of range"; return USVMPC_E_ARG; }
-        h->handover_iter = value < 0.0 ? -1 : (int)value;   // (-1: the default - qp_plan.hpp: past 20 for small batches when the follow-up works in LDS, else never)
-        return 0;
-    }
-    if (s == "handover_lds") { h->handover_lds = value != 0.0; h->caps.reset(); return 0; }
-    if (s == "handover_co") { h->handover_co = value < 0.0 ? -1 : (value != 0.0 ? 1 : 0); return 0; } // the follow-up kernel beside the draining launch (default) or only behind it
-    if (s == "handover_co_spin") { if (!(value >= 1.0 && value <= 2e9)) { h->err = "handover_co_spin out of range"; return USVMPC_E_ARG; } h->co_spin_limit = (int)value; return 0; }
-    if (s == "handover_co_wgs") { if (!(value >= 0.0 && value <= 1e6)) { h->err = "handover_co_wgs out of range"; return USVMPC_E_ARG; } h->co_wgs = (long)value; return 0; } // the follow-up launch with the planes copied into LDS when the horizon fits (default), or always over the planes in HBM
-    if (s == "disturbance_mask") { // bit j: usvmpc_advance adds its noise to state j
-        h->noise_mask = (unsigned)value;
-        return 0;
-    }
-    if (s == "instance_offset") { // global index of instance 0 of this handle: the disturbance of a shard is that of the unsharded batch
-        if (!(value >= 0.0 && value <= 9007199254740992.0) || value != (double)(long long)value) {
-            h->err = "instance_offset must be a non-negative integer";
-            return USVMPC_E_ARG;
-        }
-        h->instance_offset = (long long)value;
-        return 0;
-    }
-    if (s == "merge_box_rows") { // 1 (default): box rows processed in their slot lanes when all of them ride there
-        h->merge_rows = value != 0.0;   // (another set of kernels: merged / two-pass instantiations, wide ones included)
-        h->caps.reset();
-        return 0;
-    }
-    if (s == "host_mirror") { // 0: drop the pinned host mirror of the caller-visible arrays (every set / get then goes to the device)
-        if (value != 0.0) { if (!h->mirror) { h->err = "host_mirror cannot be switched on again"; return USVMPC_E_ARG; } return 0; }
-        if (!h->mirror) return 0;
+    case OPT_HOST_MIRROR: { // 0: drop the pinned host mirror of the caller-visible arrays (every set / get then goes to the device)
+        if (v != 0.0 || !h->mirror) break;
         HIP_TRY(h, hipSetDevice(h->device));
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
@@ -2398,19 +2260,61 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
         h->hm.dropped();
         (void)hipHostFree(h->mirror);
         h->mirror = nullptr;
-        return 0;
+        break;
     }
-    if (s == "static_obstacles" || s == "pack_box_rows") {
-        if (s == "static_obstacles") { h->spec.p_static = value != 0.0; h->tracks_dirty = true; } // (the stages the prediction writes change)
-        else { h->spec.boxpack = (value != 0.0 && h->spec.boxpack_ok) ? 1 : 0; h->caps.reset(); h->layout_dirty = true; }
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMemcpyAsync(h->d_spec, &h->spec, sizeof(DevSpec), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return 0;
+    default: break;
     }
-    h->err = "unknown option '" + s + "'";
-    return USVMPC_E_FIELD;
+    return 0;
 }
+
+// an accepted value (parse_option's) takes effect: the steps in this order for every option, each where the row asks for it.  Also the
+// typed way in for the library's own switches ("static_obstacles": guidance_reset, pf_apply_static).
+static int apply_option(usvmpc_handle *h, OptId id, double v)
+{
+    const OptRow &row = OPTION_TABLE[id];
+    if (!(row.fx & FX_KEEPS_AHEAD)) { // (options change maps, layouts or launches: a lineariser that ran ahead is not trusted across them)
+        const int rcs = spec_cancel(h);
+        if (rcs) return rcs;
+    }
+    const bool act = !(row.fx & FX_IF_CHANGED) || load(h->opt, row.at) != v;
+    DevSpec &S = h->spec;
+    switch (id) { // the store: Options, or DevSpec for what the kernels read
+    case OPT_STATIC_OBSTACLES: S.p_static = v != 0.0; break;
+    case OPT_PACK_BOX_ROWS: S.boxpack = v != 0.0; break;
+    case OPT_COND_PRED_CORR: S.cpc = v != 0.0; break;
+    case OPT_CPC_FACTOR: S.cpc_factor = v; break;
+    case OPT_HPIPM_MODE: {
+        usvmpc_desc d;
+        hpipm_profile(d, (int)v);
+        S.mu0 = d.mu0; S.alpha_min = d.alpha_min; S.cpc = d.cond_pred_corr; S.cpc_factor = d.cpc_factor;
+        break;
+    }
+    default: store(h->opt, row.at, v);
+    }
+    if (act) {
+        if (row.fx & FX_CAPS) h->caps.reset();
+        if (row.fx & FX_COND_RELEASE) cond_release(h);
+        if (row.fx & FX_MAP_CHANGED) h->map_changed = true;
+        if (row.fx & FX_LAYOUT_DIRTY) h->layout_dirty = true;
+        if (row.fx & FX_TRACKS_DIRTY) h->tracks_dirty = true;
+        if (row.fx & FX_UPLOAD_SPEC) {
+            const int rcu = upload_spec(h);
+            if (rcu) return rcu;
+        }
+    }
+    return (row.fx & FX_HOOK) ? option_hook(h, id, v) : 0;
+}
+
+int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
+{
+    if (!h) return USVMPC_E_ARG;
+    const OptParse p = parse_option(name, value, option_facts(h));
+    if (p.rc) { h->err = p.err; return p.rc; }
+    if (p.row->fx & FX_HOOK)
+        if (const char *why = option_refused(h, p.row->id, p.value)) { h->err = why; return USVMPC_E_ARG; }
+    return apply_option(h, p.row->id, p.value);
+}
+
 
 // ---- guidance front end (M1 only): see guidance.hpp
 static int guidance_alloc(usvmpc_handle *h, int npts)
@@ -2460,7 +2364,7 @@ int usvmpc_guidance_reset(usvmpc_handle *h, const double *waypoints, int npts, c
     hipLaunchKernelGGL(usv_guidance_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, G, h->gd_psi, (int)B);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!h->spec.p_static) return usvmpc_set_option(h, "static_obstacles", 1.0);
+    if (!h->spec.p_static) return apply_option(h, OPT_STATIC_OBSTACLES, 1.0);
     return 0;
 }
 
@@ -2564,9 +2468,9 @@ static int pf_check(usvmpc_handle *h)
 // "static_obstacles" as the front end needs it: off only while the world moves AND is predicted per stage (prepare then writes all stages)
 static int pf_apply_static(usvmpc_handle *h)
 {
-    const bool want = !(h->pf_moving && h->pf_predict);
+    const bool want = !(h->pf_moving && h->opt.pf_predict);
     if ((h->spec.p_static != 0) == want) return 0;
-    return usvmpc_set_option(h, "static_obstacles", want ? 1.0 : 0.0);
+    return apply_option(h, OPT_STATIC_OBSTACLES, want ? 1.0 : 0.0);
 }
 
 static int pf_alloc(usvmpc_handle *h)
@@ -2593,7 +2497,7 @@ int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
     int rc = pf_check(h);
     if (rc) return rc;
     if (!waypoints || npts < 2) { h->err = "pf_reset: a waypoint list of at least two points is needed"; return USVMPC_E_ARG; }
-    if (h->tracks_on) { h->err = "pf_reset: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    if (h->opt.tracks_on) { h->err = "pf_reset: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
     rc = pf_alloc(h);
     if (rc) return rc;
     PfPtrs &F = h->pf;
@@ -2659,7 +2563,7 @@ int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel)
         return h->pf_ready ? pf_apply_static(h) : 0;
     }
     if (!h->pf_world_set) { h->err = "pf_world_vel: no world list yet (usvmpc_pf_world first)"; return USVMPC_E_ARG; }
-    if (h->tracks_on) { h->err = "pf_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    if (h->opt.tracks_on) { h->err = "pf_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
     PfPtrs &F = h->pf;
     const size_t need = (size_t)h->B * (size_t)F.nworld * 2;
     for (size_t i = 0; i < need; i++)
@@ -2725,8 +2629,8 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     rc = spec_cancel(h); // (a caller write of yref as far as the pipelined lineariser is concerned: pf_guidance.hpp)
     if (rc) return rc;
     PfPtrs F = h->pf;
-    F.margin = h->pf_margin;
-    F.wvel = (h->pf_moving && h->pf_predict) ? h->pf_wvel : nullptr; // (held still inside the horizon: the prepare of a world at rest)
+    F.margin = h->opt.pf_margin;
+    F.wvel = (h->pf_moving && h->opt.pf_predict) ? h->pf_wvel : nullptr; // (held still inside the horizon: the prepare of a world at rest)
     const size_t B = h->B;
     if (vel_uvr) {
         HIP_TRY(h, hipMemcpyAsync(h->pf_vel, vel_uvr, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -2793,7 +2697,7 @@ int usvmpc_calibrate_traffic(usvmpc_handle *h, int nplanes, double *bytes_read, 
         if (rcs) return rcs;
     }
     const long stride = (long)h->Bp * LANES;
-    const long avail = (long)(h->N + 1) * ws_planes(h->nx, h->nu, h->kch, h->soft, model_mat_planes(h->desc.model), h->spec.any_bsoft != 0);
+    const long avail = (long)(h->N + 1) * ws_planes(h);
     if (nplanes + 1 > avail) { h->err = "nplanes exceeds the workspace"; return USVMPC_E_ARG; }
     if ((size_t)h->Bp * (size_t)(nplanes + 1) * 128u > (size_t)UINT32_MAX) { // (usv_calib_stream addresses it all through one 32-bit window)
         h->err = "nplanes * batch exceeds the 4 GiB buffer window of the calibration kernel";
@@ -2821,8 +2725,8 @@ int usvmpc_set_stream(usvmpc_handle *h, void *stream)
     {
         const int rcs = spec_cancel(h);
         if (rcs) return rcs;
-        h->pipeline = false; // (the caller's stream carries the caller's own ordering: nothing of this handle runs beside it)
-        h->handover_co = 0;
+        h->opt.pipeline = false; // (the caller's stream carries the caller's own ordering: nothing of this handle runs beside it)
+        h->opt.handover_co = 0;
     }
     if (h->own_stream) (void)hipStreamDestroy(h->stream);
     h->stream = (hipStream_t)stream;

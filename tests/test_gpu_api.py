@@ -64,6 +64,32 @@ def test_error_codes_and_messages():
     s.close()
 
 
+def test_refused_options_return_their_code_and_text_and_change_nothing():
+    """usvmpc_set_option through the option table (csrc/option_plan.hpp): the refusals that live in usvmpc.hip's hooks and glue - the ones
+    tests/test_option_plan.py cannot reach - with their code and exact text; after all of them the handle solves to the bits of a fresh one."""
+    def refused(s, name, value, code, text):
+        assert s._lib.usvmpc_set_option(s._h, name, value) == code
+        assert s._lib.usvmpc_last_error(s._h) == text
+
+    ocp, wl, s = _mk("usv_model_pf_ca", 6, 3, 4)
+    refused(s, b"obstacle_tracks", 1.0, -1, b'obstacle_tracks: set "obs_pos" before switching the option on')
+    refused(s, b"qp_cond_N", 7.0, -1, b"qp_cond_N must lie in 0..N")
+    assert s._lib.usvmpc_set_option(s._h, b"host_mirror", 0.0) == 0
+    refused(s, b"host_mirror", 1.0, -1, b"host_mirror cannot be switched on again")
+    refused(s, b"disturbance_mask", -1.0, -1, b"disturbance_mask out of range")
+    refused(s, b"max_waves", float("nan"), -1, b"max_waves out of range")
+    refused(s, b"nope", 1.0, -2, b"unknown option 'nope'")
+    st = s.solve()
+    ocp, wl, fresh = _mk("usv_model_pf_ca", 6, 3, 4)
+    assert np.array_equal(fresh.solve(), st)
+    assert np.array_equal(fresh.get_all("x"), s.get_all("x")) and np.array_equal(fresh.get_all("u"), s.get_all("u"))
+    fresh.close()
+    s.close()
+    ocp, wl, g = _mk("usv_model_guidance_ca1", 6, 3, 4)
+    refused(g, b"lin_pairs", 1.0, -1, b"lin_pairs: the model does not declare the columns to integrate")
+    g.close()
+
+
 def test_nan_input_gives_status_4_and_leaves_iterate_untouched():
     ocp, wl, s = _mk("usv_model_guidance_ca1", 8, 4, 8)
     x0 = wl["x0"].copy()
