@@ -18,22 +18,19 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: F401,E402  (before the solver library: one HIP runtime for both)
-from mpc_collisionavoidance_amd import AcadosSim, BatchOcpSolver, BatchSimSolver, usv_models  # noqa: E402
+from mpc_collisionavoidance_amd import AcadosSim, BatchOcpSolver, BatchSimSolver, scenario, usv_models  # noqa: E402
 from mpc_collisionavoidance_amd.guidance import GuidanceFrontEnd  # noqa: E402
 
 
 def make_worlds(B, L, rng):
-    """L obstacles per scenario along the first leg (4,-5) -> (4,25): one every 25/L metres (jittered), up to
-    1.5 m off the path to either side, radius 0.3..0.8 m - the reference scenario's density
-    (usv_guidance_ca1/main.py: four obstacles on a 30 m leg), randomised."""
-    y = -1.0 + (np.arange(L)[None, :] + rng.uniform(0.2, 0.8, (B, L))) * (25.0 / L)
-    x = 4.0 + rng.uniform(-1.5, 1.5, (B, L))
-    r = rng.uniform(0.3, 0.8, (B, L))
-    return np.stack([x, y, r], axis=2)
+    """scenario.make_ca_worlds: L obstacles per scenario along the first leg (4,-5) -> (4,25)."""
+    return scenario.make_ca_worlds(B, L, rng)
 
 
-def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None):
-    rng = np.random.default_rng(seed)
+def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None, resident=False, moving=False, predict=True):
+    """resident=False: the host-fed loop (the ROS nodes' callbacks, arrays through the host every tick).  resident=True: the whole mission
+    on the device - the world is uploaded once, a tick is prepare() -> solve_async -> publish(fetch=False) -> advance, and the host reads
+    once at the end.  moving=True (resident only): the obstacles cross the first leg and the horizon sees where they will be (predict)."""
     dt = 0.05
     ocp = usv_models.make_ocp("usv_model_guidance_ca1", N * dt, N, K)
     s = BatchOcpSolver(ocp, B)
@@ -44,35 +41,40 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
         sim.solver_options.T, sim.solver_options.num_steps, sim.solver_options.sens_forw = dt, int(plant_steps), False
         plant = BatchSimSolver(sim, B)
     fe = GuidanceFrontEnd(s)
-    wps = np.array([[4.0, -5.0], [4.0, 25.0], [10.0, 30.0]])
-    world = make_worlds(B, L, rng)
-    pose = np.column_stack([4.0 + rng.uniform(-1, 1, B), np.full(B, -5.0), np.full(B, np.pi / 2) + rng.uniform(-0.3, 0.3, B)])
-    vel = np.column_stack([np.full(B, 0.7), np.zeros(B)])
+    m = scenario.make_ca_missions(B, L, seed, moving=moving)
+    wps, world, pose, vel = m["waypoints"], m["world"], m["pose"], m["vel"]
     fe.reset(wps, pose[:, 2])
-    min_clear = np.full(B, np.inf)
-    bad = np.zeros(B, dtype=bool)
-    t0 = time.perf_counter()
-    for i in range(ticks):
-        fe.sense(pose, world, max_radius=100.0)      # obstacle_sim_node.simulate()
-        fe.prepare(vel, pose)                        # obstaclesCallback + waypoint_manager + control() inputs
-        st = s.solve()                               # acados_solve()
-        out = fe.publish()                           # desired heading / r / speed
-        bad |= (st != 0) & (out["active"] != 0)
-        if plant is None:
-            x1 = s.get("x", 1)
-        else:
-            plant.set("x", s.get("x", 0))
-            plant.set("u", s.get("u", 0))
-            plant.solve()
-            x1 = plant.get("x")
-        vel, pose = x1[:, 0:2].copy(), x1[:, 5:8].copy()
-        d = np.sqrt((pose[:, None, 0] - world[:, :, 0]) ** 2 + (pose[:, None, 1] - world[:, :, 1]) ** 2) - (world[:, :, 2] + 0.5)
-        min_clear = np.minimum(min_clear, d.min(axis=1))
-    el = time.perf_counter() - t0
-    k, _ = fe.state()
-    res = dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, min_clearance=min_clear, solver_failures=bad,
-               waypoint_index=k, final_pose=pose)
+    if moving and not resident:
+        raise Exception("a moving world needs the device-resident loop (resident=True)")
+    if resident:
+        res = _run_resident(s, fe, plant, m, ticks, predict)
+    else:
+        min_clear = np.full(B, np.inf)
+        bad = np.zeros(B, dtype=bool)
+        t0 = time.perf_counter()
+        for i in range(ticks):
+            fe.sense(pose, world, max_radius=100.0)      # obstacle_sim_node.simulate()
+            fe.prepare(vel, pose)                        # obstaclesCallback + waypoint_manager + control() inputs
+            st = s.solve()                               # acados_solve()
+            out = fe.publish()                           # desired heading / r / speed
+            bad |= (st != 0) & (out["active"] != 0)
+            if plant is None:
+                x1 = s.get("x", 1)
+            else:
+                plant.set("x", s.get("x", 0))
+                plant.set("u", s.get("u", 0))
+                plant.solve()
+                x1 = plant.get("x")
+            vel, pose = x1[:, 0:2].copy(), x1[:, 5:8].copy()
+            d = np.sqrt((pose[:, None, 0] - world[:, :, 0]) ** 2 + (pose[:, None, 1] - world[:, :, 1]) ** 2) - (world[:, :, 2] + 0.5)
+            min_clear = np.minimum(min_clear, d.min(axis=1))
+        el = time.perf_counter() - t0
+        k, _ = fe.state()
+        res = dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, min_clearance=min_clear, solver_failures=bad,
+                   waypoint_index=k, final_pose=pose)
     if not quiet:
+        el = ticks / res["ticks_per_s"]
+        min_clear, bad, k = res["min_clearance"], res["solver_failures"], res["waypoint_index"]
         print("%d scenarios x %d ticks in %.2f s (%.0f scenario-ticks/s)" % (B, ticks, el, B * ticks / el))
         print("minimum clearance to the keep-out circle (R + 0.5 m): worst %.3f m, 1st percentile %.3f m, median %.3f m"
               % (min_clear.min(), np.percentile(min_clear, 1), np.median(min_clear)))
@@ -83,6 +85,42 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
     return res
 
 
+def _run_resident(s, fe, plant, m, ticks, predict):
+    """The device-resident loop.  min_clearance is the front end's: the minimum over the poses the ticks were PREPARED at (the start pose
+    included, the pose after the last tick not), where the host-fed loop takes the poses after each tick.
+    solver_failures: an instance's status after the last tick, missions that are over left out as in the host-fed loop; the ticks before
+    are audited through the device-side failure counts (usvmpc_fail_counts: a ring of 64 solves, read once per 64 ticks and at the end) -
+    a failure in an earlier tick, before any mission was over, marks EVERY instance, since the host does not know which one it was."""
+    B = s.B
+    x0 = np.zeros((B, 8))
+    x0[:, 0:2], x0[:, 5:8] = m["vel"], m["pose"]
+    s.set("x0", 0, x0)
+    fe.set_world(m["world"], max_radius=100.0, vel=m.get("world_vel"), predict=predict)
+    fails = []
+    t0 = time.perf_counter()
+    for i in range(ticks):
+        fe.prepare()                                 # sensor + callbacks + waypoint manager, from the solver's own x0
+        s.solve_async()
+        fe.publish(fetch=False)
+        if plant is None:
+            s.advance(0.0, i)
+        else:
+            s.advance_sim(plant, 0.0, i)
+        if (i + 1) % 64 == 0 or i + 1 == ticks:
+            fails.append(s.fail_counts((i % 64) + 1))
+    s.sync()
+    el = time.perf_counter() - t0
+    st = fe.mission_state()
+    fails = np.concatenate(fails) if fails else np.zeros(0, dtype=int)
+    over = st["finish_tick"] >= 0
+    bad = (s.get_int("status") != 0) & ~over
+    audited = min(ticks - 1, int(st["finish_tick"][over].min())) if over.any() else ticks - 1
+    if ticks and fails[:max(audited, 0)].any():
+        bad[:] = True
+    return dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, min_clearance=st["min_clearance"], solver_failures=bad,
+                waypoint_index=st["wp_index"], final_pose=s.get("x0", 0)[:, 5:8].copy(), finish_tick=st["finish_tick"], fail_counts=fails)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -90,5 +128,8 @@ if __name__ == "__main__":
     ap.add_argument("--horizon", type=int, default=100, help="the reference uses N = 100, Tf = 5 s; shorter horizons see the obstacles too late")
     ap.add_argument("--plant-steps", type=int, default=None,
                     help="integrate the plant in this many RK4 steps per tick (default: the plant is the controller's prediction x_1)")
+    ap.add_argument("--resident", action="store_true", help="keep the whole mission on the device (no host array, no synchronisation per tick)")
+    ap.add_argument("--moving", action="store_true", help="the obstacles cross the first leg at up to 0.3 m/s (device-resident loop)")
+    ap.add_argument("--no-predict", action="store_true", help="with --moving: hold the world still inside the horizon")
     a = ap.parse_args()
-    run(a.batch, a.ticks, a.horizon, plant_steps=a.plant_steps)
+    run(a.batch, a.ticks, a.horizon, plant_steps=a.plant_steps, resident=a.resident or a.moving, moving=a.moving, predict=not a.no_predict)

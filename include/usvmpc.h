@@ -350,6 +350,41 @@ int usvmpc_guidance_sense(usvmpc_handle *h, const double *pose, const double *wo
                           double *obstacles, int *n_obstacles);
 int usvmpc_guidance_publish(usvmpc_handle *h, double *heading, double *r_des, double *speed, double *ye, int *active);
 int usvmpc_guidance_state(usvmpc_handle *h, int *wp_index, float *past_psied);
+/* DEVICE-RESIDENT MISSIONS (the arithmetic: csrc/ca_guidance.hpp; the kernel: usv_guidance_tick).  The calls above talk to the host on every
+ * tick; the ones below keep a mission on the device: a tick is prepare(NULL, NULL) -> usvmpc_solve_async -> publish(all NULL) ->
+ * usvmpc_advance / usvmpc_advance_sim, with no host array and no stream synchronisation.  usv_model_guidance_ca1 only (any other model:
+ * USVMPC_E_ARG with a message); all need usvmpc_guidance_reset first.
+ *   world     : world [B][n_world][3] = NED (X, Y, R), 0 <= n_world <= 64, uploaded ONCE; replaces the previous list.  A NaN entry is refused.
+ *   prepare   with vel_uv and pose both NULL (one of them NULL: USVMPC_E_ARG): needs a world list (an empty one will do).  A pending host
+ *             mirror is uploaded first; then ONE kernel launch on the handle's stream, no synchronisation.  Per instance: (u, v) = x0[0..1] and
+ *             (nedx, nedy, psi) = x0[5..7] as usvmpc_advance / usvmpc_advance_sim left them; the simulator's visible entries at that pose in
+ *             list order (never stored); the nearest-K choice, body -> NED through float32, stage 0 of p / lh; the waypoint manager; x0 when
+ *             the tick is active; the running minimum clearance; finish_tick at the first tick that finds the mission over.  These are the bits
+ *             usvmpc_guidance_sense + the host-fed prepare make from the same pose.  An instance whose mission was over before the tick keeps
+ *             its x0, p and lh.  The call writes x0, p and lh only - nothing a lineariser reads - so with option "pipeline_linearize" the
+ *             linearisation made a tick ahead stands (the path-following front end's prepare discards it).
+ *   publish   with every output NULL: enqueues and returns without synchronising.
+ *   mission_state: wp_index [B], past_psied [B], finish_tick [B] (device-resident prepares since reset, from 0, at the first one that found
+ *             the mission over; -1 before), min_clearance [B] (min over the visible entries and the resident ticks of
+ *             sqrt(dx^2 + dy^2) - (R + 0.5) at the tick's pose, squares and sum rounded one by one; 1e300 before the first update; reset by
+ *             usvmpc_guidance_reset).  Any may be NULL.
+ *   world_vel : vel [B][n_world][2], NED m/s, for the current list: the world moves.  predict != 0: a resident prepare still selects on the
+ *             current positions exactly as above and then writes EVERY stage for the K slots it chose: p[k][2 slot + c] = P_c + ((double)k * dt)
+ *             * v_c, k = 0 .. N (unfused: csrc/obstacle_tracks.hpp), P_c the float32-rounded NED coordinate the node would have computed;
+ *             lh[k][slot] replicated for k = 0 .. N-1; unused slots (1000, 1000) / 0 at every stage; "static_obstacles" goes off.  predict == 0:
+ *             the world moves between ticks but is held still inside the horizon - stage 0 only, "static_obstacles" stays on.  NULL: the world
+ *             is at rest again, "static_obstacles" on again.  USVMPC_E_ARG with a message, nothing changed: option "obstacle_tracks" on (and
+ *             switching it on while this world moves is refused likewise: both would own p); an entry that is not finite; no world list yet.
+ *             usvmpc_guidance_world on a moving world KEEPS the velocities when n_world is unchanged; otherwise the new list is at rest.
+ *   world_step: enqueues world[i][c] += T * vel[i][c] (unfused; R untouched); refused while the world is at rest.  While the world moves
+ *             usvmpc_advance calls it with dt and usvmpc_advance_sim with the plant's period, behind their own kernel, unless option
+ *             "obstacle_step_on_advance" is 0.
+ *   world_read: what the device holds - world [B][n_world][3], vel [B][n_world][2] (zeros for a world at rest); either may be NULL. */
+int usvmpc_guidance_world(usvmpc_handle *h, const double *world, int n_world, double max_radius);
+int usvmpc_guidance_world_vel(usvmpc_handle *h, const double *vel, int predict);
+int usvmpc_guidance_world_step(usvmpc_handle *h, double T);
+int usvmpc_guidance_world_read(usvmpc_handle *h, double *world, double *vel);
+int usvmpc_guidance_mission_state(usvmpc_handle *h, int *wp_index, float *past_psied, int *finish_tick, double *min_clearance);
 /* ---- Path-following front end (model usv_model_pf_ca only; any other model: USVMPC_E_ARG with a message): the arithmetic either side
  * of the solver call in the reference's path-following ROS node, batched on the device (class NMPC in catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp;
  * nmpc_pf_ca.cpp is the same file; the arithmetic: csrc/pf_guidance.hpp).  Per-instance state (waypoint index k, past thrust, the reference

@@ -69,7 +69,9 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_sim_create", "usvmpc_sim_destroy", "usvmpc_sim_set", "usvmpc_sim_solve", "usvmpc_sim_get", "usvmpc_sim_get_device_ptr",
            "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step",
            "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state",
-           "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read"]
+           "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read",
+           "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
+           "usvmpc_guidance_mission_state"]
 
 
 _libs = {}
@@ -130,6 +132,11 @@ def load(path):
     L.usvmpc_guidance_publish.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
     L.usvmpc_guidance_state.argtypes = [C.c_void_p, _ip, C.POINTER(C.c_float)]
     _fp = C.POINTER(C.c_float)
+    L.usvmpc_guidance_world.argtypes = [C.c_void_p, _dp, C.c_int, C.c_double]
+    L.usvmpc_guidance_world_vel.argtypes = [C.c_void_p, _dp, C.c_int]
+    L.usvmpc_guidance_world_step.argtypes = [C.c_void_p, C.c_double]
+    L.usvmpc_guidance_world_read.argtypes = [C.c_void_p, _dp, _dp]
+    L.usvmpc_guidance_mission_state.argtypes = [C.c_void_p, _ip, _fp, _ip, _dp]
     L.usvmpc_pf_reset.argtypes = [C.c_void_p, _dp, C.c_int]
     L.usvmpc_pf_world.argtypes = [C.c_void_p, _dp, C.c_int, C.c_double]
     L.usvmpc_pf_prepare.argtypes = [C.c_void_p, _dp, _dp]

@@ -591,6 +591,122 @@ __global__ void __launch_bounds__(256) usv_pf_publish(DevPtrs P, PfPtrs F)
     }
 }
 
+// ---- Guidance front end, device-resident (model usv_model_guidance_ca1; the arithmetic: ca_guidance.hpp; host-fed kernels: guidance.hpp).
+constexpr int CA_GROUP = 64; // instances per workgroup of usv_guidance_tick
+
+static __global__ void usv_guidance_mission_reset(double *min_clear, int *finish_tick, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    min_clear[b] = 1e300;
+    finish_tick[b] = -1;
+}
+
+// usv_guidance_tick: the node's input side for a vessel whose state is the solver's own x0 (as usv_advance / usv_advance_sim left it) against
+// a world list that lives on the device.  One workgroup per CA_GROUP consecutive instances, laid out as usv_pf_prepare:
+// 1. Decide: the first wave, one lane per instance - (u, v) = x0[0..1], (nedx, nedy, psi) = x0[5..7]; the simulator's visibility test and
+//    NED -> body transform per world entry (L <= 64; the body-frame list is never stored), the ranking distance of each visible entry ONCE
+//    into LDS ([64 entries][64 lanes]: a lane walks its own column, consecutive lanes consecutive words - no bank conflict), the nearest-K
+//    choice by comparisons, body -> NED through float32 for the chosen ones, the running minimum clearance, the waypoint manager, x0.  An
+//    instance whose mission was over before this tick (k >= npts) keeps its x0, p and lh and is skipped altogether; the tick that ends a
+//    mission still writes p and lh (as usv_guidance_pre does) and records finish_tick.  World at rest: the deciding lane stores stage 0.
+// 2. Stream (W.wvel: a moving world that is predicted): the decide step left each slot's TRACK (float32-rounded NED position, the chosen
+//    entry's velocity, lh) in the [B][K] scratch W.trk_pv / W.trk_lh.  The workgroup's instances own one contiguous run of p
+//    (CA_GROUP * (N + 1) * K pairs) and one of lh (CA_GROUP * N * K doubles).  All 256 threads walk each in 16-byte stores, thread t the t-th
+//    pair of every 4 KiB pass (a wave's stores cover 1 KiB without gaps), looking the slot's track up again as (instance, stage, slot) moves
+//    on; skipped instances keep their rows, and a pair of lh that straddles a skipped instance is stored as single doubles.
+__global__ void __launch_bounds__(256) usv_guidance_tick(DevPtrs P, GuidancePtrs G, CaTickPtrs W)
+{
+    const DevSpec &S = *P.spec;
+    const int B = S.B, N = S.N, K = S.K;
+    __shared__ double s_d[GUIDANCE_LMAX * CA_GROUP];
+    __shared__ int s_obs[CA_GROUP]; // (the instance's p / lh are streamed this tick)
+    __shared__ unsigned s_nobs;
+    const int t = (int)threadIdx.x;
+    const long b0 = (long)blockIdx.x * CA_GROUP;
+    const int cnt = (int)((long)B - b0 < (long)CA_GROUP ? (long)B - b0 : (long)CA_GROUP);
+    if (t == 0) s_nobs = 0u;
+    if (t < CA_GROUP) s_obs[t] = 0;
+    __syncthreads();
+    if (t < cnt) {
+        const long b = b0 + t;
+        int k = G.k[b];
+        if (k >= G.npts) { // the mission was over before this tick
+            if (W.finish_tick[b] < 0) W.finish_tick[b] = W.tick;
+        } else {
+            double *x0 = const_cast<double *>(P.x0) + b * CA_NX;
+            const double u_cb = ca_fix_u(x0[0]), v_cb = x0[1], nedx = x0[5], nedy = x0[6], psi = x0[7];
+            const int L = W.nworld < GUIDANCE_LMAX ? W.nworld : GUIDANCE_LMAX;
+            const double *w = W.world + b * 3 * W.nworld;
+            if (W.wvel) {
+                ca_select_tracks(w, W.wvel + b * 2 * W.nworld, L, K, psi, nedx, nedy, W.max_radius, s_d + t, CA_GROUP, W.trk_pv + b * 4 * K,
+                                 W.trk_lh + b * K, nullptr);
+                s_obs[t] = 1;
+                atomicAdd(&s_nobs, 1u);
+            } else {
+                ca_select_world(w, L, K, psi, nedx, nedy, W.max_radius, s_d + t, CA_GROUP, const_cast<double *>(P.p) + b * (long)(N + 1) * 2 * K,
+                                const_cast<double *>(P.lh) + b * (long)N * K, nullptr);
+            }
+            const double c = ca_min_clearance(w, L, nedx, nedy, s_d + t, CA_GROUP);
+            if (c < W.min_clear[b]) W.min_clear[b] = c;
+            float pp = G.past_psied[b];
+            int active;
+            double ak, ye;
+            ca_waypoint(G.wp + b * 2 * G.npts, G.npts, nedx, nedy, k, pp, active, ak, ye);
+            G.k[b] = k;
+            G.active[b] = active;
+            if (active) {
+                G.past_psied[b] = pp;
+                G.ak[b] = ak;
+                G.ye[b] = ye;
+                ca_x0(u_cb, v_cb, ye, psi, ak, pp, nedx, nedy, x0);
+            } else if (W.finish_tick[b] < 0) {
+                W.finish_tick[b] = W.tick;
+            }
+        }
+    }
+    __syncthreads();
+    if (s_nobs == 0u || K <= 0) return;
+    const double dt = S.dt;
+    const double2 *pv = reinterpret_cast<const double2 *>(W.trk_pv) + b0 * 2 * K; // [cnt][K][2]: (X, Y), (vX, vY)
+    {
+        double2 *row = reinterpret_cast<double2 *>(const_cast<double *>(P.p)) + b0 * (long)(N + 1) * K;
+        const int per = (N + 1) * K, total = cnt * per; // pairs per instance / of the workgroup
+        int inst = 0, rem = t;                          // j = inst * per + rem
+        while (rem >= per) { rem -= per; inst++; }
+        for (int j = t; j < total; j += 256) {
+            if (s_obs[inst]) {
+                const int k = rem / K, slot = rem - k * K;
+                const double2 q = pv[(inst * K + slot) * 2], v = pv[(inst * K + slot) * 2 + 1];
+                double2 o;
+                o.x = track_predict(q.x, v.x, k, dt);
+                o.y = track_predict(q.y, v.y, k, dt);
+                row[j] = o;
+            }
+            rem += 256;
+            while (rem >= per) { rem -= per; inst++; }
+        }
+    }
+    {
+        double *row = const_cast<double *>(P.lh) + b0 * (long)N * K;
+        const double *tl = W.trk_lh + b0 * K;
+        const int per = N * K, total = cnt * per; // doubles per instance / of the workgroup
+        int inst = 0, rem = 2 * t;                // e = 2 j = inst * per + rem: the pair's first double
+        while (rem >= per) { rem -= per; inst++; }
+        for (int e = 2 * t; e < total; e += 512) {
+            int inst1 = inst, rem1 = rem + 1;     // its second
+            if (rem1 == per) { rem1 = 0; inst1++; }
+            const bool w0 = s_obs[inst] != 0, w1 = e + 1 < total && s_obs[inst1] != 0;
+            const double a = w0 ? tl[inst * K + rem % K] : 0.0, c = w1 ? tl[inst1 * K + rem1 % K] : 0.0;
+            if (w0 && w1) *reinterpret_cast<double2 *>(row + e) = double2{a, c};
+            else if (w0) row[e] = a;
+            else if (w1) row[e + 1] = c;
+            rem += 512;
+            while (rem >= per) { rem -= per; inst++; }
+        }
+    }
+}
+
 // AcadosSimSolver's solve (usvmpc_sim_solve): x, u -> x_next (and S_forw = [Sx | Su] when SENS), sim.hpp
 template <class M, bool SENS>
 __global__ void __launch_bounds__(256) usv_sim(const double *x, const double *u, double *xn, double *S, long B, double T, int steps)
@@ -803,6 +919,17 @@ struct usvmpc_handle {
     size_t bytes;
     std::string err;
     std::vector<void *> allocs;
+    // The guidance front end's device-resident mode (usvmpc_guidance_world; the kernel: usv_guidance_tick): the world list lives on the device
+    // and a prepare without host arrays reads the vessel's state from x0.  A moving world (usvmpc_guidance_world_vel) as the path-following
+    // front end's: velocities per entry, every stage of p / lh written when it is predicted, moved on by usvmpc_advance / _advance_sim.
+    CaTickPtrs gd_tickp = {};   // world, its size and radius, the slot tracks, min_clear, finish_tick (wvel and tick: filled per launch)
+    size_t gd_rworld_cap = 0;   // doubles
+    double *gd_wvel = nullptr;  // [B][nworld][2]
+    size_t gd_wvel_cap = 0;     // doubles
+    bool gd_world_set = false;  // usvmpc_guidance_world has been called
+    bool gd_moving = false;     // velocities are set for the current list
+    bool gd_predict = false;    // ... and the horizon sees them ("static_obstacles" off)
+    int gd_tick = 0;            // device-resident prepares since the last reset
 };
 
 // Kernels::lin / lin_pair: usv_linearize for one and several RK4 steps (MULTI), every MODE
@@ -2138,6 +2265,7 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
     HIP_TRY(h, hipGetLastError());
     if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
     if (h->pf_moving && h->opt.step_on_advance) return usvmpc_pf_world_step(h, h->spec.dt); // (the front end's world likewise)
+    if (h->gd_moving && h->opt.step_on_advance) return usvmpc_guidance_world_step(h, h->spec.dt);
     return 0;
 }
 
@@ -2193,6 +2321,7 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     HIP_TRY(h, hipGetLastError());
     if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
     if (h->pf_moving && h->opt.step_on_advance) return usvmpc_pf_world_step(h, plant->T);
+    if (h->gd_moving && h->opt.step_on_advance) return usvmpc_guidance_world_step(h, plant->T);
     return 0;
 }
 
@@ -2220,6 +2349,7 @@ static const char *option_refused(const usvmpc_handle *h, OptId id, double v)
         if (!h->tracks_pos_set) return "obstacle_tracks: set \"obs_pos\" before switching the option on";
         if (h->pf_ready) return "obstacle_tracks: the path-following front end owns p on this handle";
         if (h->pf_moving) return "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle";
+        if (h->gd_moving) return "obstacle_tracks: the guidance front end's world moves (usvmpc_guidance_world_vel) and owns p on this handle";
         break;
     case OPT_HOST_MIRROR:
         if (v != 0.0 && !h->mirror) return "host_mirror cannot be switched on again";
@@ -2316,7 +2446,15 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
 }
 
 
-// ---- guidance front end (M1 only): see guidance.hpp
+// ---- guidance front end (M1 only): see ca_guidance.hpp (the arithmetic), guidance.hpp (the host-fed kernels), usv_guidance_tick above
+// "static_obstacles" as the front end needs it: off only while its world moves AND is predicted per stage (the tick then writes all stages)
+static int gd_apply_static(usvmpc_handle *h)
+{
+    const bool want = !(h->gd_moving && h->gd_predict);
+    if ((h->spec.p_static != 0) == want) return 0;
+    return apply_option(h, OPT_STATIC_OBSTACLES, want ? 1.0 : 0.0);
+}
+
 static int guidance_alloc(usvmpc_handle *h, int npts)
 {
     if (h->desc.model != USVMPC_MODEL_GUIDANCE_CA1) { h->err = "the guidance front end belongs to usv_model_guidance_ca1"; return USVMPC_E_ARG; }
@@ -2338,6 +2476,8 @@ static int guidance_alloc(usvmpc_handle *h, int npts)
         if (dev_alloc(h, &G.rdes, B, true)) return USVMPC_E_HIP;
         if (dev_alloc(h, &G.speed, B, true)) return USVMPC_E_HIP;
         if (dev_alloc(h, &h->gd_psi, B, true)) return USVMPC_E_HIP;
+        if (dev_alloc(h, &h->gd_tickp.min_clear, B, true)) return USVMPC_E_HIP;
+        if (dev_alloc(h, &h->gd_tickp.finish_tick, B, true)) return USVMPC_E_HIP;
         G.lmax = GUIDANCE_LMAX;
         h->gd_ready = true;
     }
@@ -2363,17 +2503,25 @@ int usvmpc_guidance_reset(usvmpc_handle *h, const double *waypoints, int npts, c
     HIP_TRY(h, hipMemcpyAsync(h->gd_psi, psi, B * sizeof(double), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(usv_guidance_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, G, h->gd_psi, (int)B);
     HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(usv_guidance_mission_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->gd_tickp.min_clear,
+                       h->gd_tickp.finish_tick, (int)B);
+    HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!h->spec.p_static) return apply_option(h, OPT_STATIC_OBSTACLES, 1.0);
-    return 0;
+    h->gd_tick = 0;
+    return gd_apply_static(h);
 }
+
+static int guidance_tick(usvmpc_handle *h);
 
 int usvmpc_guidance_prepare(usvmpc_handle *h, const double *vel_uv, const double *pose, const double *obstacles,
                             const int *n_obstacles, int lmax)
 {
     // n_obstacles == NULL: keep the body-frame lists usvmpc_guidance_sense left on the device
-    if (!h || !vel_uv || !pose || lmax < 0 || lmax > GUIDANCE_LMAX) return USVMPC_E_ARG;
+    if (!h) return USVMPC_E_ARG;
+    if ((vel_uv == nullptr) != (pose == nullptr)) { h->err = "guidance_prepare: give both vel_uv and pose, or neither (device-resident)"; return USVMPC_E_ARG; }
+    if (lmax < 0 || lmax > GUIDANCE_LMAX) return USVMPC_E_ARG;
     if (!h->gd_ready || h->gd.npts < 2) { h->err = "usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
+    if (!vel_uv) return guidance_tick(h);
     HIP_TRY(h, hipSetDevice(h->device));
     {
         const int rcf = mirror_flush(h);
@@ -2392,11 +2540,29 @@ int usvmpc_guidance_prepare(usvmpc_handle *h, const double *vel_uv, const double
                                     (size_t)lmax * 3 * sizeof(double), (size_t)lmax * 3 * sizeof(double), B,
                                     hipMemcpyHostToDevice, h->stream));
     }
-    hipLaunchKernelGGL(usv_guidance_pre, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, h->stream, h->ptrs, G);
+    hipLaunchKernelGGL(usv_guidance_pre, dim3((unsigned)((B + GUIDANCE_BLOCK - 1) / GUIDANCE_BLOCK)), dim3(GUIDANCE_BLOCK), 0, h->stream, h->ptrs, G);
     HIP_TRY(h, hipGetLastError());
     // the copies above read caller memory: it must be reusable when this call returns (pinned buffers make
     // hipMemcpyAsync truly asynchronous)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// the device-resident tick (usvmpc_guidance_prepare with vel_uv and pose NULL): ONE launch on the handle's stream, no synchronisation.  It
+// writes x0, p and lh only - nothing a lineariser reads - so a linearisation made a tick ahead stands (no spec_cancel, unlike usvmpc_pf_prepare).
+static int guidance_tick(usvmpc_handle *h)
+{
+    if (!h->gd_world_set) { h->err = "guidance_prepare: the device-resident tick needs a world list (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rcf = mirror_flush(h);
+    if (rcf) return rcf;
+    CaTickPtrs W = h->gd_tickp;
+    W.wvel = (h->gd_moving && h->gd_predict) ? h->gd_wvel : nullptr; // (held still inside the horizon: the tick of a world at rest)
+    W.tick = h->gd_tick;
+    const size_t B = h->B;
+    hipLaunchKernelGGL(usv_guidance_tick, dim3((unsigned)((B + CA_GROUP - 1) / CA_GROUP)), dim3(256), 0, h->stream, h->ptrs, h->gd, W);
+    HIP_TRY(h, hipGetLastError());
+    h->gd_tick++;
     return 0;
 }
 
@@ -2442,7 +2608,7 @@ int usvmpc_guidance_publish(usvmpc_handle *h, double *heading, double *r_des, do
     if (speed) HIP_TRY(h, hipMemcpyAsync(speed, G.speed, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (ye) HIP_TRY(h, hipMemcpyAsync(ye, G.ye, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (active) HIP_TRY(h, hipMemcpyAsync(active, G.active, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (heading || r_des || speed || ye || active) HIP_TRY(h, hipStreamSynchronize(h->stream)); // (every output NULL: enqueued only)
     return 0;
 }
 
@@ -2454,6 +2620,127 @@ int usvmpc_guidance_state(usvmpc_handle *h, int *wp_index, float *past_psied)
     const size_t B = h->B;
     if (wp_index) HIP_TRY(h, hipMemcpyAsync(wp_index, h->gd.k, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (past_psied) HIP_TRY(h, hipMemcpyAsync(past_psied, h->gd.past_psied, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- the guidance front end's resident world and mission state (include/usvmpc.h)
+static int gd_check(usvmpc_handle *h, const char *who)
+{
+    if (h->desc.model != USVMPC_MODEL_GUIDANCE_CA1) { h->err = std::string(who) + ": the guidance front end belongs to usv_model_guidance_ca1"; return USVMPC_E_ARG; }
+    if (!h->gd_ready) { h->err = std::string(who) + ": usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
+    return 0;
+}
+
+int usvmpc_guidance_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_world");
+    if (rc) return rc;
+    if (n_world < 0 || n_world > GUIDANCE_LMAX) { h->err = "guidance_world: n_world must lie in 0.." + std::to_string(GUIDANCE_LMAX); return USVMPC_E_ARG; }
+    if (n_world > 0 && !world) { h->err = "guidance_world: null world list"; return USVMPC_E_ARG; }
+    if (!(max_radius == max_radius)) { h->err = "guidance_world: max_radius is NaN"; return USVMPC_E_ARG; }
+    const size_t need = (size_t)h->B * (size_t)n_world * 3;
+    for (size_t i = 0; i < need; i++)
+        if (!(world[i] == world[i])) { h->err = "guidance_world: entry " + std::to_string(i) + " is NaN"; return USVMPC_E_ARG; }
+    CaTickPtrs &W = h->gd_tickp;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a tick that reads the old list may be in flight)
+    if (need > h->gd_rworld_cap) {
+        dev_free(h, const_cast<double *>(W.world), h->gd_rworld_cap * sizeof(double));
+        W.world = nullptr; h->gd_rworld_cap = 0;
+        double *d = nullptr;
+        if (dev_alloc(h, &d, need, false)) return USVMPC_E_HIP;
+        W.world = d;
+        h->gd_rworld_cap = need;
+    }
+    if (!W.trk_pv && (dev_alloc(h, &W.trk_pv, (size_t)h->B * (size_t)(h->K ? h->K : 1) * 4, true) ||
+                      dev_alloc(h, &W.trk_lh, (size_t)h->B * (size_t)(h->K ? h->K : 1), true)))
+        return USVMPC_E_HIP;
+    if (need) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(W.world), world, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const bool same = h->gd_world_set && W.nworld == n_world;
+    W.nworld = n_world;
+    W.max_radius = max_radius;
+    h->gd_world_set = true;
+    if (h->gd_moving && !same) { // (velocities belong to a list: another n_world is at rest until its own are given)
+        h->gd_moving = false;
+        return gd_apply_static(h);
+    }
+    return 0;
+}
+
+int usvmpc_guidance_world_vel(usvmpc_handle *h, const double *vel, int predict)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_world_vel");
+    if (rc) return rc;
+    if (!vel) { // back to a world at rest
+        h->gd_moving = false;
+        return gd_apply_static(h);
+    }
+    if (!h->gd_world_set) { h->err = "guidance_world_vel: no world list yet (usvmpc_guidance_world first)"; return USVMPC_E_ARG; }
+    if (h->opt.tracks_on) { h->err = "guidance_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    const size_t need = (size_t)h->B * (size_t)h->gd_tickp.nworld * 2;
+    for (size_t i = 0; i < need; i++)
+        if (vel[i] - vel[i] != 0.0) { h->err = "guidance_world_vel: entry " + std::to_string(i) + " is not finite"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a tick or a world step that reads the old velocities may be in flight)
+    if (need > h->gd_wvel_cap || !h->gd_wvel) { // (an empty list moves too: a non-null pointer is what tells the tick so)
+        dev_free(h, h->gd_wvel, h->gd_wvel_cap * sizeof(double));
+        h->gd_wvel = nullptr; h->gd_wvel_cap = 0;
+        if (dev_alloc(h, &h->gd_wvel, need, false)) return USVMPC_E_HIP;
+        h->gd_wvel_cap = need;
+    }
+    if (need) HIP_TRY(h, hipMemcpyAsync(h->gd_wvel, vel, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->gd_moving = true;
+    h->gd_predict = predict != 0;
+    return gd_apply_static(h);
+}
+
+int usvmpc_guidance_world_step(usvmpc_handle *h, double T)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_world_step");
+    if (rc) return rc;
+    if (!h->gd_moving) { h->err = "guidance_world_step: the world is at rest (usvmpc_guidance_world_vel first)"; return USVMPC_E_ARG; }
+    if (T - T != 0.0) { h->err = "guidance_world_step: T is not finite"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const long n = (long)h->B * h->gd_tickp.nworld;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(usv_pf_world_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, const_cast<double *>(h->gd_tickp.world),
+                       (const double *)h->gd_wvel, n, T); // (one kernel for both front ends' worlds: pos += T vel per entry, track_step)
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int usvmpc_guidance_world_read(usvmpc_handle *h, double *world, double *vel)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_world_read");
+    if (rc) return rc;
+    if (!h->gd_world_set) { h->err = "guidance_world_read: no world list yet (usvmpc_guidance_world first)"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->B * (size_t)h->gd_tickp.nworld;
+    if (world && n) HIP_TRY(h, hipMemcpyAsync(world, h->gd_tickp.world, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (vel && n && h->gd_moving) HIP_TRY(h, hipMemcpyAsync(vel, h->gd_wvel, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (vel && !h->gd_moving) std::fill(vel, vel + n * 2, 0.0); // (a world at rest)
+    return 0;
+}
+
+int usvmpc_guidance_mission_state(usvmpc_handle *h, int *wp_index, float *past_psied, int *finish_tick, double *min_clearance)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_mission_state");
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t B = h->B;
+    if (wp_index) HIP_TRY(h, hipMemcpyAsync(wp_index, h->gd.k, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (past_psied) HIP_TRY(h, hipMemcpyAsync(past_psied, h->gd.past_psied, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (finish_tick) HIP_TRY(h, hipMemcpyAsync(finish_tick, h->gd_tickp.finish_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (min_clearance) HIP_TRY(h, hipMemcpyAsync(min_clearance, h->gd_tickp.min_clear, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }

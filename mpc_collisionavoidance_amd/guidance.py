@@ -1,7 +1,11 @@
 """Batched counterpart of the reference's obstacle-avoidance ROS node around the solver
 (class NMPC, /root/reference/catkin_ws/src/nmpc_ca/src/nmpc_guidance_ca1.cpp): waypoint manager,
 LiDAR obstacle selection / body->NED transform, x0 assembly, and the published set-points.  All
-arithmetic runs on the device (csrc/guidance.hpp); this class only moves arrays."""
+arithmetic runs on the device (csrc/ca_guidance.hpp); this class only moves arrays.  Two ways to drive it:
+
+    host-fed          sense(pose, world) -> prepare(vel_uv, pose) -> solve -> publish()       (the ROS nodes' callbacks)
+    device-resident   set_world(world) once; prepare() -> solve_async -> publish(fetch=False) -> advance / advance_sim
+                      the vessel's state is read from the solver's own x0; no host array, no synchronisation"""
 import ctypes as C
 
 import numpy as np
@@ -44,9 +48,39 @@ class GuidanceFrontEnd:
                                                       n.ctypes.data_as(_capi._ip) if fetch else None))
         return (o, n) if fetch else None
 
-    def prepare(self, vel_uv, pose, obstacles=None, n_obstacles=None):
+    def set_world(self, world, max_radius=100.0, vel=None, predict=True):
+        """The obstacle field (X, Y, R) in NED for the device-resident mode: [B, L, 3] or [L, 3] for all, L <= 64; uploaded once.
+        vel: [B, L, 2] or [L, 2] (vX, vY) in NED m/s - the world moves: advance / advance_sim move it along (option
+        "obstacle_step_on_advance") and, with predict, prepare() writes the predicted obstacle set of every stage; predict=False holds the
+        world still inside the horizon (stage 0 only).  None: a world at rest."""
+        w = _as_world(world, self.B)
+        v = None if vel is None else _as_world_vel(vel, self.B, w.shape[1])
+        self.s._check(self._lib.usvmpc_guidance_world(self.s._h, w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius)))
+        self.s._check(self._lib.usvmpc_guidance_world_vel(self.s._h, None if v is None else v.ctypes.data_as(_capi._dp), 1 if predict else 0))
+        self._L = w.shape[1]
+
+    def step_world(self, T):
+        """The world moves on by T seconds (enqueued; a moving world only)."""
+        self.s._check(self._lib.usvmpc_guidance_world_step(self.s._h, float(T)))
+
+    def world(self):
+        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest."""
+        L = getattr(self, "_L", None)
+        if L is None:
+            raise Exception("world: no world list yet (set_world first)")
+        w, v = np.zeros((self.B, L, 3)), np.zeros((self.B, L, 2))
+        self.s._check(self._lib.usvmpc_guidance_world_read(self.s._h, w.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp)))
+        return w, v
+
+    def prepare(self, vel_uv=None, pose=None, obstacles=None, n_obstacles=None):
         """vel_uv [B,2], pose [B,3] (nedx, nedy, psi), obstacles [B,L,3] body (x, y, R), n_obstacles [B];
-        obstacles=None: the lists sense() left on the device."""
+        obstacles=None: the lists sense() left on the device.  vel_uv and pose both None: device-resident - the vessel's state is read
+        from the solver's own x0 and the obstacles from the world of set_world(); enqueues and returns."""
+        if (vel_uv is None) != (pose is None):
+            raise Exception("prepare: give both vel_uv and pose, or neither")
+        if vel_uv is None:
+            self.s._check(self._lib.usvmpc_guidance_prepare(self.s._h, None, None, None, None, 0))
+            return
         v = np.ascontiguousarray(vel_uv, dtype=np.float64).reshape(self.B, 2)
         p = np.ascontiguousarray(pose, dtype=np.float64).reshape(self.B, 3)
         if obstacles is None:
@@ -58,14 +92,26 @@ class GuidanceFrontEnd:
         self.s._check(self._lib.usvmpc_guidance_prepare(self.s._h, v.ctypes.data_as(_capi._dp), p.ctypes.data_as(_capi._dp),
                                                         o.ctypes.data_as(_capi._dp), n.ctypes.data_as(_capi._ip), o.shape[1]))
 
-    def publish(self):
-        """After solve(): dict(heading, r, speed, ye, active) - the node's published set-points."""
+    def publish(self, fetch=True):
+        """After solve(): dict(heading, r, speed, ye, active) - the node's published set-points.  fetch=False: enqueue only, returns None."""
+        if not fetch:
+            self.s._check(self._lib.usvmpc_guidance_publish(self.s._h, None, None, None, None, None))
+            return None
         h, r, sp, ye = (np.zeros(self.B) for _ in range(4))
         act = np.zeros(self.B, dtype=np.int32)
         self.s._check(self._lib.usvmpc_guidance_publish(self.s._h, h.ctypes.data_as(_capi._dp), r.ctypes.data_as(_capi._dp),
                                                         sp.ctypes.data_as(_capi._dp), ye.ctypes.data_as(_capi._dp),
                                                         act.ctypes.data_as(_capi._ip)))
         return dict(heading=h, r=r, speed=sp, ye=ye, active=act)
+
+    def mission_state(self):
+        """dict(wp_index [B], past_psied [B], finish_tick [B] (-1: not finished), min_clearance [B]) of the device-resident mode."""
+        k, ft = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        pp = np.zeros(self.B, dtype=np.float32)
+        mc = np.zeros(self.B)
+        self.s._check(self._lib.usvmpc_guidance_mission_state(self.s._h, k.ctypes.data_as(_capi._ip), pp.ctypes.data_as(C.POINTER(C.c_float)),
+                                                              ft.ctypes.data_as(_capi._ip), mc.ctypes.data_as(_capi._dp)))
+        return dict(wp_index=k, past_psied=pp, finish_tick=ft, min_clearance=mc)
 
     def state(self):
         k = np.zeros(self.B, dtype=np.int32)

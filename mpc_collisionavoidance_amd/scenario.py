@@ -355,3 +355,34 @@ def predict_world(world, vel, chosen, N, dt, margin=PF_MISSION_OCP["margin"]):
     kdt = (np.arange(N + 1, dtype=float) * dt)[None, :, None, None]
     p = (pos[:, None] + kdt * v[:, None]).reshape(B, N + 1, 2 * K)
     return p, np.tile(lh0[:, None], (1, N, 1))
+
+
+# ---- missions of the obstacle-avoidance guidance model (usv_model_guidance_ca1; examples/scenario_sweep.py)
+CA_MISSION_WAYPOINTS = np.array([[4.0, -5.0], [4.0, 25.0], [10.0, 30.0]])
+CA_DRIFT = 0.3   # m/s: the survey's range for moving obstacles
+
+
+def make_ca_worlds(B, L, rng):
+    """L obstacles per scenario along the first leg (4,-5) -> (4,25): one every 25/L metres (jittered), up to
+    1.5 m off the path to either side, radius 0.3..0.8 m - the reference scenario's density
+    (usv_guidance_ca1/main.py: four obstacles on a 30 m leg), randomised."""
+    y = -1.0 + (np.arange(L)[None, :] + rng.uniform(0.2, 0.8, (B, L))) * (25.0 / L)
+    x = 4.0 + rng.uniform(-1.5, 1.5, (B, L))
+    r = rng.uniform(0.3, 0.8, (B, L))
+    return np.stack([x, y, r], axis=2)
+
+
+def make_ca_missions(B, L, seed=0, moving=False):
+    """B LiDAR scenarios drawn from numpy.random.default_rng(seed): dict(waypoints [3,2], pose [B,3] = (nedx, nedy, psi) - the vessel starts
+    at (4 +- 1, -5), heading pi/2 +- 0.3 -, vel [B,2] = (0.7, 0), world [B,L,3] = (X, Y, R) of make_ca_worlds).
+    moving=True adds world_vel [B,L,2]: every obstacle crosses the first leg (which runs along Y) at vX ~ U(-CA_DRIFT, CA_DRIFT), vY = 0,
+    drawn from a stream of its own, default_rng([seed, 1]): every other field is the same bits with either value of `moving`."""
+    rng = np.random.default_rng(seed)
+    world = make_ca_worlds(B, L, rng)
+    pose = np.column_stack([4.0 + rng.uniform(-1, 1, B), np.full(B, -5.0), np.full(B, np.pi / 2) + rng.uniform(-0.3, 0.3, B)])
+    vel = np.column_stack([np.full(B, 0.7), np.zeros(B)])
+    out = dict(waypoints=CA_MISSION_WAYPOINTS.copy(), pose=pose, vel=vel, world=world)
+    if moving:
+        rv = np.random.default_rng([seed, 1])
+        out["world_vel"] = np.stack([rv.uniform(-CA_DRIFT, CA_DRIFT, (B, L)), np.zeros((B, L))], axis=2)
+    return out

@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""What a closed-loop tick of the guidance front end (usv_model_guidance_ca1, N = 100, K = 8, the scenarios of scenario.make_ca_missions)
+costs, three ways (needs an MI355X):
+
+  hostfed   sense(pose, world) -> prepare(vel, pose) -> solve -> publish -> x1 = get("x", 1) -> numpy clearance: the loop of
+            examples/scenario_sweep.py as it stands without --resident (five synchronisations and the world list through the host per tick)
+  resident  prepare() -> solve_async -> publish(fetch=False) -> advance: the device-resident loop over a world at rest
+  moving    the same over a moving world that is predicted: prepare() writes p / lh of every stage
+  held      the moving world held still inside the horizon (predict = 0): stage 0 only
+
+Per run one JSON line: the median tick (a host clock around the loop's body, ending in a synchronisation for the resident modes), and for the
+resident modes the HIP-event time of the prepare's kernel (usv_guidance_tick: events on the solver's stream either side of it), the bytes a
+predicted tick streams divided by that time, usvmpc_pipeline_stats, and how many missions kept their clearance.  --runs alternating runs.
+
+--root DIR imports the package from another checkout (mode hostfed only needs calls every revision has): that is how the record's
+host-fed figures were taken at the commit before the resident mode existed.
+
+    python tools/guidance_mission_probe.py --batch 8192
+    python tools/guidance_mission_probe.py --batch 65536 --modes resident,moving,held
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def missions(B, L, seed):
+    """scenario.make_ca_missions, restated so that --root may name a revision that has no such generator (the same draws)"""
+    rng = np.random.default_rng(seed)
+    y = -1.0 + (np.arange(L)[None, :] + rng.uniform(0.2, 0.8, (B, L))) * (25.0 / L)
+    x = 4.0 + rng.uniform(-1.5, 1.5, (B, L))
+    r = rng.uniform(0.3, 0.8, (B, L))
+    world = np.stack([x, y, r], axis=2)
+    pose = np.column_stack([4.0 + rng.uniform(-1, 1, B), np.full(B, -5.0), np.full(B, np.pi / 2) + rng.uniform(-0.3, 0.3, B)])
+    rv = np.random.default_rng([seed, 1])
+    wvel = np.stack([rv.uniform(-0.3, 0.3, (B, L)), np.zeros((B, L))], axis=2)
+    return dict(waypoints=np.array([[4.0, -5.0], [4.0, 25.0], [10.0, 30.0]]), pose=pose, vel=np.column_stack([np.full(B, 0.7), np.zeros(B)]),
+                world=world, world_vel=wvel)
+
+
+def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0):
+    import torch
+    from mpc_collisionavoidance_amd import BatchOcpSolver, usv_models
+    from mpc_collisionavoidance_amd.guidance import GuidanceFrontEnd
+    dt = 0.05
+    m = missions(B, L, seed)
+    s = BatchOcpSolver(usv_models.make_ocp("usv_model_guidance_ca1", N * dt, N, K), B)
+    fe = GuidanceFrontEnd(s)
+    world, pose, vel = m["world"], m["pose"], m["vel"]
+    fe.reset(m["waypoints"], pose[:, 2])
+    times, tick_ms = [], []
+    out = dict(mode=mode, batch=B, N=N, K=K, L=L, ticks=ticks, warmup=warmup)
+    if mode == "hostfed":
+        min_clear = np.full(B, np.inf)
+        for t in range(warmup + ticks):
+            t0 = time.perf_counter()
+            fe.sense(pose, world, max_radius=100.0)
+            fe.prepare(vel, pose)
+            s.solve()
+            fe.publish()
+            x1 = s.get("x", 1)
+            vel, pose = x1[:, 0:2].copy(), x1[:, 5:8].copy()
+            d = np.sqrt((pose[:, None, 0] - world[:, :, 0]) ** 2 + (pose[:, None, 1] - world[:, :, 1]) ** 2) - (world[:, :, 2] + 0.5)
+            min_clear = np.minimum(min_clear, d.min(axis=1))
+            times.append((time.perf_counter() - t0) * 1e3)
+    else:
+        x0 = np.zeros((B, 8))
+        x0[:, 0:2], x0[:, 5:8] = vel, pose
+        s.set("x0", 0, x0)
+        fe.set_world(world, max_radius=100.0, vel=m["world_vel"] if mode in ("moving", "held") else None, predict=mode != "held")
+        s.sync()
+        for t in range(warmup + ticks):
+            t0 = time.perf_counter()
+            fe.prepare()
+            s.solve_async()
+            fe.publish(fetch=False)
+            s.advance(0.0, t)
+            s.sync()
+            times.append((time.perf_counter() - t0) * 1e3)
+        lin, qp = s.kernel_ms(ticks)
+        used, discarded = s.pipeline_stats()
+        # the kernel's own time, in a pass of its own AFTER the timed ticks: events need the solver on a stream of torch's, and a handle on a
+        # caller's stream no longer pipelines its lineariser (usvmpc_set_stream)
+        stream = torch.cuda.Stream()
+        s.set_stream(stream.cuda_stream)
+        for t in range(warmup + ticks):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fe.prepare()
+            e1.record(stream)
+            s.solve_async()
+            fe.publish(fetch=False)
+            s.advance(0.0, warmup + ticks + t)
+            s.sync()
+            tick_ms.append(e0.elapsed_time(e1))
+        st = fe.mission_state()
+        min_clear = st["min_clearance"]
+        k_ms = statistics.median(tick_ms[warmup:])
+        nbytes = B * ((N + 1) * 2 * K + N * K) * 8 if mode == "moving" else 0
+        out.update(guidance_tick_ms_median=k_ms, guidance_tick_ms_min=min(tick_ms[warmup:]), streamed_bytes=nbytes,
+                   stream_TB_per_s=(nbytes / (k_ms * 1e-3) / 1e12) if nbytes else 0.0, pipelined_linearisations_used=int(used),
+                   pipelined_linearisations_discarded=int(discarded))
+    timed = times[warmup:]
+    if mode == "hostfed":
+        lin, qp = s.kernel_ms(ticks)
+    out.update(tick_ms_median=statistics.median(timed), tick_ms_min=min(timed), tick_ms_max=max(timed), linearize_ms_median=float(np.median(lin)),
+               qp_ms_median=float(np.median(qp)), failed_last_tick=int(s.fail_counts(1)[0]),
+               missions_clear_of_keepout=int((min_clear > 0.0).sum()), min_clearance_worst=float(min_clear.min()))
+    s.close()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--ticks", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--modes", default="hostfed,resident,moving")
+    ap.add_argument("--root", default=HERE, help="the checkout whose package is imported (default: this one)")
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file as well (the record: profiles/guidance_mission_probe.txt)")
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    import torch  # noqa: F401  (before the solver library: one HIP runtime for both)
+    for r in range(a.runs):
+        for mode in a.modes.split(","):
+            line = run(mode, a.batch, a.ticks, a.warmup)
+            line["run"] = r
+            line["root"] = "this tree" if os.path.abspath(a.root) == HERE else "another checkout"
+            print(json.dumps(line), flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
