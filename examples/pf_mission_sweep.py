@@ -13,7 +13,11 @@ With --moving the obstacles drift at constant velocities (scenario.make_pf_missi
 obstacle set of every stage and advance() moves the world along - the tick is the same four calls.  --no-predict holds the moving world
 still inside the horizon (option "pf_predict" 0), the baseline that shows what prediction buys.
 
-    python examples/pf_mission_sweep.py --batch 8192 --ticks 560 [--plant-steps 10] [--moving [--no-predict]]
+With --log-every n the loop also keeps its closed-loop trajectory - the reference's simX and its printed statistics (scripts/usv_pf_ca/
+main.py:153-176, 199-207) - without a host array or a synchronisation in the tick: start_log() records (nedx, nedy, psi) of every n-th tick on the
+device and sums |e| and e e of psi - ak, u - 0.7 and ye over the ticks after 400 (every tick of a shorter run); read once at the end.
+
+    python examples/pf_mission_sweep.py --batch 8192 --ticks 560 [--plant-steps 10] [--moving [--no-predict]] [--log-every 4]
 """
 import argparse
 import os
@@ -28,9 +32,11 @@ from mpc_collisionavoidance_amd import AcadosSim, BatchOcpSolver, BatchSimSolver
 from mpc_collisionavoidance_amd.guidance import PathFollowingFrontEnd  # noqa: E402
 
 RING = 64   # solves whose failure counts the library keeps
+ERRORS = (("psi - ak", (0, 9)), ("u - u_ref", (3, 0.7)), ("ye", (6, 0.0)))   # main.py's three statistics as (state, state | constant)
+ERRORS_FIRST = 401                                                          # ... over the ticks after 400
 
 
-def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False, predict=True):
+def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False, predict=True, log_every=None):
     cfg = scenario.PF_MISSION_OCP
     dt = cfg["dt"]
     m = scenario.make_pf_missions(B, seed, moving=moving)
@@ -54,6 +60,9 @@ def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False
     npts = m["waypoints"].shape[1]
     fails = np.zeros(ticks, dtype=int)
     active0 = None
+    if log_every:
+        s.start_log(-(-ticks // log_every), every=log_every, states=[0, 10, 11], u=False, status=False, errors=[c for _, c in ERRORS],
+                    errors_first=ERRORS_FIRST if ticks > ERRORS_FIRST else 0)
     s.sync()
     t0 = time.perf_counter()
     for i in range(ticks):
@@ -81,6 +90,17 @@ def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False
     res = dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, finish_tick=st["finish_tick"], min_clearance=st["min_clearance"],
                waypoint_index=k, switches=k - 1, new_segments=new_segments, active_at_tick_0=int(active0.sum()), yref_writes=st["yref_writes"],
                failures_per_tick=fails, final_status=s.get_int("status"), final_pose=s.get("x0", 0)[:, [10, 11, 0]])
+    if log_every:
+        log, err = s.read_log(), s.log_errors()
+        # beside final_pose, in its order (nedx, nedy, psi): [B][records][3] and the tick of each record
+        res.update(log_pose=log["x"][:, :, [1, 2, 0]].copy(), log_tick=log["tick"], error_count=err["count"],
+                   mean_abs_error=err["sum_abs"] / max(err["count"], 1), mean_sq_error=err["sum_sq"] / max(err["count"], 1))
+    if not quiet and log_every:
+        print("logged %d records of (nedx, nedy, psi) per mission, one every %d ticks; errors over %d ticks:"
+              % (len(res["log_tick"]), log_every, res["error_count"]))
+        for c, (name, _) in enumerate(ERRORS):
+            print("  %-9s mean absolute error %.6f, mean square error %.6f (means over the %d missions)"
+                  % (name, res["mean_abs_error"][:, c].mean(), res["mean_sq_error"][:, c].mean(), B))
     if not quiet:
         fin = st["finish_tick"] >= 0
         print("%d missions x %d ticks in %.2f s (%.1f ticks/s, %.0f mission-ticks/s)" % (B, ticks, el, ticks / el, B * ticks / el))
@@ -108,5 +128,7 @@ if __name__ == "__main__":
                     help="integrate the plant in this many RK4 steps per tick (default: the plant is the controller's prediction x_1)")
     ap.add_argument("--moving", action="store_true", help="the obstacles drift at constant velocities")
     ap.add_argument("--no-predict", action="store_true", help="with --moving: the world is held still inside the horizon (option \"pf_predict\" 0)")
+    ap.add_argument("--log-every", type=int, default=None,
+                    help="keep (nedx, nedy, psi) of every n-th tick and main.py's error statistics on the device (start_log)")
     a = ap.parse_args()
-    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps, moving=a.moving, predict=not a.no_predict)
+    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps, moving=a.moving, predict=not a.no_predict, log_every=a.log_every)

@@ -7,7 +7,12 @@ pose / velocity are read from x_1 of the solution.  With --plant-steps K the pla
 (BatchSimSolver: the same model over the same 0.05 s in K RK4 steps, from x_0 under u_0), i.e. a plant that differs from
 the controller's one-step prediction by its discretisation error.
 
-    python examples/scenario_sweep.py --batch 4096 --ticks 300 [--plant-steps 10]
+With --log-every n the device-resident loop also keeps its closed-loop trajectory (the reference's simX: scripts/usv_guidance_ca1/
+main.py:147-148) without a host array in the tick: start_log() records (xned, yned, psi) of every n-th tick on the device and sums |e| and
+e e of this model's tracking errors, the states ye and chie (scripts/usv_pf_ca/main.py prints the same statistics for its own); read once
+at the end.
+
+    python examples/scenario_sweep.py --batch 4096 --ticks 300 [--plant-steps 10] [--resident [--log-every 4]]
 """
 import argparse
 import os
@@ -27,7 +32,10 @@ def make_worlds(B, L, rng):
     return scenario.make_ca_worlds(B, L, rng)
 
 
-def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None, resident=False, moving=False, predict=True):
+ERRORS = (("ye", (2, 0.0)), ("chie", (3, 0.0)))   # the tracking errors of usv_model_guidance_ca1 are states: (state, constant)
+
+
+def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None, resident=False, moving=False, predict=True, log_every=None):
     """resident=False: the host-fed loop (the ROS nodes' callbacks, arrays through the host every tick).  resident=True: the whole mission
     on the device - the world is uploaded once, a tick is prepare() -> solve_async -> publish(fetch=False) -> advance, and the host reads
     once at the end.  moving=True (resident only): the obstacles cross the first leg and the horizon sees where they will be (predict)."""
@@ -46,8 +54,10 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
     fe.reset(wps, pose[:, 2])
     if moving and not resident:
         raise Exception("a moving world needs the device-resident loop (resident=True)")
+    if log_every and not resident:
+        raise Exception("the log replaces the host arrays of the device-resident loop (resident=True); the host-fed loop has them anyway")
     if resident:
-        res = _run_resident(s, fe, plant, m, ticks, predict)
+        res = _run_resident(s, fe, plant, m, ticks, predict, log_every)
     else:
         min_clear = np.full(B, np.inf)
         bad = np.zeros(B, dtype=bool)
@@ -79,13 +89,19 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
         print("minimum clearance to the keep-out circle (R + 0.5 m): worst %.3f m, 1st percentile %.3f m, median %.3f m"
               % (min_clear.min(), np.percentile(min_clear, 1), np.median(min_clear)))
         print("scenarios with a solver failure: %d; reached the second leg: %d" % (bad.sum(), (k >= 2).sum()))
+        if log_every:
+            print("logged %d records of (xned, yned, psi) per scenario, one every %d ticks; errors over %d ticks:"
+                  % (len(res["log_tick"]), log_every, res["error_count"]))
+            for c, (name, _) in enumerate(ERRORS):
+                print("  %-5s mean absolute error %.6f, mean square error %.6f (means over the %d scenarios)"
+                      % (name, res["mean_abs_error"][:, c].mean(), res["mean_sq_error"][:, c].mean(), B))
     s.close()
     if plant is not None:
         plant.close()
     return res
 
 
-def _run_resident(s, fe, plant, m, ticks, predict):
+def _run_resident(s, fe, plant, m, ticks, predict, log_every=None):
     """The device-resident loop.  min_clearance is the front end's: the minimum over the poses the ticks were PREPARED at (the start pose
     included, the pose after the last tick not), where the host-fed loop takes the poses after each tick.
     solver_failures: an instance's status after the last tick, missions that are over left out as in the host-fed loop; the ticks before
@@ -97,6 +113,8 @@ def _run_resident(s, fe, plant, m, ticks, predict):
     s.set("x0", 0, x0)
     fe.set_world(m["world"], max_radius=100.0, vel=m.get("world_vel"), predict=predict)
     fails = []
+    if log_every:
+        s.start_log(-(-ticks // log_every), every=log_every, states=[5, 6, 7], u=False, status=False, errors=[c for _, c in ERRORS])
     t0 = time.perf_counter()
     for i in range(ticks):
         fe.prepare()                                 # sensor + callbacks + waypoint manager, from the solver's own x0
@@ -117,8 +135,14 @@ def _run_resident(s, fe, plant, m, ticks, predict):
     audited = min(ticks - 1, int(st["finish_tick"][over].min())) if over.any() else ticks - 1
     if ticks and fails[:max(audited, 0)].any():
         bad[:] = True
-    return dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, min_clearance=st["min_clearance"], solver_failures=bad,
-                waypoint_index=st["wp_index"], final_pose=s.get("x0", 0)[:, 5:8].copy(), finish_tick=st["finish_tick"], fail_counts=fails)
+    res = dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, min_clearance=st["min_clearance"], solver_failures=bad,
+               waypoint_index=st["wp_index"], final_pose=s.get("x0", 0)[:, 5:8].copy(), finish_tick=st["finish_tick"], fail_counts=fails)
+    if log_every:
+        log, err = s.read_log(), s.log_errors()
+        # beside final_pose, in its order (xned, yned, psi): [B][records][3] and the tick of each record
+        res.update(log_pose=log["x"].copy(), log_tick=log["tick"], error_count=err["count"],
+                   mean_abs_error=err["sum_abs"] / max(err["count"], 1), mean_sq_error=err["sum_sq"] / max(err["count"], 1))
+    return res
 
 
 if __name__ == "__main__":
@@ -131,5 +155,8 @@ if __name__ == "__main__":
     ap.add_argument("--resident", action="store_true", help="keep the whole mission on the device (no host array, no synchronisation per tick)")
     ap.add_argument("--moving", action="store_true", help="the obstacles cross the first leg at up to 0.3 m/s (device-resident loop)")
     ap.add_argument("--no-predict", action="store_true", help="with --moving: hold the world still inside the horizon")
+    ap.add_argument("--log-every", type=int, default=None,
+                    help="device-resident loop: keep (xned, yned, psi) of every n-th tick and the ye / chie error statistics on the device")
     a = ap.parse_args()
-    run(a.batch, a.ticks, a.horizon, plant_steps=a.plant_steps, resident=a.resident or a.moving, moving=a.moving, predict=not a.no_predict)
+    run(a.batch, a.ticks, a.horizon, plant_steps=a.plant_steps, resident=a.resident or a.moving or bool(a.log_every), moving=a.moving,
+        predict=not a.no_predict, log_every=a.log_every)

@@ -487,6 +487,50 @@ const char *usvmpc_sim_last_error(usvmpc_sim *s);
  * solver's stream.  The plant must come from this library and have the solver's model, nx and device (else USVMPC_E_ARG); only its
  * T and num_steps are read - its buffers are not touched. */
 int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, unsigned long long seed);
+/* ---- Closed-loop log: the trajectory a closed loop leaves behind (the reference's simX[i] = get(0, "x"), simU[i] = get(0, "u") and its
+ * tracking-error statistics: scripts/usv_pf_ca/main.py:153-176), kept on the device so that a device-resident loop stays free of host
+ * arrays and synchronisation (the schedule and layout: csrc/log_plan.hpp; the arithmetic: csrc/closed_loop_log.hpp; the kernel:
+ * usv_log_record).  A HAND-OVER is a call of usvmpc_advance or usvmpc_advance_sim; hand-overs are counted from 0 since usvmpc_log_start.
+ * While a log runs each of them first enqueues usv_log_record on the handle's stream, AHEAD of its own kernel; a handle without a log
+ * launches exactly what it did before.
+ *   A RECORD is made at hand-over i when i >= first, (i - first) % every == 0 and fewer than `capacity` records exist; with the buffer
+ *   full `missed` counts it and nothing is stored (no ring).  It holds the values at the moment the hand-over was called, before its kernel
+ *   overwrites x0: the selected states of x0 as the solve saw them, u of stage 0, and status | qp_iter << 8 of the last solve.
+ *   ERROR SUMS: at every hand-over i >= err_first, recorded or not, each (instance, channel c) takes e = x0[err_a[c]] - (err_b[c] >= 0 ?
+ *   x0[err_b[c]] : err_c[c]) into sum_abs += |e| and sum_sq += e e - each operation rounded on its own, in tick order: the bits a
+ *   sequential numpy loop makes.  Means are the caller's division by `count`.
+ *   log_start : allocates the buffers, zeroes sums and counters.  USVMPC_E_ARG with a message, nothing changed: a log already runs
+ *               ("usvmpc_log_stop first"); capacity < 1, every < 1, first < 0; a state_mask bit >= nx; n_err outside 0 .. 4; err_a or err_b
+ *               >= nx, err_a < 0; a non-finite err_c that is used; a descriptor that records nothing; sizes that overflow 64 bits.  A failed
+ *               allocation: USVMPC_E_HIP, nothing changed.
+ *   log_stop  : frees the buffers (usvmpc_destroy does too); usvmpc_device_bytes includes them while the log runs.
+ *   log_info  : records made, hand-overs counted, hand-overs missed, states per record; any output may be NULL.
+ *   log_read  : channel "x", "u" or "status" -> out [nrec][nb][n], tick-major, for records rec0 .. rec0 + nrec - 1 and instances b0 ..
+ *               b0 + nb - 1; n = nsel, nu or 1, FP64 or int32; `bytes` must be exactly that size; records not made yet, instances outside the
+ *               batch and a channel that is not recorded are refused.  One 2-D copy; synchronises the stream.
+ *   log_errors: sum_abs, sum_sq [B][n_err], count = hand-overs that entered the sums; any may be NULL; synchronises the stream.
+ *   log_device_ptr: "x" [capacity][B][nsel], "u" [capacity][B][nu], "status" [capacity][B], "sum_abs", "sum_sq" [B][n_err] on the device.
+ * The record kernel reads x0, u, status and qp_iter and writes log memory only: it is no caller write - the pipelined lineariser's work
+ * made a tick ahead stands, and log_device_ptr, which exposes log memory only, leaves it alone as well.
+ * Not provided: a ring mode; the front ends' published values and waypoint index (positions, ak and the thrusts are states); a cost
+ * channel.  A loop around usvmpc_solve_sqp is logged like any other: whatever the solve, the hand-over records. */
+typedef struct usvmpc_log_desc {
+    int capacity;        /* records kept, >= 1 */
+    int every;           /* one record every `every`-th hand-over, >= 1 */
+    int first;           /* first hand-over recorded, counted from 0 since usvmpc_log_start, >= 0 */
+    unsigned state_mask; /* bit j: state j of x0 is recorded (bits >= nx refused); 0: no state channel */
+    int record_u;        /* 1: u of stage 0 */
+    int record_status;   /* 1: one int32 per instance = status | qp_iter << 8 */
+    int n_err;           /* 0 .. 4 error channels: e = x0[a] - (b >= 0 ? x0[b] : c) */
+    int err_a[4], err_b[4]; double err_c[4];
+    int err_first;       /* first hand-over that enters the sums (main.py: 401) */
+} usvmpc_log_desc;
+int usvmpc_log_start(usvmpc_handle *h, const usvmpc_log_desc *d);
+int usvmpc_log_stop(usvmpc_handle *h);
+int usvmpc_log_info(usvmpc_handle *h, int *records, long long *handovers, long long *missed, int *nsel);
+int usvmpc_log_read(usvmpc_handle *h, const char *channel, int rec0, int nrec, int b0, int nb, void *out, size_t bytes);
+int usvmpc_log_errors(usvmpc_handle *h, double *sum_abs, double *sum_sq, long long *count);
+int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr);
 /* bytes of device memory held by the handle */
 size_t usvmpc_device_bytes(usvmpc_handle *h);
 const char *usvmpc_last_error(usvmpc_handle *h);

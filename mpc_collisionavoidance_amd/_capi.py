@@ -71,7 +71,15 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state",
            "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read",
            "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
-           "usvmpc_guidance_mission_state"]
+           "usvmpc_guidance_mission_state",
+           "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr"]
+
+
+class LogDesc(C.Structure):
+    """usvmpc_log_desc"""
+    _fields_ = [("capacity", C.c_int), ("every", C.c_int), ("first", C.c_int), ("state_mask", C.c_uint),
+                ("record_u", C.c_int), ("record_status", C.c_int), ("n_err", C.c_int),
+                ("err_a", C.c_int * 4), ("err_b", C.c_int * 4), ("err_c", C.c_double * 4), ("err_first", C.c_int)]
 
 
 _libs = {}
@@ -158,6 +166,13 @@ def load(path):
     L.usvmpc_sim_last_error.restype = C.c_char_p
     L.usvmpc_advance_sim.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_ulonglong]
     L.usvmpc_obstacles_step.argtypes = [C.c_void_p, C.c_double]
+    _llp = C.POINTER(C.c_longlong)
+    L.usvmpc_log_start.argtypes = [C.c_void_p, C.POINTER(LogDesc)]
+    L.usvmpc_log_stop.argtypes = [C.c_void_p]
+    L.usvmpc_log_info.argtypes = [C.c_void_p, _ip, _llp, _llp, _ip]
+    L.usvmpc_log_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    L.usvmpc_log_errors.argtypes = [C.c_void_p, _dp, _dp, _llp]
+    L.usvmpc_log_device_ptr.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
     L.usvmpc_device_bytes.argtypes = [C.c_void_p]
     L.usvmpc_device_bytes.restype = C.c_size_t
     L.usvmpc_last_error.argtypes = [C.c_void_p]

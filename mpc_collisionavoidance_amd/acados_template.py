@@ -451,11 +451,103 @@ class BatchOcpSolver:
     def set_stream(self, stream_ptr):
         self._check(self._lib.usvmpc_set_stream(self._h, C.c_void_p(stream_ptr)))
 
+    # -- closed-loop log (include/usvmpc.h, "Closed-loop log"): simX / simU / status and error sums kept on the device
+    def start_log(self, capacity, every=1, first=0, states=None, u=True, status=True, errors=(), errors_first=0):
+        """From now on every advance / advance_sim (a hand-over, counted from 0) first records, on the device and without synchronising:
+        hand-over i makes a record when i >= first, (i - first) % every == 0 and fewer than `capacity` exist.  states: None (all) or a list of
+        state indices (stored in ascending order); u: u of stage 0; status: status and qp_iter of the last solve.  errors: up to four
+        channels (a, b) = x0[a] - x0[b] or (a, float) = x0[a] - the constant, summed as |e| and e e over the hand-overs from errors_first on
+        (log_errors)."""
+        d = _capi.LogDesc()
+        d.capacity, d.every, d.first = int(capacity), int(every), int(first)
+        sel = list(range(self.nx)) if states is None else sorted(set(int(j) for j in states))
+        if any(j < 0 or j >= 32 for j in sel):
+            raise Exception("start_log: states must be indices of the model's states")
+        d.state_mask = sum(1 << j for j in sel)
+        d.record_u, d.record_status = int(bool(u)), int(bool(status))
+        errors = list(errors)
+        if len(errors) > 4:
+            raise Exception("start_log: at most 4 error channels")
+        d.n_err = len(errors)
+        for c, (a, b) in enumerate(errors):
+            d.err_a[c] = int(a)
+            if isinstance(b, (int, np.integer)) and not isinstance(b, bool):
+                d.err_b[c], d.err_c[c] = int(b), 0.0
+            else:
+                d.err_b[c], d.err_c[c] = -1, float(b)
+        d.err_first = int(errors_first)
+        self._check(self._lib.usvmpc_log_start(self._h, C.byref(d)))
+        self._log = dict(states=sel, first=d.first, every=d.every, u=bool(u), status=bool(status), n_err=d.n_err)
+
+    def log_info(self):
+        """dict: records made, handovers counted since start_log, missed (due for a record when the buffer was full), nsel."""
+        r, n = C.c_int(), C.c_int()
+        ho, mi = C.c_longlong(), C.c_longlong()
+        self._check(self._lib.usvmpc_log_info(self._h, C.byref(r), C.byref(ho), C.byref(mi), C.byref(n)))
+        return dict(records=r.value, handovers=ho.value, missed=mi.value, nsel=n.value)
+
+    @staticmethod
+    def _log_range(r, n, what):
+        if r is None:
+            return 0, n
+        if isinstance(r, range):
+            if r.step != 1:
+                raise Exception("read_log: %s must be a contiguous range" % what)
+            return r.start, len(r)
+        a, b = r
+        return int(a), int(b) - int(a)
+
+    def read_log(self, records=None, instances=None):
+        """The log so far (synchronises).  records / instances: None (all made so far / the batch) or a half-open (start, stop) pair or range.
+        dict: x [nb][nrec][nsel] and u [nb][nrec][nu] - an instance's simX / simU, instance-major views of the tick-major copy -, status and
+        qp_iter [nb][nrec], tick [nrec] (the hand-over of each record), states (the indices of x's last axis).  Channels not recorded are
+        absent."""
+        made = self.log_info()["records"]    # (raises when no log runs)
+        lg = self._log
+        r0, nr = self._log_range(records, made, "records")
+        b0, nb = self._log_range(instances, self.B, "instances")
+        out = dict(tick=lg["first"] + lg["every"] * np.arange(r0, r0 + nr), states=list(lg["states"]))
+        chans = [("x", len(lg["states"]), np.float64)] if lg["states"] else []
+        chans += [("u", self.nu, np.float64)] if lg["u"] else []
+        chans += [("status", 1, np.int32)] if lg["status"] else []
+        for name, n, dt in chans:
+            a = np.zeros((nr, nb, n), dtype=dt)
+            if nr > 0 or records is not None:
+                self._check(self._lib.usvmpc_log_read(self._h, name.encode(), r0, nr, b0, nb, a.ctypes.data_as(C.c_void_p), a.nbytes))
+            if name == "status":
+                w = a[:, :, 0].T
+                out["status"], out["qp_iter"] = w & 0xff, w >> 8
+            else:
+                out[name] = a.transpose(1, 0, 2)
+        return out
+
+    def log_errors(self):
+        """dict: sum_abs and sum_sq [B][n_err] - the sums of |e| and e e per instance and error channel over `count` hand-overs - and count
+        (synchronises).  The reference's statistics are sum / count (scripts/usv_pf_ca/main.py:199-207)."""
+        n = (getattr(self, "_log", None) or {}).get("n_err", 0)
+        sa, sq = np.zeros((self.B, n)), np.zeros((self.B, n))
+        cnt = C.c_longlong()
+        self._check(self._lib.usvmpc_log_errors(self._h, sa.ctypes.data_as(_capi._dp), sq.ctypes.data_as(_capi._dp), C.byref(cnt)))
+        return dict(sum_abs=sa, sum_sq=sq, count=cnt.value)
+
+    def log_device_ptr(self, channel):
+        """Device address of a log channel ("x", "u", "status", "sum_abs", "sum_sq") for zero-copy views; cancels nothing."""
+        p = C.c_void_p()
+        self._check(self._lib.usvmpc_log_device_ptr(self._h, channel.encode(), C.byref(p)))
+        return p.value
+
+    def stop_log(self):
+        self._check(self._lib.usvmpc_log_stop(self._h))
+        self._log = None
+
     def device_bytes(self):
         return int(self._lib.usvmpc_device_bytes(self._h))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            if getattr(self, "_log", None) is not None:
+                self._lib.usvmpc_log_stop(self._h)
+                self._log = None
             self._lib.usvmpc_destroy(self._h)
             self._h = C.c_void_p()
 

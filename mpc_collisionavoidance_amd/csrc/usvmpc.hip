@@ -24,9 +24,11 @@
 
 #include "gfx950/lanes.hpp"
 
+#include "closed_loop_log.hpp"
 #include "guidance.hpp"
 #include "host_spec.hpp"
 #include "lin_plan.hpp"
+#include "log_plan.hpp"
 #include "linearize.hpp"
 #include "models.hpp"
 #include "obstacle_tracks.hpp"
@@ -348,6 +350,39 @@ __global__ void __launch_bounds__(256) usv_advance_sim(DevPtrs P, double T, int 
         if (sigma != 0.0 && ((mask >> j) & 1u)) v += noise(sigma, seed, (unsigned long long)((offset + b) * NX + j));
         x0[j] = v;
     });
+}
+
+// ---- Closed-loop log (usvmpc_log_*; the schedule and layout: log_plan.hpp; the arithmetic: closed_loop_log.hpp).
+// usv_log_record: one launch per hand-over that records or accumulates, enqueued AHEAD of the hand-over's own kernel, so that x0 is still the
+// state the solve saw.  It reads x0, u, status and qp_iter and writes log memory only.  Thread t serves element t of each of the record's
+// three slabs and of the sums (four guards): every store of a wave is one contiguous run (512 B of doubles), the reads gather inside an
+// instance's x0 row.  The selected states and the error channels' states travel as nibble lists in two 64-bit arguments, the constants as
+// four scalars picked by a select chain - nothing in the argument struct is indexed at run time.
+__global__ void __launch_bounds__(256) usv_log_record(LogRec R)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (R.rx && t < R.B * R.nsel) {
+        const long b = t / R.nsel;
+        const int j = (int)(t - b * R.nsel);
+        R.rx[t] = R.x0[b * R.nx + log_nibble(R.sel, j)];
+    }
+    if (R.ru && t < R.B * R.nu) {
+        const long b = t / R.nu;
+        const int l = (int)(t - b * R.nu);
+        R.ru[t] = R.u[b * R.ustride + l];
+    }
+    if (R.rs && t < R.B) R.rs[t] = R.status[t] | (R.qp_iter[t] << 8);
+    if (R.sum_abs && t < R.B * R.n_err) {
+        const long b = t / R.n_err;
+        const int c = (int)(t - b * R.n_err);
+        const double *x = R.x0 + b * R.nx;
+        const double k = c == 0 ? R.c0 : c == 1 ? R.c1 : c == 2 ? R.c2 : R.c3;
+        const double rhs = ((R.err_const >> c) & 1u) ? k : x[log_nibble(R.err_b, c)];
+        double sa = R.sum_abs[t], sq = R.sum_sq[t];
+        log_accumulate(log_error(x[log_nibble(R.err_a, c)], rhs), &sa, &sq);
+        R.sum_abs[t] = sa;
+        R.sum_sq[t] = sq;
+    }
 }
 
 // ---- Obstacle tracks (option "obstacle_tracks"; the arithmetic: obstacle_tracks.hpp).
@@ -930,6 +965,13 @@ struct usvmpc_handle {
     bool gd_moving = false;     // velocities are set for the current list
     bool gd_predict = false;    // ... and the horizon sees them ("static_obstacles" off)
     int gd_tick = 0;            // device-resident prepares since the last reset
+    // Closed-loop log (usvmpc_log_*): which hand-over records, the counters and the layout are log_plan.hpp's - the state machine LogPlan (no
+    // field of it is assigned in this file: usvmpc_log_start / _stop and log_handover call its methods), host-only and checked on the CPU by
+    // tests/test_log_plan.py.  Here: the buffers its layout sizes (nullptr: channel not recorded) and the kernel arguments that do not change.
+    LogPlan log;
+    double *log_x = nullptr, *log_u = nullptr, *log_sums = nullptr; // [capacity][B][nsel], [capacity][B][nu], [2][B][n_err]
+    int *log_status = nullptr;  // [capacity][B]
+    LogRec log_rec = {};
 };
 
 // Kernels::lin / lin_pair: usv_linearize for one and several RK4 steps (MULTI), every MODE
@@ -2251,6 +2293,153 @@ int usvmpc_last_kernel_ms(usvmpc_handle *h, float *linearize_ms, float *qp_ms)
 
 static int pf_apply_static(usvmpc_handle *h);
 
+// ---- the closed-loop log: log_plan.hpp says what a hand-over does and what a read copies; here: the buffers, the launch, the copies
+static void log_release(usvmpc_handle *h)
+{
+    const LogLayout &l = h->log.lay;
+    dev_free(h, h->log_x, (size_t)l.x_bytes);
+    dev_free(h, h->log_u, (size_t)l.u_bytes);
+    dev_free(h, h->log_status, (size_t)l.status_bytes);
+    dev_free(h, h->log_sums, (size_t)l.sums_bytes);
+    h->log_x = h->log_u = h->log_sums = nullptr;
+    h->log_status = nullptr;
+}
+
+// a hand-over of a handle whose log runs (usvmpc_advance / usvmpc_advance_sim, behind the mirror's upload and ahead of their own kernel)
+static int log_handover(usvmpc_handle *h)
+{
+    const LogTick t = h->log.on_handover();
+    if (t.slot < 0 && !t.errors) return 0;
+    const LogLayout &l = h->log.lay;
+    LogRec r = h->log_rec;
+    r.x0 = h->ptrs.x0; r.u = h->ptrs.u; r.status = h->ptrs.status; r.qp_iter = h->ptrs.qp_iter;
+    long n = 0;
+    if (t.slot >= 0) {
+        const long at = (long)t.slot * l.B;
+        if (h->log_x) { r.rx = h->log_x + at * l.nsel; n = std::max(n, (long)l.B * l.nsel); }
+        if (h->log_u) { r.ru = h->log_u + at * l.nu; n = std::max(n, (long)l.B * l.nu); }
+        if (h->log_status) { r.rs = h->log_status + at; n = std::max(n, (long)l.B); }
+    }
+    if (t.errors) {
+        r.sum_abs = h->log_sums;
+        r.sum_sq = h->log_sums + (long)l.B * l.n_err;
+        n = std::max(n, (long)l.B * l.n_err);
+    }
+    hipLaunchKernelGGL(usv_log_record, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int usvmpc_log_start(usvmpc_handle *h, const usvmpc_log_desc *d)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!d) { h->err = "log_start: null descriptor"; return USVMPC_E_ARG; }
+    if (h->log.on) { h->err = "log_start: a log is running (usvmpc_log_stop first)"; return USVMPC_E_ARG; }
+    LogDesc ld = {};
+    ld.capacity = d->capacity; ld.every = d->every; ld.first = d->first; ld.state_mask = d->state_mask;
+    ld.record_u = d->record_u; ld.record_status = d->record_status; ld.n_err = d->n_err; ld.err_first = d->err_first;
+    for (int c = 0; c < LOG_ERR_MAX; c++) { ld.err_a[c] = d->err_a[c]; ld.err_b[c] = d->err_b[c]; ld.err_c[c] = d->err_c[c]; }
+    LogLayout lay;
+    if (const char *why = check_log_desc(ld, h->nx, h->nu, h->B, &lay)) { h->err = why; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    // all four buffers or none: a failed allocation leaves the handle as it was
+    void *buf[4] = {nullptr, nullptr, nullptr, nullptr};
+    const long long want[4] = {lay.x_bytes, lay.u_bytes, lay.status_bytes, lay.sums_bytes};
+    for (int i = 0; i < 4; i++) {
+        if (want[i] == 0) continue;
+        const hipError_t e = hipMalloc(&buf[i], (size_t)want[i]);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < i; j++)
+                if (buf[j]) (void)hipFree(buf[j]);
+            h->err = std::string("log_start: hipMalloc of ") + std::to_string(want[i]) + " bytes: " + hipGetErrorString(e);
+            return USVMPC_E_HIP;
+        }
+    }
+    for (int i = 0; i < 4; i++)
+        if (buf[i]) { h->allocs.push_back(buf[i]); h->bytes += (size_t)want[i]; }
+    h->log_x = (double *)buf[0]; h->log_u = (double *)buf[1]; h->log_status = (int *)buf[2]; h->log_sums = (double *)buf[3];
+    h->log.start(ld, lay);
+    if (h->log_sums) HIP_TRY(h, hipMemsetAsync(h->log_sums, 0, (size_t)lay.sums_bytes, h->stream));
+    LogRec r = {};
+    r.B = h->B; r.nx = h->nx; r.nu = lay.nu; r.ustride = h->N * h->nu; r.n_err = lay.n_err;
+    r.sel = log_pack_mask(ld.state_mask, &r.nsel);
+    int eb[LOG_ERR_MAX];
+    for (int c = 0; c < LOG_ERR_MAX; c++) {
+        eb[c] = ld.err_b[c] < 0 ? 0 : ld.err_b[c];
+        if (c < ld.n_err && ld.err_b[c] < 0) r.err_const |= 1u << c;
+    }
+    r.err_a = log_pack_list(ld.err_a, ld.n_err);
+    r.err_b = log_pack_list(eb, ld.n_err);
+    r.c0 = ld.err_c[0]; r.c1 = ld.err_c[1]; r.c2 = ld.err_c[2]; r.c3 = ld.err_c[3];
+    h->log_rec = r;
+    return 0;
+}
+
+int usvmpc_log_stop(usvmpc_handle *h)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!h->log.on) { h->err = "log_stop: no log is running"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    log_release(h);
+    h->log.stop();
+    return 0;
+}
+
+int usvmpc_log_info(usvmpc_handle *h, int *records, long long *handovers, long long *missed, int *nsel)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!h->log.on) { h->err = "log_info: no log is running (usvmpc_log_start)"; return USVMPC_E_ARG; }
+    if (records) *records = h->log.records;
+    if (handovers) *handovers = h->log.handovers;
+    if (missed) *missed = h->log.missed;
+    if (nsel) *nsel = h->log.lay.nsel;
+    return 0;
+}
+
+int usvmpc_log_read(usvmpc_handle *h, const char *channel, int rec0, int nrec, int b0, int nb, void *out, size_t bytes)
+{
+    if (!h) return USVMPC_E_ARG;
+    LogCopy c;
+    if (const char *why = h->log.read_desc(channel, rec0, nrec, b0, nb, &c)) { h->err = why; return USVMPC_E_ARG; }
+    if (!out || (long long)bytes != c.bytes()) {
+        h->err = "log_read: out must hold exactly " + std::to_string(c.bytes()) + " bytes ([nrec][nb][" + std::to_string(c.n) + "])";
+        return USVMPC_E_ARG;
+    }
+    const char *src = c.channel == LOG_X ? (const char *)h->log_x : c.channel == LOG_U ? (const char *)h->log_u : (const char *)h->log_status;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpy2DAsync(out, (size_t)c.width, src + c.offset, (size_t)c.pitch, (size_t)c.width, (size_t)c.rows, hipMemcpyDeviceToHost,
+                                h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int usvmpc_log_errors(usvmpc_handle *h, double *sum_abs, double *sum_sq, long long *count)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!h->log.on || h->log.lay.n_err == 0) { h->err = "log_errors: no log with error channels is running"; return USVMPC_E_ARG; }
+    const size_t half = (size_t)h->log.lay.sums_bytes / 2;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (sum_abs) HIP_TRY(h, hipMemcpyAsync(sum_abs, h->log_sums, half, hipMemcpyDeviceToHost, h->stream));
+    if (sum_sq) HIP_TRY(h, hipMemcpyAsync(sum_sq, (const char *)h->log_sums + half, half, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (count) *count = h->log.err_count;
+    return 0;
+}
+
+int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr)
+{
+    if (!h || !dptr) return USVMPC_E_ARG;
+    if (!h->log.on) { h->err = "log_device_ptr: no log is running (usvmpc_log_start)"; return USVMPC_E_ARG; }
+    const std::string s = channel ? channel : "";
+    void *p = s == "x" ? (void *)h->log_x : s == "u" ? (void *)h->log_u : s == "status" ? (void *)h->log_status
+            : s == "sum_abs" ? (void *)h->log_sums
+            : s == "sum_sq" ? (void *)(h->log_sums ? h->log_sums + (long)h->log.lay.B * h->log.lay.n_err : nullptr) : nullptr;
+    if (!p) { h->err = "log_device_ptr: '" + s + "' is no channel of the running log"; return USVMPC_E_ARG; }
+    *dptr = p;
+    return 0;
+}
+
 int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
 {
     if (!h) return USVMPC_E_ARG;
@@ -2258,6 +2447,10 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
     {
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
+    }
+    if (h->log.on) { // (ahead of the kernel that overwrites x0)
+        const int rcl = log_handover(h);
+        if (rcl) return rcl;
     }
     const long n = (long)h->B * h->nx;
     hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->opt.noise_mask,
@@ -2297,6 +2490,10 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     {
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
+    }
+    if (h->log.on) { // (ahead of the kernel that overwrites x0)
+        const int rcl = log_handover(h);
+        if (rcl) return rcl;
     }
     const dim3 grid((unsigned)((h->B + 255) / 256)), block(256);
     switch (h->desc.model) {
