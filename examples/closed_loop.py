@@ -42,6 +42,7 @@ def usv_acados(ticks):
         x0 = acados_solver.get(1, "x")
         acados_solver.set(0, "lbx", x0)
         acados_solver.set(0, "ubx", x0)
+    print("objective value of the last tick: %.6f" % acados_solver.get_cost())
     print("final surge speed u = %.4f (reference %.2f)" % (simX[-1, 0], uref))
     return tcomp_sum / Nsim, tcomp_max
 
@@ -91,6 +92,7 @@ def usv_guidance_ca1(ticks):
         x0 = acados_solver.get(1, "x")
         acados_solver.set(0, "lbx", x0)
         acados_solver.set(0, "ubx", x0)
+    print("objective value of the last tick: %.6f" % acados_solver.get_cost())
     clear = min(np.hypot(simX[:, 5] - ox, simX[:, 6] - oy).min() - 1.5 for ox, oy in zip(obsx, obsy))
     print("minimum clearance to an obstacle: %.3f m (nominal 0.2 from lsh)" % clear)
     if nstat:
@@ -136,6 +138,7 @@ def usv_pf_ca(ticks):
         x0 = acados_solver.get(1, "x")
         acados_solver.set(0, "lbx", x0)
         acados_solver.set(0, "ubx", x0)
+    print("objective value of the last tick: %.6f" % acados_solver.get_cost())
     clear = min(np.hypot(simX[:, 10] - ox, simX[:, 11] - oy).min() - 0.7 for ox, oy in zip(obsx, obsy))
     print("final surge speed u = %.4f (reference 0.7), minimum margin to the keep-out circles %.3f m" % (simX[-1, 3], clear))
     return tcomp_sum / Nsim, tcomp_max

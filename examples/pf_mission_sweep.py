@@ -36,7 +36,7 @@ ERRORS = (("psi - ak", (0, 9)), ("u - u_ref", (3, 0.7)), ("ye", (6, 0.0)))   # m
 ERRORS_FIRST = 401                                                          # ... over the ticks after 400
 
 
-def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False, predict=True, log_every=None):
+def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False, predict=True, log_every=None, cost=False):
     cfg = scenario.PF_MISSION_OCP
     dt = cfg["dt"]
     m = scenario.make_pf_missions(B, seed, moving=moving)
@@ -63,6 +63,8 @@ def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False
     if log_every:
         s.start_log(-(-ticks // log_every), every=log_every, states=[0, 10, 11], u=False, status=False, errors=[c for _, c in ERRORS],
                     errors_first=ERRORS_FIRST if ticks > ERRORS_FIRST else 0)
+    if cost:
+        s.track_cost(True)      # the realised closed-loop cost: every hand-over adds c_0(x0, u_0) on the device
     s.sync()
     t0 = time.perf_counter()
     for i in range(ticks):
@@ -95,6 +97,15 @@ def run(B, ticks, N=40, K=4, seed=0, plant_steps=None, quiet=False, moving=False
         # beside final_pose, in its order (nedx, nedy, psi): [B][records][3] and the tick of each record
         res.update(log_pose=log["x"][:, :, [1, 2, 0]].copy(), log_tick=log["tick"], error_count=err["count"],
                    mean_abs_error=err["sum_abs"] / max(err["count"], 1), mean_sq_error=err["sum_sq"] / max(err["count"], 1))
+    if cost:
+        res["tracked_cost"], res["tracked_count"] = s.tracked_cost()
+        if not quiet:
+            tc = res["tracked_cost"][st["finish_tick"] >= 0]
+            if tc.size:
+                print("realised closed-loop cost over %d hand-overs, finished missions: min %.4f, median %.4f, max %.4f"
+                      % (res["tracked_count"], tc.min(), np.median(tc), tc.max()))
+            else:
+                print("realised closed-loop cost over %d hand-overs: no mission has finished" % res["tracked_count"])
     if not quiet and log_every:
         print("logged %d records of (nedx, nedy, psi) per mission, one every %d ticks; errors over %d ticks:"
               % (len(res["log_tick"]), log_every, res["error_count"]))
@@ -130,5 +141,7 @@ if __name__ == "__main__":
     ap.add_argument("--no-predict", action="store_true", help="with --moving: the world is held still inside the horizon (option \"pf_predict\" 0)")
     ap.add_argument("--log-every", type=int, default=None,
                     help="keep (nedx, nedy, psi) of every n-th tick and main.py's error statistics on the device (start_log)")
+    ap.add_argument("--cost", action="store_true", help="sum the realised closed-loop cost of every mission on the device (track_cost)")
     a = ap.parse_args()
-    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps, moving=a.moving, predict=not a.no_predict, log_every=a.log_every)
+    run(a.batch, a.ticks, N=a.horizon, seed=a.seed, plant_steps=a.plant_steps, moving=a.moving, predict=not a.no_predict, log_every=a.log_every,
+        cost=a.cost)

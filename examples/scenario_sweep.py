@@ -35,7 +35,8 @@ def make_worlds(B, L, rng):
 ERRORS = (("ye", (2, 0.0)), ("chie", (3, 0.0)))   # the tracking errors of usv_model_guidance_ca1 are states: (state, constant)
 
 
-def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None, resident=False, moving=False, predict=True, log_every=None):
+def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=None, resident=False, moving=False, predict=True, log_every=None,
+        cost=False):
     """resident=False: the host-fed loop (the ROS nodes' callbacks, arrays through the host every tick).  resident=True: the whole mission
     on the device - the world is uploaded once, a tick is prepare() -> solve_async -> publish(fetch=False) -> advance, and the host reads
     once at the end.  moving=True (resident only): the obstacles cross the first leg and the horizon sees where they will be (predict)."""
@@ -56,8 +57,10 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
         raise Exception("a moving world needs the device-resident loop (resident=True)")
     if log_every and not resident:
         raise Exception("the log replaces the host arrays of the device-resident loop (resident=True); the host-fed loop has them anyway")
+    if cost and not resident:
+        raise Exception("the tracked cost replaces the read-backs of the device-resident loop (resident=True)")
     if resident:
-        res = _run_resident(s, fe, plant, m, ticks, predict, log_every)
+        res = _run_resident(s, fe, plant, m, ticks, predict, log_every, cost)
     else:
         min_clear = np.full(B, np.inf)
         bad = np.zeros(B, dtype=bool)
@@ -89,6 +92,13 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
         print("minimum clearance to the keep-out circle (R + 0.5 m): worst %.3f m, 1st percentile %.3f m, median %.3f m"
               % (min_clear.min(), np.percentile(min_clear, 1), np.median(min_clear)))
         print("scenarios with a solver failure: %d; reached the second leg: %d" % (bad.sum(), (k >= 2).sum()))
+        if cost:
+            tc = res["tracked_cost"][res["finish_tick"] >= 0]
+            if tc.size:
+                print("realised closed-loop cost over %d hand-overs, finished missions: min %.4f, median %.4f, max %.4f"
+                      % (res["tracked_count"], tc.min(), np.median(tc), tc.max()))
+            else:
+                print("realised closed-loop cost over %d hand-overs: no mission has finished" % res["tracked_count"])
         if log_every:
             print("logged %d records of (xned, yned, psi) per scenario, one every %d ticks; errors over %d ticks:"
                   % (len(res["log_tick"]), log_every, res["error_count"]))
@@ -101,7 +111,7 @@ def run(B=1024, ticks=600, N=100, K=8, L=5, seed=0, quiet=False, plant_steps=Non
     return res
 
 
-def _run_resident(s, fe, plant, m, ticks, predict, log_every=None):
+def _run_resident(s, fe, plant, m, ticks, predict, log_every=None, cost=False):
     """The device-resident loop.  min_clearance is the front end's: the minimum over the poses the ticks were PREPARED at (the start pose
     included, the pose after the last tick not), where the host-fed loop takes the poses after each tick.
     solver_failures: an instance's status after the last tick, missions that are over left out as in the host-fed loop; the ticks before
@@ -115,6 +125,8 @@ def _run_resident(s, fe, plant, m, ticks, predict, log_every=None):
     fails = []
     if log_every:
         s.start_log(-(-ticks // log_every), every=log_every, states=[5, 6, 7], u=False, status=False, errors=[c for _, c in ERRORS])
+    if cost:
+        s.track_cost(True)                           # the realised closed-loop cost: every hand-over adds c_0(x0, u_0) on the device
     t0 = time.perf_counter()
     for i in range(ticks):
         fe.prepare()                                 # sensor + callbacks + waypoint manager, from the solver's own x0
@@ -137,6 +149,8 @@ def _run_resident(s, fe, plant, m, ticks, predict, log_every=None):
         bad[:] = True
     res = dict(ticks_per_s=ticks / el, scenario_ticks_per_s=B * ticks / el, min_clearance=st["min_clearance"], solver_failures=bad,
                waypoint_index=st["wp_index"], final_pose=s.get("x0", 0)[:, 5:8].copy(), finish_tick=st["finish_tick"], fail_counts=fails)
+    if cost:
+        res["tracked_cost"], res["tracked_count"] = s.tracked_cost()
     if log_every:
         log, err = s.read_log(), s.log_errors()
         # beside final_pose, in its order (xned, yned, psi): [B][records][3] and the tick of each record
@@ -157,6 +171,7 @@ if __name__ == "__main__":
     ap.add_argument("--no-predict", action="store_true", help="with --moving: hold the world still inside the horizon")
     ap.add_argument("--log-every", type=int, default=None,
                     help="device-resident loop: keep (xned, yned, psi) of every n-th tick and the ye / chie error statistics on the device")
+    ap.add_argument("--cost", action="store_true", help="device-resident loop: sum the realised closed-loop cost of every scenario on the device")
     a = ap.parse_args()
     run(a.batch, a.ticks, a.horizon, plant_steps=a.plant_steps, resident=a.resident or a.moving or bool(a.log_every), moving=a.moving,
-        predict=not a.no_predict, log_every=a.log_every)
+        predict=not a.no_predict, log_every=a.log_every, cost=a.cost)

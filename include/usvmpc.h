@@ -513,7 +513,8 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
  * The record kernel reads x0, u, status and qp_iter and writes log memory only: it is no caller write - the pipelined lineariser's work
  * made a tick ahead stands, and log_device_ptr, which exposes log memory only, leaves it alone as well.
  * Not provided: a ring mode; the front ends' published values and waypoint index (positions, ak and the thrusts are states); a cost
- * channel.  A loop around usvmpc_solve_sqp is logged like any other: whatever the solve, the hand-over records. */
+ * channel - the realised closed-loop cost is usvmpc_cost_track's ("Objective value" below).  A loop around usvmpc_solve_sqp is logged like
+ * any other: whatever the solve, the hand-over records. */
 typedef struct usvmpc_log_desc {
     int capacity;        /* records kept, >= 1 */
     int every;           /* one record every `every`-th hand-over, >= 1 */
@@ -531,6 +532,34 @@ int usvmpc_log_info(usvmpc_handle *h, int *records, long long *handovers, long l
 int usvmpc_log_read(usvmpc_handle *h, const char *channel, int rec0, int nrec, int b0, int nb, void *out, size_t bytes);
 int usvmpc_log_errors(usvmpc_handle *h, double *sum_abs, double *sum_sq, long long *count);
 int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr);
+/* ---- Objective value (acados' AcadosOcpSolver.get_cost()): the cost of the iterate the handle holds and the realised closed-loop cost, on
+ * the device, so that a device-resident loop compares weightings, horizons and prediction modes without reading x, u, yref, sl and su back
+ * every tick (the arithmetic: csrc/cost_eval.hpp; the kernels: usv_cost_eval, usv_cost_track).  With z = [u_k; x_k], V = [Vu Vx], dt = Tf / N:
+ *       r = V z - yref[k],  ls_k = (0.5 dt) r' W r,  slack_k = dt * sum_i (zl_i sl_i + zu_i su_i + 0.5 Zl_i sl_i^2 + 0.5 Zu_i su_i^2)   (soft h rows;
+ *       hard ones: 0),  c_k = ls_k + slack_k  for k < N;   c_N = 0.5 r' W_e r,  r = Vx_e x_N - yref_e;   cost = c_0 + .. + c_N
+ * Every product, difference and sum is rounded on its own (no fused multiply-add) and every sum runs sequentially from 0.0 in the order
+ * csrc/cost_eval.hpp writes down - the order is part of the interface: a sequential numpy loop over get "x", "u", "yref", "sl", "su"
+ * returns the same bits.  No clamp: a negative slack enters as it is; a NaN stays a NaN in its instance and in no other.
+ *   get "cost" [batch] (n = 1, stage ignored), "cost_stage" (stage 0..N, n = 1; stage -1: [batch][N+1]), "cost_parts" [batch][3] (n = 3, stage
+ *       ignored) = [sum of ls_k, c_N, sum of slack_k]: every such usvmpc_get uploads pending host writes, enqueues usv_cost_eval on the
+ *       handle's stream, copies and synchronises - no staleness state is kept, the value is that of the arrays as the device holds them
+ *       (whichever solve produced them, or the caller's own sets).  usvmpc_set of them is refused like any output.
+ *   usvmpc_eval_cost: enqueues the evaluation without synchronising - for resident loops that read the result through
+ *       usvmpc_get_device_ptr "cost" | "cost_stage" | "cost_parts".  The three buffers and the kernels' tables are made by the first call of
+ *       either kind: a handle that never asks for a cost allocates nothing and launches what it always did.
+ *   usvmpc_cost_track(h, 1): allocates sum [batch], zeroes sum and count and starts (while running: zeroes again); (h, 0): stops and frees.
+ *       While tracking runs every hand-over (usvmpc_advance, usvmpc_advance_sim) first enqueues usv_cost_track AHEAD of its own kernel (where
+ *       the log's record goes):  sum[b] = sum[b] + c_0(x0[b], u[b][0], yref[b][0], sl[b][0], su[b][0]) - the stage function with z = [u_0; x0],
+ *       the state the solve saw (after a status-4 solve x of stage 0 may be something else), in hand-over order.
+ *   usvmpc_cost_tracked: sum [batch] (may be NULL) and the hand-overs counted; synchronises.  USVMPC_E_ARG with a message while no tracking
+ *       runs.  usvmpc_get_device_ptr "cost_tracked" is the sum on the device (while tracking runs).
+ * Neither kernel is a caller write: they read x, u, yref and write cost memory only, so the pipelined lineariser's pass made a tick ahead
+ * stands and the device pointers above cancel nothing.  usvmpc_device_bytes includes every cost buffer while it exists.
+ * Not built for handles with soft state bounds, whose slack values are not among the arrays a caller can get: every entry point answers
+ * USVMPC_E_ARG, "cost: not built for soft state bounds".  No option and no channel of the log. */
+int usvmpc_eval_cost(usvmpc_handle *h);
+int usvmpc_cost_track(usvmpc_handle *h, int on);
+int usvmpc_cost_tracked(usvmpc_handle *h, double *sum, long long *count);
 /* bytes of device memory held by the handle */
 size_t usvmpc_device_bytes(usvmpc_handle *h);
 const char *usvmpc_last_error(usvmpc_handle *h);

@@ -72,7 +72,8 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read",
            "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
            "usvmpc_guidance_mission_state",
-           "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr"]
+           "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr",
+           "usvmpc_eval_cost", "usvmpc_cost_track", "usvmpc_cost_tracked"]
 
 
 class LogDesc(C.Structure):
@@ -173,6 +174,9 @@ def load(path):
     L.usvmpc_log_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     L.usvmpc_log_errors.argtypes = [C.c_void_p, _dp, _dp, _llp]
     L.usvmpc_log_device_ptr.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    L.usvmpc_eval_cost.argtypes = [C.c_void_p]
+    L.usvmpc_cost_track.argtypes = [C.c_void_p, C.c_int]
+    L.usvmpc_cost_tracked.argtypes = [C.c_void_p, _dp, _llp]
     L.usvmpc_device_bytes.argtypes = [C.c_void_p]
     L.usvmpc_device_bytes.restype = C.c_size_t
     L.usvmpc_last_error.argtypes = [C.c_void_p]

@@ -251,7 +251,8 @@ class BatchOcpSolver:
         N = self.N
         tab = {"x": (self.nx, N + 1), "u": (self.nu, N), "p": (2 * self.K, N + 1), "lh": (self.K, N),
                "pi": (self.nx, N), "sl": (self.K, N), "su": (self.K, N), "x0": (self.nx, 1),
-               "lam": (self.nlam, N + 1), "t": (self.nlam, N + 1)}
+               "lam": (self.nlam, N + 1), "t": (self.nlam, N + 1),
+               "cost": (1, 1), "cost_stage": (1, N + 1), "cost_parts": (3, 1)}
         if field == "yref":
             return (self.ny_e, 1) if stage == N else (self.ny, N)
         if field not in tab:
@@ -298,6 +299,12 @@ class BatchOcpSolver:
             out = np.zeros(self.B)
             self._check(self._lib.usvmpc_get(self._h, field.encode(), 0, out.ctypes.data_as(_capi._dp), 1))
             return out
+        if field in ("cost", "cost_stage", "cost_parts"):   # evaluated on the device now: [B], [B] (a stage) or [B, N + 1] (-1), [B, 3]
+            n = 3 if field == "cost_parts" else 1
+            whole = field == "cost_stage" and int(stage) < 0
+            out = np.zeros((self.B, self.N + 1 if whole else n))
+            self._check(self._lib.usvmpc_get(self._h, field.encode(), int(stage), out.ctypes.data_as(_capi._dp), n))
+            return out if whole or n == 3 else out[:, 0].copy()
         n, _ = self._field(field, stage)
         out = np.zeros((self.B, n))
         self._check(self._lib.usvmpc_get(self._h, field.encode(), int(stage), out.ctypes.data_as(_capi._dp), n))
@@ -540,6 +547,28 @@ class BatchOcpSolver:
         self._check(self._lib.usvmpc_log_stop(self._h))
         self._log = None
 
+    # -- objective value (include/usvmpc.h, "Objective value"; the arithmetic and the order of every sum: csrc/cost_eval.hpp)
+    def get_cost(self):
+        """[B]: the cost of the iterate the handle holds (x, u, yref, sl, su as the device has them), evaluated on the device now;
+        get("cost_stage", k | -1) and get("cost_parts", 0) = [sum of the stage terms, the terminal term, sum of the slack terms] likewise."""
+        return self.get("cost", 0)
+
+    def eval_cost(self):
+        """Enqueue the evaluation without synchronising: the results are behind device_ptr("cost" | "cost_stage" | "cost_parts")."""
+        self._check(self._lib.usvmpc_eval_cost(self._h))
+
+    def track_cost(self, on=True):
+        """Realised closed-loop cost: while on, every hand-over (advance, advance_sim) first adds c_0(x0, u_0, yref_0, sl_0, su_0) to a
+        per-instance sum on the device.  on=True (again) zeroes sum and count; on=False stops and frees."""
+        self._check(self._lib.usvmpc_cost_track(self._h, 1 if on else 0))
+
+    def tracked_cost(self):
+        """(sum [B], count): the tracked sums and the hand-overs they hold (synchronises); device_ptr("cost_tracked") is the sum on the device."""
+        s = np.zeros(self.B)
+        cnt = C.c_longlong()
+        self._check(self._lib.usvmpc_cost_tracked(self._h, s.ctypes.data_as(_capi._dp), C.byref(cnt)))
+        return s, cnt.value
+
     def device_bytes(self):
         return int(self._lib.usvmpc_device_bytes(self._h))
 
@@ -632,6 +661,10 @@ class AcadosOcpSolver:
         if field_ == "pi":
             return self._b.get("pi", stage_ + 1)[0].copy()  # acados: pi of stage k couples k -> k+1
         return self._b.get(field_, stage_)[0].copy()
+
+    def get_cost(self):
+        """acados' AcadosOcpSolver.get_cost(): the cost of the current iterate, a float"""
+        return float(self._b.get_cost()[0])
 
     def get_stats(self, field_):
         if field_ == "qp_iter":

@@ -15,9 +15,9 @@ namespace usv {
 enum FieldId {
     FLD_X = 0, FLD_U, FLD_STATUS, FLD_X0, FLD_YREF, FLD_YREF_E, FLD_P, FLD_LH, ARENA_FIELDS,
     FLD_PI = ARENA_FIELDS, FLD_SL, FLD_SU, FLD_RES, FLD_OBS_TMIN, FLD_NLP_RES, FLD_LAM, FLD_T, FLD_QP_ITER, FLD_QP_STATUS, FLD_SQP_ITER,
-    FLD_OBS_POS, FLD_OBS_VEL, FLD_CLEARANCE, FLD_CLEARANCE_MIN, FLD_COUNT
+    FLD_OBS_POS, FLD_OBS_VEL, FLD_CLEARANCE, FLD_CLEARANCE_MIN, FLD_COST, FLD_COST_STAGE, FLD_COST_PARTS, FLD_COUNT
 };
-enum FieldLen { LEN_NX, LEN_NU, LEN_NY, LEN_NY_E, LEN_2K, LEN_K, LEN_NLAM, LEN_4, LEN_1 }; // per-stage length, over the handle's sizes
+enum FieldLen { LEN_NX, LEN_NU, LEN_NY, LEN_NY_E, LEN_2K, LEN_K, LEN_NLAM, LEN_4, LEN_3, LEN_1 }; // per-stage length, over the handle's sizes
 enum FieldStages { ST_N1, ST_N, ST_1 };                                                      // N + 1 | N | 1
 enum : unsigned { // rights
     R_SET = 1,     // usvmpc_set
@@ -30,7 +30,8 @@ enum : unsigned { // flags
     FF_LIN = 2,    // read by the lineariser: a caller write invalidates the pass made a tick ahead (LinSched::caller_wrote)
     FF_PF = 4,     // owned by the path-following front end: a caller write makes it rewrite its rows (usvmpc_handle::pf_stale)
     FF_EXPORT = 8, // a multiplier read-back: the export runs first, and the field exists only once its buffers do (FieldDims::exported)
-    FF_TRACK = 16  // an obstacle-track field (usvmpc.hip: tracks_field)
+    FF_TRACK = 16, // an obstacle-track field (usvmpc.hip: tracks_field)
+    FF_COST = 32   // an objective value: evaluated by usv_cost_eval ahead of the copy, into buffers made on first use (usvmpc.hip: cost_enqueue)
 };
 
 struct FieldRow {
@@ -70,6 +71,10 @@ constexpr FieldRow FIELD_TABLE[FLD_COUNT] = {
     {"obs_vel",       FLD_OBS_VEL,       -1,          false, LEN_2K,   ST_1,  false, R_SET | R_GET | R_DEV,  FF_TRACK},
     {"clearance",     FLD_CLEARANCE,     -1,          false, LEN_1,    ST_1,  false, R_GET,                  FF_TRACK},
     {"clearance_min", FLD_CLEARANCE_MIN, -1,          false, LEN_1,    ST_1,  false, R_GET,                  FF_TRACK},
+    // (the objective value of the iterate the handle holds: cost_eval.hpp)
+    {"cost",          FLD_COST,          -1,          false, LEN_1,    ST_1,  false, R_GET | R_DEV,          FF_WHOLE | FF_COST},
+    {"cost_stage",    FLD_COST_STAGE,    -1,          false, LEN_1,    ST_N1, false, R_GET | R_DEV,          FF_COST},
+    {"cost_parts",    FLD_COST_PARTS,    -1,          false, LEN_3,    ST_1,  false, R_GET | R_DEV,          FF_WHOLE | FF_COST},
 };
 
 constexpr bool field_table_ordered()
@@ -105,6 +110,7 @@ inline int field_len(const FieldRow &r, const FieldDims &d)
     case LEN_K: return d.K;
     case LEN_NLAM: return d.nlam;
     case LEN_4: return 4;
+    case LEN_3: return 3;
     case LEN_1: break;
     }
     return 1;

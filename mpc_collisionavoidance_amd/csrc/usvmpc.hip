@@ -25,6 +25,7 @@
 #include "gfx950/lanes.hpp"
 
 #include "closed_loop_log.hpp"
+#include "cost_eval.hpp"
 #include "guidance.hpp"
 #include "host_spec.hpp"
 #include "lin_plan.hpp"
@@ -383,6 +384,201 @@ __global__ void __launch_bounds__(256) usv_log_record(LogRec R)
         R.sum_abs[t] = sa;
         R.sum_sq[t] = sq;
     }
+}
+
+// ---- Objective value (usvmpc_get "cost" / "cost_stage" / "cost_parts", usvmpc_eval_cost, usvmpc_cost_track; the arithmetic and the order of
+// every sum: cost_eval.hpp).  Both kernels read arrays a caller can get (x, u, yref, yref_e, sl, su, x0) and write cost memory only.
+// One 16-lane group per (instance, stage): lane r owns row r of V and of W (16 + 16 registers, from the transposed device table CostTab: a
+// kernel argument indexed at run time would be scratch - usv_log_record's trap) and loads element r of the stage's z and yref row, so a
+// group's loads are contiguous runs; z_j, r_j and the rows' shares of q reach the other lanes through lanes::bcast<j> in unrolled loops whose
+// bounds are compile-time constants - sequential sums, no butterfly.
+struct CostRows {
+    double V[COST_LANES], W[COST_LANES];
+};
+__device__ __forceinline__ void cost_load_rows(CostRows &R, const double *Vt, const double *Wt, int lane)
+{
+    sfor<0, COST_LANES>([&](auto j) { R.V[j] = Vt[j * COST_LANES + lane]; R.W[j] = Wt[j * COST_LANES + lane]; });
+}
+// q of the group's stage, in every lane: z and yr are this lane's entries, 0.0 beyond nz / ny.  Every loop runs to 16 over the zero-padded
+// tables without a guard (16 + 16 + 16 + 32 hoisted lane masks cost the kernel a hundred scalar registers): a padded term is 0.0 * 0.0, and
+// adding +0.0 to a sum that started from +0.0 leaves its bits as they are (such a sum is never -0.0) - cost_eval.hpp, "padding".
+__device__ __forceinline__ double cost_group_q(const CostRows &R, double z, double yr)
+{
+    double y = 0.0;
+    sfor<0, COST_LANES>([&](auto j) { y = cost_mac(y, R.V[j], lanes::bcast<j>(z)); });
+    const double r = cost_sub(y, yr);
+    double t = 0.0;
+    sfor<0, COST_LANES>([&](auto j) { t = cost_mac(t, R.W[j], lanes::bcast<j>(r)); });
+    const double p = cost_mul(r, t);
+    double q = 0.0;
+    sfor<0, COST_LANES>([&](auto i) { q = cost_add(q, lanes::bcast<i>(p)); });
+    return q;
+}
+// S of the group's stage, in every lane: t0 / t1 are this lane's cost_slack_term of rows lane / 16 + lane (0.0 beyond Ks)
+__device__ __forceinline__ double cost_group_S(double t0, double t1, int Ks)
+{
+    double S = 0.0;
+    sfor<0, COST_LANES>([&](auto i) { S = cost_add(S, lanes::bcast<i>(t0)); });
+    if (Ks > COST_LANES) sfor<0, COST_LANES>([&](auto i) { S = cost_add(S, lanes::bcast<i>(t1)); });
+    return S;
+}
+// what lane `lane` of a group loads for stage k < N of instance b: its entry of z = [u_k; xs] and of yref, its slack terms (xs: x_k, or x0).
+// SOFT false (hard h rows, or none): no slack term exists - neither loads nor registers for them.
+template <bool SOFT> struct CostIn;
+template <> struct CostIn<false> {
+    double z, yr;
+};
+template <> struct CostIn<true> {
+    double z, yr, sl0, su0, sl1, su1;
+};
+template <bool SOFT>
+__device__ __forceinline__ CostIn<SOFT> cost_load_stage(const CostArgs &A, const double *xs, long b, int k, int lane)
+{
+    CostIn<SOFT> I;
+    const long bk = b * A.N + k;
+    const int nz = A.nu + A.nx;
+    const double *pz = lane < A.nu ? A.u + bk * A.nu + lane : xs + (lane - A.nu);
+    I.z = lane < nz ? *pz : 0.0;
+    I.yr = lane < A.ny ? A.yref[bk * A.ny + lane] : 0.0;
+    if constexpr (SOFT) {
+        const double *sl = A.sl + bk * A.K, *su = A.su + bk * A.K;
+        I.sl0 = lane < A.Ks ? sl[lane] : 0.0;
+        I.su0 = lane < A.Ks ? su[lane] : 0.0;
+        I.sl1 = COST_LANES + lane < A.Ks ? sl[COST_LANES + lane] : 0.0;
+        I.su1 = COST_LANES + lane < A.Ks ? su[COST_LANES + lane] : 0.0;
+    }
+    return I;
+}
+// this lane's penalties of rows lane and 16 + lane (zero beyond Ks: the table is zero-padded)
+template <bool SOFT> struct CostPen;
+template <> struct CostPen<false> {};
+template <> struct CostPen<true> {
+    double zl0, zu0, Zl0, Zu0, zl1, zu1, Zl1, Zu1;
+};
+template <bool SOFT>
+__device__ __forceinline__ CostPen<SOFT> cost_load_pen(const CostTab *T, int lane)
+{
+    if constexpr (SOFT)
+        return CostPen<true>{T->zl[lane], T->zu[lane], T->Zl[lane], T->Zu[lane], T->zl[16 + lane], T->zu[16 + lane], T->Zl[16 + lane], T->Zu[16 + lane]};
+    else
+        return CostPen<false>{};
+}
+// ls_k and slack_k of the group's stage, in every lane (hard rows: slack_k = dt * 0.0)
+template <bool SOFT>
+__device__ __forceinline__ void cost_group_stage(const CostArgs &A, const CostRows &R, const CostPen<SOFT> &P, const CostIn<SOFT> &I, double &ls, double &slack)
+{
+    ls = cost_ls(A.dt, cost_group_q(R, I.z, I.yr));
+    double S = 0.0;
+    if constexpr (SOFT) {
+        const double t0 = cost_slack_term(P.zl0, P.zu0, P.Zl0, P.Zu0, I.sl0, I.su0);
+        const double t1 = cost_slack_term(P.zl1, P.zu1, P.Zl1, P.Zu1, I.sl1, I.su1);
+        S = cost_group_S(t0, t1, A.Ks);
+    }
+    slack = cost_mul(A.dt, S);
+}
+// the value lane `src` of the wave holds, as a wave-uniform number
+__device__ __forceinline__ double cost_from_lane(double v, int src)
+{
+    const long l = __builtin_bit_cast(long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(l & 0xffffffffL), src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(l >> 32), src);
+    return __builtin_bit_cast(double, (long)(((unsigned long)hi << 32) | lo));
+}
+
+// usv_cost_eval: ONE wave per instance (four to a workgroup).  The wave's four groups take four consecutive stages k < N at a time (a PASS) -
+// their loads of x, u, yref, sl and su join up into one contiguous run each.  The arithmetic of a pass is some 150 FP64 instructions in a
+// dependent chain, so what keeps HBM busy is how many passes' loads a wave has in flight: COST_AHEAD passes are loaded ahead of the one
+// being worked on, in a ring whose slots are compile-time indices (two doubles per lane and pass for hard rows, six for soft ones).  The
+// stages' values then enter the instance's three running sums one by one in stage order (wave-uniform numbers read from lanes 0, 16, 32,
+// 48), so the totals need neither a second pass nor a per-stage buffer for the two shares.  A group past stage N - 1 works on stage N - 1
+// again and neither stores nor enters the sums (control flow stays wave-uniform around the DPP reads).  Stage N comes last, on the terminal
+// tables, which take over the stage tables' registers.
+constexpr int COST_AHEAD = 4;
+template <bool SOFT>
+__global__ void __launch_bounds__(256) usv_cost_eval(CostArgs A)
+{
+    const long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= A.B) return; // (a whole wave)
+    const int lane = lanes::lane(), row = (int)lanes::wave_row();
+    const CostPen<SOFT> P = cost_load_pen<SOFT>(A.tab, lane);
+    CostRows R;
+    cost_load_rows(R, A.tab->Vt, A.tab->Wt, lane);
+    const double *xb = A.x + b * (long)(A.N + 1) * A.nx;
+    double total = 0.0, p_ls = 0.0, p_slack = 0.0;
+    const int last = A.N - 1;
+    auto load = [&](int k0) { // (the pass that starts at stage k0; past the end: stage N - 1 again)
+        const int k = k0 + row < last ? k0 + row : last;
+        return cost_load_stage<SOFT>(A, xb + (long)k * A.nx, b, k, lane);
+    };
+    CostIn<SOFT> ring[COST_AHEAD];
+    sfor<0, COST_AHEAD>([&](auto d) { ring[d] = load(4 * d); });
+    for (int k0 = 0; k0 < A.N; k0 += 4 * COST_AHEAD) {
+        sfor<0, COST_AHEAD>([&](auto d) {
+            const int kd = k0 + 4 * d;
+            if (kd < A.N) { // (wave-uniform)
+                const CostIn<SOFT> I = ring[d];
+                ring[d] = load(kd + 4 * COST_AHEAD);
+                double ls, slack;
+                cost_group_stage<SOFT>(A, R, P, I, ls, slack);
+                const double c = cost_add(ls, slack);
+                if (kd + row < A.N && lane == 0) A.cost_stage[b * (A.N + 1) + kd + row] = c;
+                sfor<0, 4>([&](auto g) {
+                    if (kd + g < A.N) {
+                        total = cost_add(total, cost_from_lane(c, 16 * g));
+                        if constexpr (SOFT) {
+                            p_ls = cost_add(p_ls, cost_from_lane(ls, 16 * g));
+                            p_slack = cost_add(p_slack, cost_from_lane(slack, 16 * g));
+                        }
+                    }
+                });
+            }
+        });
+    }
+    // (hard rows: slack_k = dt * 0.0 = +0.0 and c_k = ls_k + 0.0 = ls_k to the bit - ls_k is never -0.0 - so the sum of the ls_k is the
+    // sum of the c_k, the same additions in the same order, and the sum of the slack_k stays +0.0)
+    if constexpr (!SOFT) p_ls = total;
+    cost_load_rows(R, A.tab->Vte, A.tab->Wte, lane);
+    const double zN = lane < A.nx ? xb[(long)A.N * A.nx + lane] : 0.0;
+    const double yN = lane < A.ny_e ? A.yref_e[b * A.ny_e + lane] : 0.0;
+    const double cN = cost_mul(0.5, cost_group_q(R, zN, yN));
+    total = cost_add(total, cN);
+    if (threadIdx.x % 64 == 0) {
+        A.cost_stage[b * (A.N + 1) + A.N] = cN;
+        A.cost[b] = total;
+        A.parts[b * 3 + 0] = p_ls;
+        A.parts[b * 3 + 1] = cN;
+        A.parts[b * 3 + 2] = p_slack;
+    }
+}
+
+// usv_cost_track: sum[b] += c_0(x0[b], u[b][0], yref[b][0], sl[b][0], su[b][0]), a 16-lane group per instance (the same rows-over-lanes
+// arithmetic: every lane's load is its element of a contiguous run, none walks a row of its own), enqueued by a hand-over AHEAD of its own
+// kernel so that x0 is still the state the solve saw.  A group serves up to COST_TRACK_EACH instances, G groups apart, so that its 32
+// table loads are paid once, with the next instance's loads issued ahead of the current one's arithmetic.  A group past the batch works on
+// the last instance again and stores nothing.
+constexpr int COST_TRACK_EACH = 4;
+template <bool SOFT>
+__global__ void __launch_bounds__(256) usv_cost_track(CostArgs A)
+{
+    const long g = lanes::group_linear(), G = (long)gridDim.x * (blockDim.x >> 4);
+    const int lane = lanes::lane();
+    const CostPen<SOFT> P = cost_load_pen<SOFT>(A.tab, lane);
+    CostRows R;
+    cost_load_rows(R, A.tab->Vt, A.tab->Wt, lane);
+    auto load = [&](long b) {
+        b = b < A.B ? b : A.B - 1;
+        return cost_load_stage<SOFT>(A, A.x0 + b * A.nx, b, 0, lane);
+    };
+    CostIn<SOFT> In = load(g);
+    sfor<0, COST_TRACK_EACH>([&](auto it) {
+        const long b = g + it * G;
+        const CostIn<SOFT> I = In;
+        if (it + 1 < COST_TRACK_EACH) In = load(b + G);
+        double ls, slack;
+        cost_group_stage<SOFT>(A, R, P, I, ls, slack);
+        const double c = cost_add(ls, slack);
+        if (b < A.B && lane == 0) A.sum[b] = cost_add(A.sum[b], c);
+    });
 }
 
 // ---- Obstacle tracks (option "obstacle_tracks"; the arithmetic: obstacle_tracks.hpp).
@@ -972,6 +1168,12 @@ struct usvmpc_handle {
     double *log_x = nullptr, *log_u = nullptr, *log_sums = nullptr; // [capacity][B][nsel], [capacity][B][nu], [2][B][n_err]
     int *log_status = nullptr;  // [capacity][B]
     LogRec log_rec = {};
+    // Objective value (usvmpc_get "cost" .., usvmpc_eval_cost, usvmpc_cost_track): everything on first use - a handle that never asks for a
+    // cost allocates nothing and launches what it always did.
+    CostTab *d_cost_tab = nullptr;  // the kernels' tables (cost_eval.hpp)
+    double *d_cost = nullptr, *d_cost_stage = nullptr, *d_cost_parts = nullptr; // [B], [B][N+1], [B][3]
+    double *d_cost_sum = nullptr;   // [B] the realised closed-loop cost while tracking runs (nullptr: it does not)
+    long long cost_count = 0;       // hand-overs that entered it
 };
 
 // Kernels::lin / lin_pair: usv_linearize for one and several RK4 steps (MULTI), every MODE
@@ -1108,8 +1310,9 @@ void *field_ptr(usvmpc_handle *h, FieldId id)
     const DevPtrs &P = h->ptrs;
     const void *const by_id[] = {P.x, P.u, P.status, P.x0, P.yref, P.yref_e, P.p, P.lh, // (in FieldId's order)
                                  P.pi, P.sl, P.su, P.res, P.obs_tmin, P.nlp_res, P.lam_out, P.t_out, P.qp_iter, P.qp_status, P.sqp_iter,
-                                 h->d_obs_pos, h->d_obs_vel, h->d_clear, h->d_clear_min};
-    static_assert(sizeof by_id / sizeof *by_id == FLD_COUNT && FLD_PI == 8 && FLD_QP_ITER == 16 && FLD_OBS_POS == 19, "one pointer per row of the field table");
+                                 h->d_obs_pos, h->d_obs_vel, h->d_clear, h->d_clear_min, h->d_cost, h->d_cost_stage, h->d_cost_parts};
+    static_assert(sizeof by_id / sizeof *by_id == FLD_COUNT && FLD_PI == 8 && FLD_QP_ITER == 16 && FLD_OBS_POS == 19 && FLD_COST == 23,
+                  "one pointer per row of the field table");
     return const_cast<void *>(by_id[id]);
 }
 
@@ -1262,6 +1465,80 @@ int tracks_step(usvmpc_handle *h, double T)
     return 0;
 }
 
+// ---- objective value (usvmpc_handle: d_cost_tab ..): what every entry point refuses, the buffers on first use, the two launches
+int cost_check(usvmpc_handle *h)
+{
+    // (the slack values of soft state bounds are not among the arrays a caller can get: their share of the cost could not be restated)
+    if (h->spec.any_bsoft) { h->err = "cost: not built for soft state bounds"; return USVMPC_E_ARG; }
+    return 0;
+}
+
+int cost_tab_ensure(usvmpc_handle *h)
+{
+    if (h->d_cost_tab) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const usvmpc_desc &d = h->desc;
+    CostTab T;
+    cost_fill_tab(T, h->nx, h->nu, h->ny, h->ny_e, h->soft ? h->K : 0, d.Vu, d.Vx, d.W, d.Vx_e, d.W_e, d.zl, d.zu, d.Zl, d.Zu);
+    CostTab *tab = nullptr;
+    if (dev_alloc(h, &tab, 1, false)) return USVMPC_E_HIP;
+    HIP_TRY(h, hipMemcpyAsync(tab, &T, sizeof(CostTab), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (T is a local)
+    h->d_cost_tab = tab;
+    return 0;
+}
+
+int cost_alloc(usvmpc_handle *h)
+{
+    if (h->d_cost) return 0;
+    const int rct = cost_tab_ensure(h);
+    if (rct) return rct;
+    const size_t B = (size_t)h->B;
+    double *c = nullptr, *cs = nullptr, *cp = nullptr;
+    if (dev_alloc(h, &c, B, true) || dev_alloc(h, &cs, B * (size_t)(h->N + 1), true) || dev_alloc(h, &cp, B * 3, true)) return USVMPC_E_HIP;
+    h->d_cost = c; h->d_cost_stage = cs; h->d_cost_parts = cp;
+    return 0;
+}
+
+CostArgs cost_args(const usvmpc_handle *h)
+{
+    CostArgs a = {};
+    const DevPtrs &P = h->ptrs;
+    a.tab = h->d_cost_tab;
+    a.x = P.x; a.u = P.u; a.yref = P.yref; a.yref_e = P.yref_e; a.sl = P.sl; a.su = P.su; a.x0 = P.x0;
+    a.cost_stage = h->d_cost_stage; a.cost = h->d_cost; a.parts = h->d_cost_parts; a.sum = h->d_cost_sum;
+    a.B = h->B; a.N = h->N; a.nx = h->nx; a.nu = h->nu; a.ny = h->ny; a.ny_e = h->ny_e;
+    a.K = h->K; a.Ks = h->soft ? h->K : 0;
+    a.dt = h->spec.dt;
+    return a;
+}
+
+// usv_cost_eval enqueued on the main stream, behind the upload of pending host writes (it reads x, u, yref).  No caller write: it writes cost
+// memory only, so the pipelined lineariser's pass made a tick ahead stands (as for usv_log_record).
+int cost_enqueue(usvmpc_handle *h)
+{
+    int rc = cost_check(h);
+    if (rc) return rc;
+    rc = cost_alloc(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    rc = mirror_flush(h);
+    if (rc) return rc;
+    hipLaunchKernelGGL(h->soft && h->K > 0 ? usv_cost_eval<true> : usv_cost_eval<false>, dim3((unsigned)((h->B + 3) / 4)), dim3(256), 0, h->stream, cost_args(h));
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// a hand-over of a handle that tracks its realised cost (usvmpc_advance / usvmpc_advance_sim, behind the mirror's upload and ahead of their own kernel)
+int cost_handover(usvmpc_handle *h)
+{
+    hipLaunchKernelGGL(h->soft && h->K > 0 ? usv_cost_track<true> : usv_cost_track<false>, dim3((unsigned)((h->B + 16 * COST_TRACK_EACH - 1) / (16 * COST_TRACK_EACH))), dim3(256), 0,
+                       h->stream, cost_args(h));
+    HIP_TRY(h, hipGetLastError());
+    h->cost_count++;
+    return 0;
+}
+
 // usvmpc_set / usvmpc_get: the name resolved through the field table, validated once, then either a memcpy into / out of the pinned mirror
 // (HostMirror says whether, and what that leaves to upload) or one copy to / from the device, synchronised
 int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, size_t n, bool set)
@@ -1279,6 +1556,10 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
     if (!set && (flags & FF_EXPORT)) {
         const int rce = ensure_export(h);
         if (rce) return rce;
+    }
+    if (!set && (flags & FF_COST)) {
+        const int rcc = cost_check(h);
+        if (rcc) return rcc;
     }
     Field f;
     if (resolve(row, stage, field_dims(h), set, f)) {
@@ -1319,6 +1600,10 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
     HIP_TRY(h, hipSetDevice(h->device));
     if (!set) { // (a get of a field with pending writes sees them)
         const int rc = mirror_flush(h);
+        if (rc) return rc;
+    }
+    if (!set && (f.row->flags & FF_COST)) { // (an objective value: evaluated now, of the iterate the device holds; no staleness state is kept)
+        const int rc = cost_enqueue(h);
         if (rc) return rc;
     }
     const int rc = exec_copy(h, (char *)field_ptr(h, f.row->id) + span.off, (char *)host, span.width, span, set);
@@ -2068,8 +2353,22 @@ int usvmpc_solve_sqp(usvmpc_handle *h, int *status)
 int usvmpc_get_device_ptr(usvmpc_handle *h, const char *field, void **dptr)
 {
     if (!h || !dptr) return USVMPC_E_ARG;
+    if (field && std::strcmp(field, "cost_tracked") == 0) { // (no field of the table: it exists only while tracking runs)
+        if (!h->d_cost_sum) { h->err = "cost_tracked: no tracking is running (usvmpc_cost_track)"; return USVMPC_E_ARG; }
+        *dptr = h->d_cost_sum;
+        return 0;
+    }
     const FieldRow *row = find_field(field);
     if (!row || !(row->rights & R_DEV)) { h->err = std::string("unknown field '") + (field ? field : "") + "'"; return USVMPC_E_FIELD; }
+    if (row->flags & FF_COST) {
+        // cost memory only: nothing a lineariser reads and nothing the host mirror holds is exposed - the pipeline keeps running
+        int rcc = cost_check(h);
+        if (rcc) return rcc;
+        rcc = cost_alloc(h);
+        if (rcc) return rcc;
+        *dptr = field_ptr(h, row->id);
+        return 0;
+    }
     if (row->flags & FF_TRACK) {
         // a track field: the caller's own kernels may move the obstacles behind the handle's back, so the prediction runs before every solve
         // from now on.  Nothing a lineariser reads is exposed: the pipeline keeps running.
@@ -2440,6 +2739,47 @@ int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr)
     return 0;
 }
 
+// ---- the objective value: usv_cost_eval on demand, the realised closed-loop cost hand-over by hand-over
+int usvmpc_eval_cost(usvmpc_handle *h)
+{
+    if (!h) return USVMPC_E_ARG;
+    return cost_enqueue(h);
+}
+
+int usvmpc_cost_track(usvmpc_handle *h, int on)
+{
+    if (!h) return USVMPC_E_ARG;
+    const int rcc = cost_check(h);
+    if (rcc) return rcc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!on) {
+        if (h->d_cost_sum) dev_free(h, h->d_cost_sum, (size_t)h->B * sizeof(double));
+        h->d_cost_sum = nullptr;
+        return 0;
+    }
+    const int rct = cost_tab_ensure(h);
+    if (rct) return rct;
+    if (!h->d_cost_sum) {
+        double *s = nullptr;
+        if (dev_alloc(h, &s, (size_t)h->B, false)) return USVMPC_E_HIP;
+        h->d_cost_sum = s;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_cost_sum, 0, (size_t)h->B * sizeof(double), h->stream)); // (behind the hand-overs already enqueued)
+    h->cost_count = 0;
+    return 0;
+}
+
+int usvmpc_cost_tracked(usvmpc_handle *h, double *sum, long long *count)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!h->d_cost_sum) { h->err = "cost_tracked: no tracking is running (usvmpc_cost_track)"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (sum) HIP_TRY(h, hipMemcpyAsync(sum, h->d_cost_sum, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (count) *count = h->cost_count;
+    return 0;
+}
+
 int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
 {
     if (!h) return USVMPC_E_ARG;
@@ -2451,6 +2791,10 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
     if (h->log.on) { // (ahead of the kernel that overwrites x0)
         const int rcl = log_handover(h);
         if (rcl) return rcl;
+    }
+    if (h->d_cost_sum) { // (likewise: c_0 of the state the solve saw)
+        const int rcc = cost_handover(h);
+        if (rcc) return rcc;
     }
     const long n = (long)h->B * h->nx;
     hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->opt.noise_mask,
@@ -2494,6 +2838,10 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     if (h->log.on) { // (ahead of the kernel that overwrites x0)
         const int rcl = log_handover(h);
         if (rcl) return rcl;
+    }
+    if (h->d_cost_sum) {
+        const int rcc = cost_handover(h);
+        if (rcc) return rcc;
     }
     const dim3 grid((unsigned)((h->B + 255) / 256)), block(256);
     switch (h->desc.model) {
