@@ -442,6 +442,35 @@ int usvmpc_pf_state(usvmpc_handle *h, int *wp_index, int *finish_tick, double *m
 int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel);
 int usvmpc_pf_world_step(usvmpc_handle *h, double T);
 int usvmpc_pf_world_read(usvmpc_handle *h, double *world, double *vel);
+/* VESSEL ENCOUNTERS: a scene's vessels as each other's moving obstacles (the arithmetic: csrc/fleet_world.hpp).  The batch is cut into scenes
+ * of scene_size = S consecutive instances (scene s: instances s S .. s S + S - 1; shards of a larger batch must be cut at multiples of S).
+ * Every instance keeps its own waypoints, mission state and OCP, and sees the other S - 1 vessels of its scene as moving world entries that
+ * every DEVICE-RESIDENT prepare refreshes on the device (kernel usv_pf_fleet_gather, ahead of the prepare's own kernel on the handle's stream);
+ * a tick stays prepare -> solve -> publish -> advance, no synchronisation.
+ *   fleet, scene_size >= 2: the world list becomes the caller's n_fixed entries followed by S - 1 fleet entries the front end owns, parked at
+ *             (1000, 1000, 0) with velocity 0 until the first gather.  The world counts as moving from then on ("static_obstacles" off;
+ *             option "pf_predict" 0 holds the scene still inside the horizon): velocities already given to the fixed entries are kept, a world
+ *             that was at rest gets zero velocities.  With a = i mod S, fleet slot e = 0 .. S-2 of instance i is vessel
+ *             j = i - a + (e < a ? e : e + 1), and list index n_fixed + e receives from x0 as usvmpc_advance / usvmpc_advance_sim left it
+ *                 X = x0_j[10], Y = x0_j[11], R = radius, sog = sqrt(x0_j[3]^2 + x0_j[4]^2), vX = sog * x0_j[2], vY = sog * x0_j[1]
+ *             (x0[1], x0[2]: the model's sin / cos of the course angle; no trigonometric call, every product and sum rounded on its own).
+ *             The gather also keeps, per instance and over the other vessels of its scene, the smallest d = sqrt(dx^2 + dy^2) between the
+ *             two positions and the prepare it was met at - for every instance, whatever its mission phase: a vessel whose mission is over
+ *             is still in the water and is still gathered by the others.
+ *   fleet, scene_size 0 or 1: the fleet is off and the list is cut back to the fixed entries, which keep their velocities
+ *             (usvmpc_pf_world_vel(NULL) puts the world at rest as ever).
+ *   While the fleet is on: usvmpc_pf_world takes the fixed entries only (n_world <= 64 - (S - 1)) and keeps the fleet slots (the fixed
+ *             entries' velocities too when n_world is unchanged, else they are zero); usvmpc_pf_world_vel takes [B][n_fixed][2];
+ *             usvmpc_pf_world_read returns all n_fixed + S - 1 entries as the device holds them; usvmpc_pf_world_step moves every entry - the
+ *             fleet slots are overwritten by the next gather.
+ *   USVMPC_E_ARG with a message, nothing changed: another model; no usvmpc_pf_reset or no world list yet (an empty list will do);
+ *             B % scene_size != 0; n_fixed + S - 1 > 64; a negative or non-finite radius; option "obstacle_tracks" on (and switching it on
+ *             while the fleet is on); a HOST-FED prepare while the fleet is on (the scene exists on the device only);
+ *             usvmpc_pf_world_vel(NULL) while the fleet is on.
+ *   fleet_state: min_separation [B] (1e300 after usvmpc_pf_reset; a NaN never wins), separation_tick [B] (prepares since reset, from 0;
+ *             -1: none yet).  Either may be NULL. */
+int usvmpc_pf_fleet(usvmpc_handle *h, int scene_size, double radius);
+int usvmpc_pf_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick);
 /* Profiling aid: stream `nplanes` workspace planes with the solver kernels' access instruction
  * (kernel usv_calib_stream) and report the exact byte counts, to calibrate HBM PMC counters.
  * Overwrites solver scratch; the next usvmpc_solve re-initialises it. */

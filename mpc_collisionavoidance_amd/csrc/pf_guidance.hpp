@@ -64,6 +64,8 @@ struct PfPtrs {
     double *thr_port, *thr_stbd, *Tx, *Tz, *speed; // [B] published
     float *e_u, *e_ye;
     int *active;
+    double *min_sep;     // [B] smallest distance to a vessel of the instance's scene (fleet_world.hpp; 1e300 after a reset)
+    int *sep_tick;       // [B] the prepare it was met at (-1: none yet)
 };
 
 // velocityCallback :201-203

@@ -26,6 +26,7 @@
 
 #include "closed_loop_log.hpp"
 #include "cost_eval.hpp"
+#include "fleet_world.hpp"
 #include "guidance.hpp"
 #include "host_spec.hpp"
 #include "lin_plan.hpp"
@@ -634,6 +635,7 @@ static __global__ void usv_pf_reset(PfPtrs F, int B)
     F.last[3 * b] = F.last[3 * b + 1] = F.last[3 * b + 2] = __builtin_nan("");
     F.u[b] = 0.0; F.ye[b] = 0.0;
     F.min_clear[b] = 1e300;
+    F.min_sep[b] = 1e300; F.sep_tick[b] = -1;
     F.thr_port[b] = 0.0; F.thr_stbd[b] = 0.0; F.Tx[b] = 0.0; F.Tz[b] = 0.0; F.speed[b] = 0.0;
     F.e_u[b] = 0.0f; F.e_ye[b] = 0.0f;
     F.active[b] = 0;
@@ -799,6 +801,31 @@ __global__ void __launch_bounds__(256) usv_pf_world_step(double *world, const do
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     pf_world_step(world + 3 * i, wvel + 2 * i, T);
+}
+
+// usv_pf_fleet_gather: vessel encounters (fleet_world.hpp) - the other S - 1 vessels of an instance's scene, as the plant left them in x0,
+// become the fleet entries behind the n_fixed fixed ones of its world list.  A kernel of its own ahead of usv_pf_prepare, which rewrites
+// x0[1..3] while a scene-mate in another workgroup would still be reading them; this one reads x0 only.  One thread per (instance, fleet
+// slot), the slot fastest: a thread loads six doubles of one scene-mate (the scene's states are S neighbouring 112-byte rows) and stores one
+// entry (24 bytes) and one velocity (16 bytes); the threads of an instance store its S - 1 entries as one run, a wave's runs lying
+// 24 nworld bytes apart.  The separation bookkeeping needs all S - 1 distances of an instance in one place: its slot-0 thread takes the
+// S - 1 positions again (lines its own wave has just loaded) - no atomics, no LDS.
+__global__ void __launch_bounds__(256) usv_pf_fleet_gather(const double *x0, double *world, double *wvel, double *min_sep, int *sep_tick,
+                                                           long B, int S, int n_fixed, double radius, int tick)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = S - 1;
+    if (t >= B * f) return;
+    const long i = t / f;
+    const int e = (int)(t - i * f);
+    const long at = i * (n_fixed + f) + n_fixed + e; // the entry's place in the [B][nworld] lists
+    fleet_entry(x0 + fleet_vessel(i, e, S) * FLEET_NX, radius, world + 3 * at, wvel + 2 * at);
+    if (e != 0) return;
+    double m = min_sep[i];
+    int mt = sep_tick[i];
+    for (int q = 0; q < f; q++) fleet_closest(fleet_separation(x0 + i * FLEET_NX, x0 + fleet_vessel(i, q, S) * FLEET_NX), tick, m, mt);
+    min_sep[i] = m;
+    sep_tick[i] = mt;
 }
 
 // usv_pf_publish: the node's outputs after the solve, one lane per instance (a dozen scalars each).  An active instance reads the thrusters
@@ -1094,6 +1121,11 @@ struct usvmpc_handle {
     size_t pf_wvel_cap;       // doubles
     bool pf_world_set;        // usvmpc_pf_world has been called
     bool pf_moving;           // velocities are set for the current list
+    // Vessel encounters (usvmpc_pf_fleet, fleet_world.hpp): scenes of pf_fleet_S consecutive instances; the world list is then the caller's
+    // pf_nfixed entries followed by pf_fleet_S - 1 fleet slots (pf.nworld counts both), which a resident prepare gathers from x0
+    int pf_fleet_S = 0;       // 0: no fleet
+    int pf_nfixed = 0;        // (meaningful while a fleet is on)
+    double pf_fleet_radius = 0.0;
     int last_wide;            // the last RTI launch ran on the wide kernel
     // hand-over of long runners to a follow-up launch (option "handover_iter")
     int *d_susp_count, *d_susp_list; // [RING] instances each of the last launches handed over / [B] their groups
@@ -2891,6 +2923,7 @@ static const char *option_refused(const usvmpc_handle *h, OptId id, double v)
     switch (id) {
     case OPT_OBSTACLE_TRACKS: // (off: p stays as it stands and is the caller's again)
         if (v == 0.0) break;
+        if (h->pf_fleet_S) return "obstacle_tracks: a fleet is on (usvmpc_pf_fleet) and the path-following front end owns p on this handle";
         if (!h->tracks_pos_set) return "obstacle_tracks: set \"obs_pos\" before switching the option on";
         if (h->pf_ready) return "obstacle_tracks: the path-following front end owns p on this handle";
         if (h->pf_moving) return "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle";
@@ -3316,7 +3349,7 @@ static int pf_alloc(usvmpc_handle *h)
         dev_alloc(h, &F.yref_writes, 1, true) || dev_alloc(h, &F.thr_port, B, true) || dev_alloc(h, &F.thr_stbd, B, true) ||
         dev_alloc(h, &F.Tx, B, true) || dev_alloc(h, &F.Tz, B, true) || dev_alloc(h, &F.speed, B, true) || dev_alloc(h, &F.e_u, B, true) ||
         dev_alloc(h, &F.e_ye, B, true) || dev_alloc(h, &F.active, B, true) || dev_alloc(h, &h->pf_vel, B * 3, true) ||
-        dev_alloc(h, &h->pf_pose, B * 3, true))
+        dev_alloc(h, &h->pf_pose, B * 3, true) || dev_alloc(h, &F.min_sep, B, true) || dev_alloc(h, &F.sep_tick, B, true))
         return USVMPC_E_HIP;
     F.max_radius = 100.0;
     h->pf_alloc = true;
@@ -3351,6 +3384,55 @@ int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
     return pf_apply_static(h);
 }
 
+// the [B][K] slot tracks a moving prepare leaves between its two steps
+static int pf_alloc_tracks(usvmpc_handle *h)
+{
+    PfPtrs &F = h->pf;
+    if (!F.trk_pv && (dev_alloc(h, &F.trk_pv, (size_t)h->B * (size_t)(h->K ? h->K : 1) * 4, true) ||
+                      dev_alloc(h, &F.trk_lh, (size_t)h->B * (size_t)(h->K ? h->K : 1), true)))
+        return USVMPC_E_HIP;
+    return 0;
+}
+
+// Vessel encounters: the world list laid out anew - n1_fixed fixed entries, f1 fleet slots behind them (fleet_world.hpp: fleet_relayout, which
+// says what is kept) - through the host: a set-up call, never part of a tick.  fixed: the new fixed entries [B][n1_fixed][3]; null keeps the
+// present ones (n1_fixed is then their count).  Afterwards the list has velocities, whether the world moved before or not.
+static int pf_relayout(usvmpc_handle *h, const double *fixed, int n1_fixed, int f1)
+{
+    PfPtrs &F = h->pf;
+    const size_t B = h->B;
+    const int f0 = fleet_slots(h->pf_fleet_S), n0 = F.nworld, n0_fixed = n0 - f0, n1 = n1_fixed + f1;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step on the old list may be in flight)
+    std::vector<double> w0(B * (size_t)n0 * 3), v0(B * (size_t)n0 * 2), w1(B * (size_t)n1 * 3), v1(B * (size_t)n1 * 2);
+    if (!w0.empty()) HIP_TRY(h, hipMemcpyAsync(w0.data(), F.world, w0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (!v0.empty() && h->pf_moving) HIP_TRY(h, hipMemcpyAsync(v0.data(), h->pf_wvel, v0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; b++)
+        fleet_relayout(w0.data() + b * (size_t)n0 * 3, h->pf_moving ? v0.data() + b * (size_t)n0 * 2 : nullptr, n0_fixed, f0,
+                       fixed ? fixed + b * (size_t)n1_fixed * 3 : nullptr, n1_fixed, f1, w1.data() + b * (size_t)n1 * 3, v1.data() + b * (size_t)n1 * 2);
+    if (w1.size() > h->pf_world_cap) {
+        dev_free(h, const_cast<double *>(F.world), h->pf_world_cap * sizeof(double));
+        F.world = nullptr; h->pf_world_cap = 0;
+        double *d = nullptr;
+        if (dev_alloc(h, &d, w1.size(), false)) return USVMPC_E_HIP;
+        F.world = d;
+        h->pf_world_cap = w1.size();
+    }
+    if (v1.size() > h->pf_wvel_cap || !h->pf_wvel) {
+        dev_free(h, h->pf_wvel, h->pf_wvel_cap * sizeof(double));
+        h->pf_wvel = nullptr; h->pf_wvel_cap = 0;
+        if (dev_alloc(h, &h->pf_wvel, v1.size(), false)) return USVMPC_E_HIP;
+        h->pf_wvel_cap = v1.size();
+    }
+    if (pf_alloc_tracks(h)) return USVMPC_E_HIP;
+    if (!w1.empty()) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.world), w1.data(), w1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!v1.empty()) HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, v1.data(), v1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    F.nworld = n1;
+    return 0;
+}
+
 int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
 {
     if (!h) return USVMPC_E_ARG;
@@ -3359,6 +3441,18 @@ int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double m
     if (n_world < 0 || n_world > PF_LMAX) { h->err = "pf_world: n_world must lie in 0.." + std::to_string(PF_LMAX); return USVMPC_E_ARG; }
     if (n_world > 0 && !world) { h->err = "pf_world: null world list"; return USVMPC_E_ARG; }
     if (!(max_radius == max_radius)) { h->err = "pf_world: max_radius is NaN"; return USVMPC_E_ARG; }
+    if (h->pf_fleet_S) { // (the fixed entries only; the fleet slots stay)
+        if (!fleet_fits(n_world, h->pf_fleet_S)) {
+            h->err = "pf_world: a fleet is on and owns " + std::to_string(fleet_slots(h->pf_fleet_S)) + " entries of the list: n_world must lie in 0.." +
+                     std::to_string(PF_LMAX - fleet_slots(h->pf_fleet_S));
+            return USVMPC_E_ARG;
+        }
+        rc = pf_relayout(h, world, n_world, fleet_slots(h->pf_fleet_S));
+        if (rc) return rc;
+        h->pf_nfixed = n_world;
+        h->pf.max_radius = max_radius;
+        return 0;
+    }
     rc = pf_alloc(h);
     if (rc) return rc;
     PfPtrs &F = h->pf;
@@ -3391,26 +3485,36 @@ int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel)
     int rc = pf_check(h);
     if (rc) return rc;
     if (!vel) { // back to a world at rest
+        if (h->pf_fleet_S) { h->err = "pf_world_vel: a fleet is on and its world moves; switch it off first (usvmpc_pf_fleet with scene_size 0)"; return USVMPC_E_ARG; }
         h->pf_moving = false;
         return h->pf_ready ? pf_apply_static(h) : 0;
     }
     if (!h->pf_world_set) { h->err = "pf_world_vel: no world list yet (usvmpc_pf_world first)"; return USVMPC_E_ARG; }
     if (h->opt.tracks_on) { h->err = "pf_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
     PfPtrs &F = h->pf;
-    const size_t need = (size_t)h->B * (size_t)F.nworld * 2;
+    const int nvel = h->pf_fleet_S ? h->pf_nfixed : F.nworld; // (a fleet's slots have the velocities the gather gave them)
+    const size_t need = (size_t)h->B * (size_t)nvel * 2;
     for (size_t i = 0; i < need; i++)
         if (vel[i] - vel[i] != 0.0) { h->err = "pf_world_vel: entry " + std::to_string(i) + " is not finite"; return USVMPC_E_ARG; }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step that reads the old velocities may be in flight)
+    if (h->pf_fleet_S) { // [B][n_fixed][2] into the head of every instance's [nworld][2]
+        const size_t row = (size_t)F.nworld * 2, head = (size_t)nvel * 2;
+        std::vector<double> v(h->B * row);
+        HIP_TRY(h, hipMemcpyAsync(v.data(), h->pf_wvel, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < (size_t)h->B; b++) std::copy(vel + b * head, vel + (b + 1) * head, v.begin() + (long)(b * row));
+        HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
     if (need > h->pf_wvel_cap || !h->pf_wvel) { // (an empty list moves too: a non-null pointer is what tells prepare so)
         dev_free(h, h->pf_wvel, h->pf_wvel_cap * sizeof(double));
         h->pf_wvel = nullptr; h->pf_wvel_cap = 0;
         if (dev_alloc(h, &h->pf_wvel, need, false)) return USVMPC_E_HIP;
         h->pf_wvel_cap = need;
     }
-    if (!F.trk_pv && (dev_alloc(h, &F.trk_pv, (size_t)h->B * (size_t)(h->K ? h->K : 1) * 4, true) ||
-                      dev_alloc(h, &F.trk_lh, (size_t)h->B * (size_t)(h->K ? h->K : 1), true)))
-        return USVMPC_E_HIP;
+    if (pf_alloc_tracks(h)) return USVMPC_E_HIP;
     if (need) HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, vel, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->pf_moving = true;
@@ -3455,11 +3559,21 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     if (rc) return rc;
     if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
     if ((vel_uvr == nullptr) != (pose == nullptr)) { h->err = "pf_prepare: give both vel_uvr and pose, or neither (device-resident)"; return USVMPC_E_ARG; }
+    if (vel_uvr && h->pf_fleet_S) {
+        h->err = "pf_prepare: a fleet is on and its scene exists on the device only; prepare device-resident (both NULL)";
+        return USVMPC_E_ARG;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     rc = mirror_flush(h);
     if (rc) return rc;
     rc = spec_cancel(h); // (a caller write of yref as far as the pipelined lineariser is concerned: pf_guidance.hpp)
     if (rc) return rc;
+    if (h->pf_fleet_S) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_pf_prepare rewrites x0[1..3]
+        const long n = (long)h->B * fleet_slots(h->pf_fleet_S);
+        hipLaunchKernelGGL(usv_pf_fleet_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs.x0, const_cast<double *>(h->pf.world),
+                           h->pf_wvel, h->pf.min_sep, h->pf.sep_tick, (long)h->B, h->pf_fleet_S, h->pf_nfixed, h->pf_fleet_radius, h->pf_tick);
+        HIP_TRY(h, hipGetLastError());
+    }
     PfPtrs F = h->pf;
     F.margin = h->opt.pf_margin;
     F.wvel = (h->pf_moving && h->opt.pf_predict) ? h->pf_wvel : nullptr; // (held still inside the horizon: the prepare of a world at rest)
@@ -3516,6 +3630,58 @@ int usvmpc_pf_state(usvmpc_handle *h, int *wp_index, int *finish_tick, double *m
     if (finish_tick) HIP_TRY(h, hipMemcpyAsync(finish_tick, F.finish_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (min_clearance) HIP_TRY(h, hipMemcpyAsync(min_clearance, F.min_clear, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (yref_writes) HIP_TRY(h, hipMemcpyAsync(yref_writes, F.yref_writes, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int usvmpc_pf_fleet(usvmpc_handle *h, int scene_size, double radius)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_ready || !h->pf_world_set) {
+        h->err = "pf_fleet: usvmpc_pf_reset and a world list (usvmpc_pf_world; an empty one will do) come first";
+        return USVMPC_E_ARG;
+    }
+    if (scene_size < 0) { h->err = "pf_fleet: scene_size must not be negative"; return USVMPC_E_ARG; }
+    if (!fleet_on(scene_size)) { // off: the list is cut back to the fixed entries, which keep their velocities
+        if (!h->pf_fleet_S) return 0;
+        rc = pf_relayout(h, nullptr, h->pf_nfixed, 0);
+        if (rc) return rc;
+        h->pf_fleet_S = 0;
+        return 0;
+    }
+    const int n_fixed = h->pf_fleet_S ? h->pf_nfixed : h->pf.nworld;
+    if (h->opt.tracks_on) { h->err = "pf_fleet: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    if (!fleet_scene_ok(h->B, scene_size)) {
+        h->err = "pf_fleet: the batch of " + std::to_string(h->B) + " is not a whole number of scenes of " + std::to_string(scene_size);
+        return USVMPC_E_ARG;
+    }
+    if (!fleet_fits(n_fixed, scene_size)) {
+        h->err = "pf_fleet: " + std::to_string(n_fixed) + " fixed entries and " + std::to_string(scene_size - 1) + " fleet entries exceed the " +
+                 std::to_string(PF_LMAX) + " of a world list";
+        return USVMPC_E_ARG;
+    }
+    if (!fleet_radius_ok(radius)) { h->err = "pf_fleet: radius must be finite and not negative"; return USVMPC_E_ARG; }
+    rc = pf_relayout(h, nullptr, n_fixed, scene_size - 1);
+    if (rc) return rc;
+    h->pf_fleet_S = scene_size;
+    h->pf_nfixed = n_fixed;
+    h->pf_fleet_radius = radius;
+    h->pf_moving = true;
+    return pf_apply_static(h);
+}
+
+int usvmpc_pf_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = pf_check(h);
+    if (rc) return rc;
+    if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t B = h->B;
+    if (min_separation) HIP_TRY(h, hipMemcpyAsync(min_separation, h->pf.min_sep, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (separation_tick) HIP_TRY(h, hipMemcpyAsync(separation_tick, h->pf.sep_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -386,3 +386,79 @@ def make_ca_missions(B, L, seed=0, moving=False):
         rv = np.random.default_rng([seed, 1])
         out["world_vel"] = np.stack([rv.uniform(-CA_DRIFT, CA_DRIFT, (B, L)), np.zeros((B, L))], axis=2)
     return out
+
+
+# ---- vessel encounters for usv_model_pf_ca behind guidance.PathFollowingFrontEnd.set_fleet: scenes of S vessels that are each other's
+# moving obstacles (csrc/fleet_world.hpp)
+def fleet_vessels(B, S):
+    """[B, S-1]: the vessel behind fleet slot e of instance i = s S + a is s S + (e if e < a else e + 1)."""
+    i, e = np.arange(B)[:, None], np.arange(S - 1)[None, :]
+    a = i % S
+    return i - a + np.where(e < a, e, e + 1)
+
+
+def fleet_world(x0, S, radius=0.5):
+    """The numpy restatement of the device's gather: x0 [B,14] -> (entries [B,S-1,3] = (X, Y, R), vel [B,S-1,2] = (vX, vY),
+    separation [B,S-1]) of every instance's scene-mates; X, Y = x0_j[10], x0_j[11], sog = sqrt(u u + v v), vX = sog x0_j[2], vY = sog x0_j[1]
+    (the model's own cos / sin of the course angle), separation = sqrt(dx dx + dy dy).  Every product and sum is rounded on its own, no
+    trigonometric call: the same bits as the device."""
+    x0 = np.asarray(x0, dtype=float)
+    B = x0.shape[0]
+    if S < 2 or B % S:
+        raise ValueError("fleet_world: %d instances are not a whole number of scenes of %d (S >= 2)" % (B, S))
+    xj = x0[fleet_vessels(B, S)]                                   # [B, S-1, 14]
+    u, v = xj[..., 3], xj[..., 4]
+    sog = np.sqrt(u * u + v * v)
+    entries = np.stack([xj[..., 10], xj[..., 11], np.full(sog.shape, float(radius))], axis=2)
+    vel = np.stack([sog * xj[..., 2], sog * xj[..., 1]], axis=2)
+    dx, dy = xj[..., 10] - x0[:, None, 10], xj[..., 11] - x0[:, None, 11]
+    return entries, vel, np.sqrt(dx * dx + dy * dy)
+
+
+# Encounter geometry, settled with tools/pf_encounter_oracle.py (profiles/pf_encounter_oracle.txt) under hard obstacle rows, whose keep-out
+# distance between two hulls of radius 0.5 is (0.5 + 0.5) + 0.2 = 1.2 m:
+PF_ENC_LANE = 2.0            # m between neighbouring lanes, +- PF_ENC_LANE_JITTER per vessel
+PF_ENC_LANE_JITTER = 0.2
+PF_ENC_STAGGER = 0.5         # m: a vessel starts up to this far ahead of or behind its line
+PF_ENC_CROSS_OFFSET = 3.0    # m: a crossing vessel starts this much farther from the crossing point than the one it crosses (4.3 s at 0.7 m/s)
+PF_ENC_HEAD_ON_LATERAL = 1.1 # m: lateral offset of two opposing lanes (port to port), +- PF_ENC_LANE_JITTER per vessel: less than the 1.2 m, both swerve
+PF_ENC_SPEED = 0.7
+PF_ENC_KINDS = ("parallel", "crossing", "head_on")
+
+
+def make_pf_encounters(scenes, S, seed=0, kind="parallel"):
+    """scenes * S missions, scene s (instances s S .. s S + S - 1) drawn from numpy.random.default_rng(seed + s): a scene does not depend on
+    the batch it is in.  Returns dict(waypoints [B,3,2], x0 [B,14], world [B,0,3] - no fixed obstacle: the scene's vessels are the obstacles).
+    Every vessel sails a two-leg route at PF_ENC_SPEED from the start (u = 0.7; x0[1], x0[2] = sin / cos of the heading), vessel a of a
+    scene, with lane l = a // 2 for the kinds that pair vessels up:
+      "parallel"   all northwards side by side: (x, -5) -> (x, -1) -> (x + 1.5, 2) with x = 4 + a (PF_ENC_LANE +- jitter)
+      "crossing"   even a northwards as above on x = 4 + l (lane); odd a westwards (9 + offset, y) -> (1, y) -> (-2, y + 1.5) with
+                   y = -2 + l (lane): it reaches the crossing point PF_ENC_CROSS_OFFSET (+- stagger) metres of sailing after the northbound one
+      "head_on"    even a northwards on x = 4 + 2 l (lane); odd a southwards (x', 3) -> (x', -1) -> (x' - 1.5, -4) on
+                   x' = 4 + 2 l (lane) - PF_ENC_HEAD_ON_LATERAL: the two pass port to port and turn away from each other."""
+    if kind not in PF_ENC_KINDS:
+        raise ValueError("make_pf_encounters: kind must be one of %s" % (PF_ENC_KINDS,))
+    B = scenes * S
+    wp, x0 = np.zeros((B, 3, 2)), np.zeros((B, 14))
+    for s in range(scenes):
+        rng = np.random.default_rng(seed + s)
+        for a in range(S):
+            b = s * S + a
+            jit = rng.uniform(-PF_ENC_LANE_JITTER, PF_ENC_LANE_JITTER)
+            stag = rng.uniform(-PF_ENC_STAGGER, PF_ENC_STAGGER)
+            lane = a // 2
+            if kind == "parallel" or a % 2 == 0:
+                x = 4.0 + (a * PF_ENC_LANE if kind == "parallel" else (2 * lane if kind == "head_on" else lane) * PF_ENC_LANE) + jit
+                wp[b] = [[x, -5.0], [x, -1.0], [x + 1.5, 2.0]]
+                start, psi = (x, -5.0 + stag), np.pi / 2
+            elif kind == "crossing":
+                y = -2.0 + lane * PF_ENC_LANE + jit
+                wp[b] = [[9.0 + PF_ENC_CROSS_OFFSET, y], [1.0, y], [-2.0, y + 1.5]]
+                start, psi = (7.0 + PF_ENC_CROSS_OFFSET + stag, y), np.pi
+            else:
+                x = 4.0 + 2 * lane * PF_ENC_LANE - PF_ENC_HEAD_ON_LATERAL + jit
+                wp[b] = [[x, 3.0], [x, -1.0], [x - 1.5, -4.0]]
+                start, psi = (x, 3.0 + stag), -np.pi / 2
+            x0[b, 0], x0[b, 1], x0[b, 2], x0[b, 3] = psi, np.sin(psi), np.cos(psi), PF_ENC_SPEED
+            x0[b, 10], x0[b, 11] = start
+    return dict(waypoints=wp, x0=x0, world=np.zeros((B, 0, 3)))

@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""The vessel encounters of scenario.make_pf_encounters in closed loop ON THE CPU: the numpy front end (tests/pf_frontend_ref.PfRef,
+device-resident mode), in front of it the numpy gather scenario.fleet_world - every vessel's scene-mates as moving world entries, from the
+states the plant left -, scenario.predict_world for the per-stage obstacle set, then the CPU oracle's SQP-RTI step; the plant is the
+controller's prediction x_1.  The loop examples/pf_encounter_sweep.py runs on the device, restated without one.  No GPU, no solver library.
+
+Prints finish ticks, separations, clearances and failure counts per kind.  It is the yardstick the device's encounters are held against
+(profiles/pf_encounter_oracle.txt; tests/test_gpu_pf_fleet.py copies its figures) and the place where the generator's constants were settled
+(--lane / --cross-offset / --lateral override scenario.PF_ENC_LANE / PF_ENC_CROSS_OFFSET / PF_ENC_HEAD_ON_LATERAL).
+
+    python tools/pf_encounter_oracle.py --scenes 32 --scene-size 2 --ticks 400 --write
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mpc_collisionavoidance_amd import scenario  # noqa: E402
+from oracle import binding as oracle  # noqa: E402
+from tests import pf_frontend_ref as R  # noqa: E402
+
+MODEL_PF_CA = 2
+
+
+def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=None, K=None, quiet=False, out=None):
+    cfg = scenario.PF_MISSION_OCP
+    N, K, dt = N or cfg["N"], K or cfg["K"], cfg["dt"]
+    m = scenario.make_pf_encounters(scenes, S, seed, kind)
+    B = scenes * S
+    fixed = m["world"].copy()
+    fvel = np.zeros((B, fixed.shape[1], 2))
+    spec = oracle.spec(MODEL_PF_CA, N, N * dt, K, sim_steps=cfg["sim_steps"])
+    fe = R.PfRef(B, N, K, cfg["margin"])
+    fe.reset(m["waypoints"])
+    fe.max_radius = cfg["max_radius"]
+    fe.x0[:] = m["x0"]
+    x = np.ascontiguousarray(np.tile(m["x0"][:, None, :], (1, N + 1, 1)))
+    u = np.zeros((B, N, 2))
+    p, lh = np.zeros((B, N + 1, 2 * K)), np.zeros((B, N, K))
+    fails = np.zeros(ticks, dtype=int)
+    min_sep, sep_tick = np.full(B, 1e300), np.full(B, -1)
+    status = np.zeros(B, dtype=np.int32)
+    for t in range(ticks):
+        ent, vel, sep = scenario.fleet_world(fe.x0, S, radius)
+        for e in range(S - 1):
+            win = sep[:, e] < min_sep
+            min_sep[win], sep_tick[win] = sep[win, e], t
+        world, wvel = np.concatenate([fixed, ent], axis=1), np.concatenate([fvel, vel], axis=1)
+        fe.world = world
+        fe.prepare()
+        live = fe.phase != R.OVER
+        if predict:
+            pp, ll = scenario.predict_world(world, wvel, fe.chosen, N, dt, margin=cfg["margin"])
+        else:
+            pp, ll = np.tile(fe.p0[:, None], (1, N + 1, 1)), np.tile(fe.lh0[:, None], (1, N, 1))
+        p[live], lh[live] = pp[live], ll[live]
+        status, its = oracle.rti_batch(spec, x, u, fe.x0, fe.yref, fe.yref_e, p, lh, threads=threads)
+        fails[t] = int((status != 0).sum())
+        fe.publish(x[:, 1])
+        fe.x0[:] = x[:, 1]               # the hand-over: the plant is the controller's prediction, no trajectory shift
+        fixed[:, :, :2] = fixed[:, :, :2] + dt * fvel
+    res = dict(finish_tick=fe.finish_tick.copy(), min_clearance=fe.min_clearance.copy(), min_separation=min_sep, separation_tick=sep_tick,
+               failures_per_tick=fails, final_status=status, waypoint_index=fe.k.copy())
+    if not quiet:
+        ft, mc = res["finish_tick"], res["min_clearance"]
+        fin = ft >= 0
+        lines = ["kind %s: %d scenes of %d, seeds %d .. %d, %d ticks, %s" % (kind, scenes, S, seed, seed + scenes - 1, ticks,
+                                                                          "predicted per stage" if predict else "held still inside the horizon"),
+                 "  constants: lane %.3g +- %.3g, stagger %.3g, crossing offset %.3g, head-on lateral offset %.3g" % (
+                     scenario.PF_ENC_LANE, scenario.PF_ENC_LANE_JITTER, scenario.PF_ENC_STAGGER, scenario.PF_ENC_CROSS_OFFSET,
+                     scenario.PF_ENC_HEAD_ON_LATERAL),
+                 "  finished %d of %d%s" % (fin.sum(), B, ", at ticks %d .. %d" % (ft[fin].min(), ft[fin].max()) if fin.any() else ""),
+                 "  smallest min_separation %.4f m (median %.4f), met at tick %d" % (min_sep.min(), np.median(min_sep), sep_tick[min_sep.argmin()]),
+                 "  smallest min_clearance %.4f m (median %.4f)" % (mc.min(), np.median(mc)),
+                 "  failed solves %d over all ticks (%d ticks with at least one)" % (fails.sum(), (fails > 0).sum()),
+                 "  not finished: instances %s, waypoint index %s" % (np.nonzero(~fin)[0].tolist(), fe.k[~fin].tolist()),
+                 "  finish ticks %s" % ft.tolist(),
+                 "  min_separation %s" % np.round(min_sep, 4).tolist()]
+        print("\n".join(lines))
+        if out is not None:
+            out.extend(lines)
+    return res
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--scenes", type=int, default=32)
+    ap.add_argument("--scene-size", type=int, default=2)
+    ap.add_argument("--ticks", type=int, default=400)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--kinds", default=",".join(scenario.PF_ENC_KINDS))
+    ap.add_argument("--no-predict", action="store_true", help="the scene held still inside the horizon (option \"pf_predict\" 0)")
+    ap.add_argument("--lane", type=float, default=None)
+    ap.add_argument("--cross-offset", type=float, default=None)
+    ap.add_argument("--lateral", type=float, default=None)
+    ap.add_argument("--write", action="store_true", help="also write profiles/pf_encounter_oracle.txt")
+    a = ap.parse_args()
+    if a.lane is not None:
+        scenario.PF_ENC_LANE = a.lane
+    if a.cross_offset is not None:
+        scenario.PF_ENC_CROSS_OFFSET = a.cross_offset
+    if a.lateral is not None:
+        scenario.PF_ENC_HEAD_ON_LATERAL = a.lateral
+    text = ["# tools/pf_encounter_oracle.py --scenes %d --scene-size %d --ticks %d --seed %d%s" % (
+        a.scenes, a.scene_size, a.ticks, a.seed, " --no-predict" if a.no_predict else ""),
+        "# the CPU oracle behind the numpy front end and the numpy gather: the yardstick of tests/test_gpu_pf_fleet.py"]
+    for kind in a.kinds.split(","):
+        run(a.scenes, a.scene_size, a.ticks, kind, seed=a.seed, predict=not a.no_predict, threads=a.threads, out=text)
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "pf_encounter_oracle.txt"), "w") as f:
+            f.write("\n".join(text) + "\n")

@@ -12,12 +12,20 @@ With --moving the world of `resident` and `hostfed` moves (scenario.make_pf_miss
 advance steps the world; the extra mode `held` is `resident` with option "pf_predict" 0 (the world moves between ticks, stage 0 only) and `static` is `resident` over
 a world at rest whatever --moving says, so that one invocation alternates the three.
 
+With --fleet S the batch is cut into scenes of S vessels that are each other's moving obstacles (PathFollowingFrontEnd.set_fleet; every
+vessel's route, start and four fixed obstacles are moved 4 a metres east for vessel a of a scene, so that scene-mates sail side by side),
+the world of every mode moves, and two more modes exist: `fleet` is `resident` with the fleet on - prepare() gathers the scene-mates on the
+device ahead of its own kernel -, and `fleethost` is the loop a handle without the fleet needs for the same scenes: synchronise, read x0 and
+the world back, rebuild the S - 1 trailing entries and velocities in numpy (scenario.fleet_world), upload, then the same four calls.  The
+JSON lines also go to --out (default profiles/pf_fleet_probe.txt).
+
 Median over --ticks timed ticks after --warmup warm-up ticks (a host clock around the tick and a final sync), `--runs` alternating runs, one
 JSON line each, with the lineariser's and the QP launch's kernel times of the same ticks (HIP events) and the bytes a full yref rewrite
 streams.
 
     python tools/pf_frontend_probe.py --batch 65536
     python tools/pf_frontend_probe.py --batch 65536 --moving --modes static,resident,held
+    python tools/pf_frontend_probe.py --batch 65536 --fleet 4 --modes resident,fleet,fleethost
     rocprofv3 --kernel-trace --stats -- python tools/pf_frontend_probe.py --batch 65536 --modes resident --runs 1 --ticks 4 --warmup 1
 """
 import argparse
@@ -38,12 +46,23 @@ MODES = ("plain", "resident", "hostfed")   # and "held", "static" (see above)
 _missions = {}
 
 
-def run(mode, B, ticks, warmup, seed=0, moving=False):
+def fleet_missions(m, S):
+    """make_pf_missions' batch with vessel a of every scene moved 4 a metres east: route, start and fixed obstacles"""
+    east = 4.0 * (np.arange(m["x0"].shape[0]) % S)
+    out = {k: v.copy() for k, v in m.items()}
+    out["waypoints"][:, :, 0] += east[:, None]
+    out["world"][:, :, 0] += east[:, None]
+    out["x0"][:, 10] += east
+    return out
+
+
+def run(mode, B, ticks, warmup, seed=0, moving=False, fleet=0, radius=0.5):
     cfg = scenario.PF_MISSION_OCP
     N, K, dt = cfg["N"], cfg["K"], cfg["dt"]
-    if (B, seed) not in _missions:
-        _missions[(B, seed)] = scenario.make_pf_missions(B, seed, moving=True)   # (every other field is the same with either value)
-    m = _missions[(B, seed)]
+    if (B, seed, fleet) not in _missions:
+        m = scenario.make_pf_missions(B, seed, moving=True)   # (every other field is the same with either value)
+        _missions[(B, seed, fleet)] = fleet_missions(m, fleet) if fleet else m
+    m = _missions[(B, seed, fleet)]
     ocp = usv_models.make_ocp("usv_model_pf_ca", N * dt, N, K)
     ocp.solver_options.sim_method_num_steps = cfg["sim_steps"]
     s = BatchOcpSolver(ocp, B)
@@ -54,15 +73,28 @@ def run(mode, B, ticks, warmup, seed=0, moving=False):
     fe.reset(m["waypoints"])
     if mode == "held":
         s.set_option("pf_predict", 0)
-    moves = mode == "held" or (moving and mode in ("resident", "hostfed"))
+    moves = mode == "held" or mode in ("fleet", "fleethost") or (moving and mode in ("resident", "hostfed"))
     fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"], vel=m["world_vel"] if moves else None)
+    n_fixed = m["world"].shape[1]
+    if mode == "fleet":
+        fe.set_fleet(fleet, radius)
+    elif mode == "fleethost":             # the same list, the trailing S - 1 entries the host's to fill
+        far = np.tile([1000.0, 1000.0, 0.0], (B, fleet - 1, 1))
+        fe.set_world(np.concatenate([m["world"], far], axis=1), max_radius=cfg["max_radius"],
+                     vel=np.concatenate([m["world_vel"], np.zeros((B, fleet - 1, 2))], axis=1))
     if mode == "plain":
         fe.prepare()                      # the first tick's inputs, once
     s.sync()
     times = []
     for t in range(warmup + ticks):
         t0 = time.perf_counter()
-        if mode in ("resident", "held", "static"):
+        if mode in ("resident", "held", "static", "fleet"):
+            fe.prepare()
+        elif mode == "fleethost":
+            x0 = s.get("x0", 0)
+            w, v = fe.world()
+            w[:, n_fixed:], v[:, n_fixed:], _ = scenario.fleet_world(x0, fleet, radius)
+            fe.set_world(w, max_radius=cfg["max_radius"], vel=v)
             fe.prepare()
         elif mode == "hostfed":
             x0 = s.get("x0", 0)
@@ -78,7 +110,8 @@ def run(mode, B, ticks, warmup, seed=0, moving=False):
     used, discarded = s.pipeline_stats()
     st = fe.state()
     out = dict(mode=mode, batch=B, N=N, K=K, ticks=ticks, warmup=warmup, tick_ms_median=statistics.median(timed), tick_ms_min=min(timed),
-               tick_ms_max=max(timed), linearize_ms_median=float(np.median(lin)), qp_ms_median=float(np.median(qp)),
+               tick_ms_max=max(timed), tick_net_of_qp_ms_median=statistics.median(timed) - float(np.median(qp)), fleet=fleet,
+               linearize_ms_median=float(np.median(lin)), qp_ms_median=float(np.median(qp)),
                pipelined_linearisations_used=int(used), yref_writes=st["yref_writes"], yref_full_rewrite_bytes=B * (N * 16 + 14) * 8,
                failed_last_tick=int(s.fail_counts(1)[0]), moving=bool(moves),
                p_lh_full_rewrite_bytes=B * ((N + 1) * 2 * K + N * K) * 8 if moves and mode != "held" else 0)
@@ -94,9 +127,19 @@ if __name__ == "__main__":
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--modes", default=",".join(MODES))
     ap.add_argument("--moving", action="store_true", help="the world of the front-end modes moves (every stage of p / lh per tick)")
+    ap.add_argument("--fleet", type=int, default=0, help="scenes of this many vessels (modes fleet, fleethost); the world of every mode moves")
+    ap.add_argument("--out", default=None, help="with --fleet: where the JSON lines are also written (default profiles/pf_fleet_probe.txt)")
     a = ap.parse_args()
+    lines = []
     for r in range(a.runs):
         for mode in a.modes.split(","):
-            line = run(mode, a.batch, a.ticks, a.warmup, moving=a.moving)
+            line = run(mode, a.batch, a.ticks, a.warmup, moving=a.moving or a.fleet > 0, fleet=a.fleet)
             line["run"] = r
-            print(json.dumps(line), flush=True)
+            lines.append(json.dumps(line))
+            print(lines[-1], flush=True)
+    if a.fleet:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(a.out or os.path.join(root, "profiles", "pf_fleet_probe.txt"), "a") as f:
+            f.write("# tools/pf_frontend_probe.py --batch %d --fleet %d --modes %s --ticks %d --warmup %d --runs %d\n" % (
+                a.batch, a.fleet, a.modes, a.ticks, a.warmup, a.runs))
+            f.write("\n".join(lines) + "\n")
