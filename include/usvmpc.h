@@ -385,6 +385,39 @@ int usvmpc_guidance_world_vel(usvmpc_handle *h, const double *vel, int predict);
 int usvmpc_guidance_world_step(usvmpc_handle *h, double T);
 int usvmpc_guidance_world_read(usvmpc_handle *h, double *world, double *vel);
 int usvmpc_guidance_mission_state(usvmpc_handle *h, int *wp_index, float *past_psied, int *finish_tick, double *min_clearance);
+/* VESSEL ENCOUNTERS for the guidance front end: a scene's vessels as each other's moving obstacles (the arithmetic: csrc/ca_fleet_world.hpp;
+ * scenes, slots and layout as usvmpc_pf_fleet below).  The batch is cut into scenes of scene_size = S consecutive instances (scene s:
+ * instances s S .. s S + S - 1; shards of a larger batch must be cut at multiples of S).  Every instance keeps its own waypoints, mission
+ * state and OCP, and sees the other S - 1 vessels of its scene as moving world entries that every DEVICE-RESIDENT prepare refreshes on the
+ * device (kernel usv_guidance_fleet_gather, ahead of usv_guidance_tick on the handle's stream); a tick stays prepare -> solve -> publish ->
+ * advance, no synchronisation, and a linearisation made a tick ahead still stands.
+ *   fleet, scene_size >= 2: the world list becomes the caller's n_fixed entries followed by S - 1 fleet entries the front end owns, parked at
+ *             (1000, 1000, 0) with velocity 0 until the first gather.  The world counts as moving from then on: velocities and the `predict`
+ *             choice already given (usvmpc_guidance_world_vel) are kept, a world that was at rest gets zero velocities and predict 1.  With
+ *             a = i mod S, fleet slot e = 0 .. S-2 of instance i is vessel j = i - a + (e < a ? e : e + 1), and list index n_fixed + e
+ *             receives from x0 as usvmpc_advance / usvmpc_advance_sim left it
+ *                 X = x0_j[5], Y = x0_j[6], R = radius, vX = u cos psi - v sin psi, vY = u sin psi + v cos psi
+ *             with u, v, psi = x0_j[0], x0_j[1], x0_j[7]: sine and cosine evaluated once each, in double, every product and sum rounded on
+ *             its own - a host that restates it agrees to 8 * 2^-52 * (|u| + |v|), the two libraries' sin / cos apart.  The entries then
+ *             go the way of any moving entry: the sensor's max_radius, the nearest-K choice, the per-stage prediction (predict 0: held still
+ *             inside the horizon), the running minimum clearance, the world step of usvmpc_advance / usvmpc_advance_sim.  The gather also
+ *             keeps, per instance and over the other vessels of its scene, the smallest d = sqrt(dx^2 + dy^2) between the two positions
+ *             and the prepare it was met at - for every instance, whatever its mission phase: a vessel whose mission is over is still in
+ *             the water and is still gathered by the others.
+ *   fleet, scene_size 0 or 1: the fleet is off and the list is cut back to the fixed entries, which keep their velocities
+ *             (usvmpc_guidance_world_vel(NULL) puts the world at rest as ever).
+ *   While the fleet is on: usvmpc_guidance_world takes the fixed entries only (n_world <= 64 - (S - 1)) and keeps the fleet slots (the fixed
+ *             entries' velocities too when n_world is unchanged, else they are zero); usvmpc_guidance_world_vel takes [B][n_fixed][2];
+ *             usvmpc_guidance_world_read returns all n_fixed + S - 1 entries as the device holds them; usvmpc_guidance_world_step moves every
+ *             entry - the fleet slots are overwritten by the next gather.
+ *   USVMPC_E_ARG with a message, nothing changed: another model; no usvmpc_guidance_reset or no world list yet (an empty list will do);
+ *             B % scene_size != 0; n_fixed + S - 1 > 64; a negative or non-finite radius; option "obstacle_tracks" on (and switching it on
+ *             while the fleet is on); a HOST-FED usvmpc_guidance_sense or usvmpc_guidance_prepare while the fleet is on (the scene exists on
+ *             the device only); usvmpc_guidance_world_vel(NULL) while the fleet is on.
+ *   fleet_state: min_separation [B] (1e300 after usvmpc_guidance_reset; a NaN never wins), separation_tick [B] (device-resident prepares since
+ *             reset, from 0; -1: none yet).  Either may be NULL. */
+int usvmpc_guidance_fleet(usvmpc_handle *h, int scene_size, double radius);
+int usvmpc_guidance_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick);
 /* ---- Path-following front end (model usv_model_pf_ca only; any other model: USVMPC_E_ARG with a message): the arithmetic either side
  * of the solver call in the reference's path-following ROS node, batched on the device (class NMPC in catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp;
  * nmpc_pf_ca.cpp is the same file; the arithmetic: csrc/pf_guidance.hpp).  Per-instance state (waypoint index k, past thrust, the reference

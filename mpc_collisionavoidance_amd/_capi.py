@@ -72,7 +72,7 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read",
            "usvmpc_pf_fleet", "usvmpc_pf_fleet_state",
            "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
-           "usvmpc_guidance_mission_state",
+           "usvmpc_guidance_mission_state", "usvmpc_guidance_fleet", "usvmpc_guidance_fleet_state",
            "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr",
            "usvmpc_eval_cost", "usvmpc_cost_track", "usvmpc_cost_tracked"]
 
@@ -156,6 +156,8 @@ def load(path):
     L.usvmpc_pf_world_step.argtypes = [C.c_void_p, C.c_double]
     L.usvmpc_pf_world_read.argtypes = [C.c_void_p, _dp, _dp]
     L.usvmpc_pf_fleet.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    L.usvmpc_guidance_fleet.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    L.usvmpc_guidance_fleet_state.argtypes = [C.c_void_p, _dp, _ip]
     L.usvmpc_pf_fleet_state.argtypes = [C.c_void_p, _dp, _ip]
     L.usvmpc_debug_model_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_obstacle_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]

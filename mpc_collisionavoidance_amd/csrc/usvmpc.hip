@@ -24,6 +24,7 @@
 
 #include "gfx950/lanes.hpp"
 
+#include "ca_fleet_world.hpp"
 #include "closed_loop_log.hpp"
 #include "cost_eval.hpp"
 #include "fleet_world.hpp"
@@ -860,6 +861,41 @@ static __global__ void usv_guidance_mission_reset(double *min_clear, int *finish
     finish_tick[b] = -1;
 }
 
+static __global__ void usv_guidance_fleet_reset(double *min_sep, int *sep_tick, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    min_sep[b] = 1e300;
+    sep_tick[b] = -1;
+}
+
+// usv_guidance_fleet_gather: vessel encounters (ca_fleet_world.hpp) - the other S - 1 vessels of an instance's scene, as the plant left them
+// in x0, become the fleet entries behind the n_fixed fixed ones of its world list.  A kernel of its own ahead of usv_guidance_tick, which
+// rewrites x0 (ca_x0) while a scene-mate in another workgroup would still be reading it; this one reads x0 only and writes the world lists
+// and the separation bookkeeping only - nothing a lineariser reads.  One thread per (instance, fleet slot), the slot fastest: a thread
+// loads five doubles of one scene-mate (the scene's states are S neighbouring 64-byte rows), takes one sine and one cosine, and stores one
+// entry (24 bytes) and one velocity (16 bytes); the threads of an instance store its S - 1 entries as one run, a wave's runs lying
+// 24 nworld bytes apart.  The separation bookkeeping needs all S - 1 distances of an instance in one place: its slot-0 thread takes the
+// S - 1 positions again (lines its own wave has just loaded) - no atomics, no LDS.
+__global__ void __launch_bounds__(256) usv_guidance_fleet_gather(const double *x0, double *world, double *wvel, double *min_sep, int *sep_tick,
+                                                                 long B, int S, int n_fixed, double radius, int tick)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = S - 1;
+    if (t >= B * f) return;
+    const long i = t / f;
+    const int e = (int)(t - i * f);
+    const long at = i * (n_fixed + f) + n_fixed + e; // the entry's place in the [B][nworld] lists
+    ca_fleet_entry(x0 + fleet_vessel(i, e, S) * CA_FLEET_NX, radius, world + 3 * at, wvel + 2 * at);
+    if (e != 0) return;
+    double m = min_sep[i];
+    int mt = sep_tick[i];
+    for (int q = 0; q < f; q++)
+        fleet_closest(ca_fleet_separation(x0 + i * CA_FLEET_NX, x0 + fleet_vessel(i, q, S) * CA_FLEET_NX), tick, m, mt);
+    min_sep[i] = m;
+    sep_tick[i] = mt;
+}
+
 // usv_guidance_tick: the node's input side for a vessel whose state is the solver's own x0 (as usv_advance / usv_advance_sim left it) against
 // a world list that lives on the device.  One workgroup per CA_GROUP consecutive instances, laid out as usv_pf_prepare:
 // 1. Decide: the first wave, one lane per instance - (u, v) = x0[0..1], (nedx, nedy, psi) = x0[5..7]; the simulator's visibility test and
@@ -1193,6 +1229,13 @@ struct usvmpc_handle {
     bool gd_moving = false;     // velocities are set for the current list
     bool gd_predict = false;    // ... and the horizon sees them ("static_obstacles" off)
     int gd_tick = 0;            // device-resident prepares since the last reset
+    // Vessel encounters (usvmpc_guidance_fleet, ca_fleet_world.hpp): scenes of gd_fleet_S consecutive instances; the world list is then the
+    // caller's gd_nfixed entries followed by gd_fleet_S - 1 fleet slots (gd_tickp.nworld counts both), which a resident prepare gathers from x0
+    int gd_fleet_S = 0;         // 0: no fleet
+    int gd_nfixed = 0;          // (meaningful while a fleet is on)
+    double gd_fleet_radius = 0.0;
+    double *gd_min_sep = nullptr; // [B] smallest distance to a vessel of the instance's scene (allocated by the first usvmpc_guidance_fleet)
+    int *gd_sep_tick = nullptr;   // [B] the prepare it was met at (-1: none yet)
     // Closed-loop log (usvmpc_log_*): which hand-over records, the counters and the layout are log_plan.hpp's - the state machine LogPlan (no
     // field of it is assigned in this file: usvmpc_log_start / _stop and log_handover call its methods), host-only and checked on the CPU by
     // tests/test_log_plan.py.  Here: the buffers its layout sizes (nullptr: channel not recorded) and the kernel arguments that do not change.
@@ -3024,6 +3067,44 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
 }
 
 
+// Vessel encounters, either front end: a world list ([B][n][3] at *world, velocities [B][n][2] at *wvel - read only when `moving` -, capacities
+// in doubles) laid out anew through the host: n0 entries of which the last f0 are fleet slots -> n1_fixed fixed entries and f1 fleet slots
+// (fleet_world.hpp: fleet_relayout, which says what is kept).  fixed: the new fixed entries [B][n1_fixed][3]; null keeps the present ones.
+// Afterwards the list has velocities, whether the world moved before or not.  A set-up call, never part of a tick.
+static int world_relayout(usvmpc_handle *h, const double **world, size_t *world_cap, double **wvel, size_t *wvel_cap, bool moving, int n0, int f0,
+                          const double *fixed, int n1_fixed, int f1)
+{
+    const size_t B = h->B;
+    const int n0_fixed = n0 - f0, n1 = n1_fixed + f1;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step on the old list may be in flight)
+    std::vector<double> w0(B * (size_t)n0 * 3), v0(B * (size_t)n0 * 2), w1(B * (size_t)n1 * 3), v1(B * (size_t)n1 * 2);
+    if (!w0.empty()) HIP_TRY(h, hipMemcpyAsync(w0.data(), *world, w0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (!v0.empty() && moving) HIP_TRY(h, hipMemcpyAsync(v0.data(), *wvel, v0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; b++)
+        fleet_relayout(w0.data() + b * (size_t)n0 * 3, moving ? v0.data() + b * (size_t)n0 * 2 : nullptr, n0_fixed, f0,
+                       fixed ? fixed + b * (size_t)n1_fixed * 3 : nullptr, n1_fixed, f1, w1.data() + b * (size_t)n1 * 3, v1.data() + b * (size_t)n1 * 2);
+    if (w1.size() > *world_cap) {
+        dev_free(h, const_cast<double *>(*world), *world_cap * sizeof(double));
+        *world = nullptr; *world_cap = 0;
+        double *d = nullptr;
+        if (dev_alloc(h, &d, w1.size(), false)) return USVMPC_E_HIP;
+        *world = d;
+        *world_cap = w1.size();
+    }
+    if (v1.size() > *wvel_cap || !*wvel) {
+        dev_free(h, *wvel, *wvel_cap * sizeof(double));
+        *wvel = nullptr; *wvel_cap = 0;
+        if (dev_alloc(h, wvel, v1.size(), false)) return USVMPC_E_HIP;
+        *wvel_cap = v1.size();
+    }
+    if (!w1.empty()) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(*world), w1.data(), w1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!v1.empty()) HIP_TRY(h, hipMemcpyAsync(*wvel, v1.data(), v1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // ---- guidance front end (M1 only): see ca_guidance.hpp (the arithmetic), guidance.hpp (the host-fed kernels), usv_guidance_tick above
 // "static_obstacles" as the front end needs it: off only while its world moves AND is predicted per stage (the tick then writes all stages)
 static int gd_apply_static(usvmpc_handle *h)
@@ -3084,6 +3165,10 @@ int usvmpc_guidance_reset(usvmpc_handle *h, const double *waypoints, int npts, c
     hipLaunchKernelGGL(usv_guidance_mission_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->gd_tickp.min_clear,
                        h->gd_tickp.finish_tick, (int)B);
     HIP_TRY(h, hipGetLastError());
+    if (h->gd_min_sep) {
+        hipLaunchKernelGGL(usv_guidance_fleet_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->gd_min_sep, h->gd_sep_tick, (int)B);
+        HIP_TRY(h, hipGetLastError());
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->gd_tick = 0;
     return gd_apply_static(h);
@@ -3100,6 +3185,10 @@ int usvmpc_guidance_prepare(usvmpc_handle *h, const double *vel_uv, const double
     if (lmax < 0 || lmax > GUIDANCE_LMAX) return USVMPC_E_ARG;
     if (!h->gd_ready || h->gd.npts < 2) { h->err = "usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
     if (!vel_uv) return guidance_tick(h);
+    if (h->gd_fleet_S) {
+        h->err = "guidance_prepare: a fleet is on and its scene exists on the device only; prepare device-resident (vel_uv and pose NULL)";
+        return USVMPC_E_ARG;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     {
         const int rcf = mirror_flush(h);
@@ -3138,6 +3227,13 @@ static int guidance_tick(usvmpc_handle *h)
     W.wvel = (h->gd_moving && h->gd_predict) ? h->gd_wvel : nullptr; // (held still inside the horizon: the tick of a world at rest)
     W.tick = h->gd_tick;
     const size_t B = h->B;
+    if (h->gd_fleet_S) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_guidance_tick rewrites x0
+        const long n = (long)B * fleet_slots(h->gd_fleet_S);
+        hipLaunchKernelGGL(usv_guidance_fleet_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs.x0,
+                           const_cast<double *>(W.world), h->gd_wvel, h->gd_min_sep, h->gd_sep_tick, (long)B, h->gd_fleet_S, h->gd_nfixed,
+                           h->gd_fleet_radius, h->gd_tick);
+        HIP_TRY(h, hipGetLastError());
+    }
     hipLaunchKernelGGL(usv_guidance_tick, dim3((unsigned)((B + CA_GROUP - 1) / CA_GROUP)), dim3(256), 0, h->stream, h->ptrs, h->gd, W);
     HIP_TRY(h, hipGetLastError());
     h->gd_tick++;
@@ -3149,6 +3245,10 @@ int usvmpc_guidance_sense(usvmpc_handle *h, const double *pose, const double *wo
 {
     if (!h || !pose || n_world < 0 || (n_world > 0 && !world)) return USVMPC_E_ARG;
     if (!h->gd_ready) { h->err = "usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
+    if (h->gd_fleet_S) {
+        h->err = "guidance_sense: a fleet is on and its scene exists on the device only; prepare device-resident (usvmpc_guidance_prepare, vel_uv and pose NULL)";
+        return USVMPC_E_ARG;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     GuidancePtrs &G = h->gd;
     const size_t B = h->B;
@@ -3222,6 +3322,20 @@ int usvmpc_guidance_world(usvmpc_handle *h, const double *world, int n_world, do
     for (size_t i = 0; i < need; i++)
         if (!(world[i] == world[i])) { h->err = "guidance_world: entry " + std::to_string(i) + " is NaN"; return USVMPC_E_ARG; }
     CaTickPtrs &W = h->gd_tickp;
+    if (h->gd_fleet_S) { // (the fixed entries only; the fleet slots stay)
+        if (!fleet_fits(n_world, h->gd_fleet_S)) {
+            h->err = "guidance_world: a fleet is on and owns " + std::to_string(fleet_slots(h->gd_fleet_S)) +
+                     " entries of the list: n_world must lie in 0.." + std::to_string(GUIDANCE_LMAX - fleet_slots(h->gd_fleet_S));
+            return USVMPC_E_ARG;
+        }
+        rc = world_relayout(h, &W.world, &h->gd_rworld_cap, &h->gd_wvel, &h->gd_wvel_cap, h->gd_moving, W.nworld, fleet_slots(h->gd_fleet_S), world,
+                            n_world, fleet_slots(h->gd_fleet_S));
+        if (rc) return rc;
+        W.nworld = n_world + fleet_slots(h->gd_fleet_S);
+        h->gd_nfixed = n_world;
+        W.max_radius = max_radius;
+        return 0;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a tick that reads the old list may be in flight)
     if (need > h->gd_rworld_cap) {
@@ -3254,16 +3368,29 @@ int usvmpc_guidance_world_vel(usvmpc_handle *h, const double *vel, int predict)
     int rc = gd_check(h, "guidance_world_vel");
     if (rc) return rc;
     if (!vel) { // back to a world at rest
+        if (h->gd_fleet_S) { h->err = "guidance_world_vel: a fleet is on and its world moves; switch it off first (usvmpc_guidance_fleet with scene_size 0)"; return USVMPC_E_ARG; }
         h->gd_moving = false;
         return gd_apply_static(h);
     }
     if (!h->gd_world_set) { h->err = "guidance_world_vel: no world list yet (usvmpc_guidance_world first)"; return USVMPC_E_ARG; }
     if (h->opt.tracks_on) { h->err = "guidance_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
-    const size_t need = (size_t)h->B * (size_t)h->gd_tickp.nworld * 2;
+    const int nvel = h->gd_fleet_S ? h->gd_nfixed : h->gd_tickp.nworld; // (a fleet's slots have the velocities the gather gave them)
+    const size_t need = (size_t)h->B * (size_t)nvel * 2;
     for (size_t i = 0; i < need; i++)
         if (vel[i] - vel[i] != 0.0) { h->err = "guidance_world_vel: entry " + std::to_string(i) + " is not finite"; return USVMPC_E_ARG; }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a tick or a world step that reads the old velocities may be in flight)
+    if (h->gd_fleet_S) { // [B][n_fixed][2] into the head of every instance's [nworld][2]
+        const size_t row = (size_t)h->gd_tickp.nworld * 2, head = (size_t)nvel * 2;
+        std::vector<double> v(h->B * row);
+        HIP_TRY(h, hipMemcpyAsync(v.data(), h->gd_wvel, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < (size_t)h->B; b++) std::copy(vel + b * head, vel + (b + 1) * head, v.begin() + (long)(b * row));
+        HIP_TRY(h, hipMemcpyAsync(h->gd_wvel, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->gd_predict = predict != 0;
+        return gd_apply_static(h);
+    }
     if (need > h->gd_wvel_cap || !h->gd_wvel) { // (an empty list moves too: a non-null pointer is what tells the tick so)
         dev_free(h, h->gd_wvel, h->gd_wvel_cap * sizeof(double));
         h->gd_wvel = nullptr; h->gd_wvel_cap = 0;
@@ -3319,6 +3446,72 @@ int usvmpc_guidance_mission_state(usvmpc_handle *h, int *wp_index, float *past_p
     if (past_psied) HIP_TRY(h, hipMemcpyAsync(past_psied, h->gd.past_psied, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (finish_tick) HIP_TRY(h, hipMemcpyAsync(finish_tick, h->gd_tickp.finish_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (min_clearance) HIP_TRY(h, hipMemcpyAsync(min_clearance, h->gd_tickp.min_clear, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int usvmpc_guidance_fleet(usvmpc_handle *h, int scene_size, double radius)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_fleet");
+    if (rc) return rc;
+    if (!h->gd_world_set) { h->err = "guidance_fleet: no world list yet (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
+    if (scene_size < 0) { h->err = "guidance_fleet: scene_size must not be negative"; return USVMPC_E_ARG; }
+    CaTickPtrs &W = h->gd_tickp;
+    if (!fleet_on(scene_size)) { // off: the list is cut back to the fixed entries, which keep their velocities
+        if (!h->gd_fleet_S) return 0;
+        rc = world_relayout(h, &W.world, &h->gd_rworld_cap, &h->gd_wvel, &h->gd_wvel_cap, h->gd_moving, W.nworld, fleet_slots(h->gd_fleet_S), nullptr,
+                            h->gd_nfixed, 0);
+        if (rc) return rc;
+        W.nworld = h->gd_nfixed;
+        h->gd_fleet_S = 0;
+        return 0;
+    }
+    const int n_fixed = h->gd_fleet_S ? h->gd_nfixed : W.nworld;
+    if (h->opt.tracks_on) { h->err = "guidance_fleet: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
+    if (!fleet_scene_ok(h->B, scene_size)) {
+        h->err = "guidance_fleet: the batch of " + std::to_string(h->B) + " is not a whole number of scenes of " + std::to_string(scene_size);
+        return USVMPC_E_ARG;
+    }
+    if (!fleet_fits(n_fixed, scene_size)) {
+        h->err = "guidance_fleet: " + std::to_string(n_fixed) + " fixed entries and " + std::to_string(scene_size - 1) + " fleet entries exceed the " +
+                 std::to_string(GUIDANCE_LMAX) + " of a world list";
+        return USVMPC_E_ARG;
+    }
+    if (!fleet_radius_ok(radius)) { h->err = "guidance_fleet: radius must be finite and not negative"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->gd_min_sep) {
+        if (dev_alloc(h, &h->gd_min_sep, h->B, true) || dev_alloc(h, &h->gd_sep_tick, h->B, true)) return USVMPC_E_HIP;
+        hipLaunchKernelGGL(usv_guidance_fleet_reset, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->gd_min_sep, h->gd_sep_tick,
+                           (int)h->B);
+        HIP_TRY(h, hipGetLastError());
+    }
+    rc = world_relayout(h, &W.world, &h->gd_rworld_cap, &h->gd_wvel, &h->gd_wvel_cap, h->gd_moving, W.nworld, fleet_slots(h->gd_fleet_S), nullptr,
+                        n_fixed, scene_size - 1);
+    if (rc) return rc;
+    W.nworld = n_fixed + scene_size - 1;
+    if (!h->gd_moving) h->gd_predict = true; // (a world at rest had no say in it; usvmpc_guidance_world_vel changes it)
+    h->gd_fleet_S = scene_size;
+    h->gd_nfixed = n_fixed;
+    h->gd_fleet_radius = radius;
+    h->gd_moving = true;
+    return gd_apply_static(h);
+}
+
+int usvmpc_guidance_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick)
+{
+    if (!h) return USVMPC_E_ARG;
+    int rc = gd_check(h, "guidance_fleet_state");
+    if (rc) return rc;
+    const size_t B = h->B;
+    if (!h->gd_min_sep) { // no fleet yet: as after a reset
+        if (min_separation) std::fill(min_separation, min_separation + B, 1e300);
+        if (separation_tick) std::fill(separation_tick, separation_tick + B, -1);
+        return 0;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (min_separation) HIP_TRY(h, hipMemcpyAsync(min_separation, h->gd_min_sep, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (separation_tick) HIP_TRY(h, hipMemcpyAsync(separation_tick, h->gd_sep_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -3400,36 +3593,11 @@ static int pf_alloc_tracks(usvmpc_handle *h)
 static int pf_relayout(usvmpc_handle *h, const double *fixed, int n1_fixed, int f1)
 {
     PfPtrs &F = h->pf;
-    const size_t B = h->B;
-    const int f0 = fleet_slots(h->pf_fleet_S), n0 = F.nworld, n0_fixed = n0 - f0, n1 = n1_fixed + f1;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step on the old list may be in flight)
-    std::vector<double> w0(B * (size_t)n0 * 3), v0(B * (size_t)n0 * 2), w1(B * (size_t)n1 * 3), v1(B * (size_t)n1 * 2);
-    if (!w0.empty()) HIP_TRY(h, hipMemcpyAsync(w0.data(), F.world, w0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (!v0.empty() && h->pf_moving) HIP_TRY(h, hipMemcpyAsync(v0.data(), h->pf_wvel, v0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (size_t b = 0; b < B; b++)
-        fleet_relayout(w0.data() + b * (size_t)n0 * 3, h->pf_moving ? v0.data() + b * (size_t)n0 * 2 : nullptr, n0_fixed, f0,
-                       fixed ? fixed + b * (size_t)n1_fixed * 3 : nullptr, n1_fixed, f1, w1.data() + b * (size_t)n1 * 3, v1.data() + b * (size_t)n1 * 2);
-    if (w1.size() > h->pf_world_cap) {
-        dev_free(h, const_cast<double *>(F.world), h->pf_world_cap * sizeof(double));
-        F.world = nullptr; h->pf_world_cap = 0;
-        double *d = nullptr;
-        if (dev_alloc(h, &d, w1.size(), false)) return USVMPC_E_HIP;
-        F.world = d;
-        h->pf_world_cap = w1.size();
-    }
-    if (v1.size() > h->pf_wvel_cap || !h->pf_wvel) {
-        dev_free(h, h->pf_wvel, h->pf_wvel_cap * sizeof(double));
-        h->pf_wvel = nullptr; h->pf_wvel_cap = 0;
-        if (dev_alloc(h, &h->pf_wvel, v1.size(), false)) return USVMPC_E_HIP;
-        h->pf_wvel_cap = v1.size();
-    }
+    const int rc = world_relayout(h, &F.world, &h->pf_world_cap, &h->pf_wvel, &h->pf_wvel_cap, h->pf_moving, F.nworld, fleet_slots(h->pf_fleet_S),
+                                  fixed, n1_fixed, f1);
+    if (rc) return rc;
     if (pf_alloc_tracks(h)) return USVMPC_E_HIP;
-    if (!w1.empty()) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.world), w1.data(), w1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!v1.empty()) HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, v1.data(), v1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    F.nworld = n1;
+    F.nworld = n1_fixed + f1;
     return 0;
 }
 

@@ -52,22 +52,46 @@ class GuidanceFrontEnd:
         """The obstacle field (X, Y, R) in NED for the device-resident mode: [B, L, 3] or [L, 3] for all, L <= 64; uploaded once.
         vel: [B, L, 2] or [L, 2] (vX, vY) in NED m/s - the world moves: advance / advance_sim move it along (option
         "obstacle_step_on_advance") and, with predict, prepare() writes the predicted obstacle set of every stage; predict=False holds the
-        world still inside the horizon (stage 0 only).  None: a world at rest."""
-        w = _as_world(world, self.B)
+        world still inside the horizon (stage 0 only).  None: a world at rest.
+        While a fleet is on (set_fleet) these are the FIXED entries, L <= 64 - (S - 1): the fleet's slots stay behind them, and vel None
+        gives the fixed entries zero velocities (the scene's world moves)."""
+        S = getattr(self, "_S", 0)
+        w = _as_world(world, self.B, 64 - (S - 1 if S else 0))
         v = None if vel is None else _as_world_vel(vel, self.B, w.shape[1])
+        if S and v is None:
+            v = np.zeros((self.B, w.shape[1], 2))
         self.s._check(self._lib.usvmpc_guidance_world(self.s._h, w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius)))
         self.s._check(self._lib.usvmpc_guidance_world_vel(self.s._h, None if v is None else v.ctypes.data_as(_capi._dp), 1 if predict else 0))
         self._L = w.shape[1]
+
+    def set_fleet(self, scene_size, radius=0.5):
+        """Vessel encounters: the batch is cut into scenes of scene_size = S consecutive instances, and every instance sees the other
+        S - 1 vessels of its scene - position, hull radius `radius`, velocity (u, v) turned by psi, from the state the plant left in x0 -
+        as moving world entries behind its fixed ones (set_world), refreshed on the device by every device-resident prepare().  B % S == 0;
+        after reset() and set_world() (an empty world will do).  Over a world at rest the scene is predicted per stage; a set_world(...,
+        predict=False) AFTER this call holds it still inside the horizon.  scene_size 0 or 1: off, the world list is the fixed entries again."""
+        self.s._check(self._lib.usvmpc_guidance_fleet(self.s._h, int(scene_size), float(radius)))
+        self._S = int(scene_size) if int(scene_size) >= 2 else 0
+
+    def fleet_state(self):
+        """dict(min_separation [B] (smallest distance to a vessel of the instance's scene, any tick; 1e300 before the first),
+        separation_tick [B] (the prepare it was met at; -1: none yet))."""
+        ms, st = np.zeros(self.B), np.zeros(self.B, dtype=np.int32)
+        self.s._check(self._lib.usvmpc_guidance_fleet_state(self.s._h, ms.ctypes.data_as(_capi._dp), st.ctypes.data_as(_capi._ip)))
+        return dict(min_separation=ms, separation_tick=st)
 
     def step_world(self, T):
         """The world moves on by T seconds (enqueued; a moving world only)."""
         self.s._check(self._lib.usvmpc_guidance_world_step(self.s._h, float(T)))
 
     def world(self):
-        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest."""
+        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest.  While a fleet is on L counts the
+        fixed entries and the S - 1 fleet entries behind them."""
         L = getattr(self, "_L", None)
         if L is None:
             raise Exception("world: no world list yet (set_world first)")
+        S = getattr(self, "_S", 0)
+        L += S - 1 if S else 0
         w, v = np.zeros((self.B, L, 3)), np.zeros((self.B, L, 2))
         self.s._check(self._lib.usvmpc_guidance_world_read(self.s._h, w.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp)))
         return w, v

@@ -462,3 +462,74 @@ def make_pf_encounters(scenes, S, seed=0, kind="parallel"):
             x0[b, 0], x0[b, 1], x0[b, 2], x0[b, 3] = psi, np.sin(psi), np.cos(psi), PF_ENC_SPEED
             x0[b, 10], x0[b, 11] = start
     return dict(waypoints=wp, x0=x0, world=np.zeros((B, 0, 3)))
+
+
+# ---- vessel encounters for usv_model_guidance_ca1 behind guidance.GuidanceFrontEnd.set_fleet (csrc/ca_fleet_world.hpp); scenes and slots
+# as fleet_vessels above
+def ca_fleet_world(x0, S, radius=0.5):
+    """The numpy restatement of the device's gather for the guidance model: x0 [B,8] = (u, v, ye, chie, psied, xned, yned, psi) ->
+    (entries [B,S-1,3] = (X, Y, R), vel [B,S-1,2] = (vX, vY), separation [B,S-1]) of every instance's scene-mates; X, Y = x0_j[5], x0_j[6],
+    vX = u cos psi - v sin psi, vY = u sin psi + v cos psi, separation = sqrt(dx dx + dy dy).  Every product and sum is rounded on its own:
+    entries and separations are the device's bits, the velocities agree to 8 * 2^-52 * (|u| + |v|) (two libraries' sin / cos)."""
+    x0 = np.asarray(x0, dtype=float)
+    B = x0.shape[0]
+    if S < 2 or B % S:
+        raise ValueError("ca_fleet_world: %d instances are not a whole number of scenes of %d (S >= 2)" % (B, S))
+    xj = x0[fleet_vessels(B, S)]                                   # [B, S-1, 8]
+    u, v = xj[..., 0], xj[..., 1]
+    s, c = np.sin(xj[..., 7]), np.cos(xj[..., 7])
+    entries = np.stack([xj[..., 5], xj[..., 6], np.full(u.shape, float(radius))], axis=2)
+    vel = np.stack([u * c + -(v * s), u * s + v * c], axis=2)
+    dx, dy = xj[..., 5] - x0[:, None, 5], xj[..., 6] - x0[:, None, 6]
+    return entries, vel, np.sqrt(dx * dx + dy * dy)
+
+
+# Encounter geometry, settled with tools/guidance_encounter_oracle.py (profiles/guidance_encounter_oracle.txt) under this model's SOFT
+# obstacle rows, whose keep-out distance between two hulls of radius 0.5 is 0.5 + 0.5 = 1.0 m:
+CA_ENC_LANE = 2.0            # m between neighbouring lanes, +- CA_ENC_LANE_JITTER per vessel
+CA_ENC_LANE_JITTER = 0.2
+CA_ENC_STAGGER = 0.5         # m: a vessel starts up to this far ahead of or behind its line
+CA_ENC_CROSS_OFFSET = 3.0    # m: a crossing vessel starts this much farther from the crossing point than the one it crosses (4.3 s at 0.7 m/s)
+CA_ENC_HEAD_ON_LATERAL = 1.1 # m: lateral offset of two opposing lanes (port to port), +- CA_ENC_LANE_JITTER per vessel
+CA_ENC_SPEED = 0.7           # (the node's speed set-point, D_SPEED)
+CA_ENC_KINDS = ("parallel", "crossing", "head_on")
+CA_ENC_OCP = dict(N=100, K=8, dt=0.05, max_radius=100.0)   # examples/scenario_sweep.py --resident: the reference's deployment
+
+
+def make_ca_encounters(scenes, S, seed=0, kind="parallel"):
+    """scenes * S missions, scene s (instances s S .. s S + S - 1) drawn from numpy.random.default_rng(seed + s): a scene does not depend on
+    the batch it is in.  Returns dict(waypoints [B,3,2], pose [B,3] = (nedx, nedy, psi), vel [B,2] = (CA_ENC_SPEED, 0), x0 [B,8] (the two in
+    the model's state order), world [B,0,3] - no fixed obstacle: the scene's vessels are the obstacles).  Every vessel sails a two-leg route,
+    vessel a of a scene, with lane l = a // 2 for the kinds that pair vessels up:
+      "parallel"   all northwards side by side: (x, -5) -> (x, -1) -> (x + 1.5, 2) with x = 4 + a (CA_ENC_LANE +- jitter)
+      "crossing"   even a northwards as above on x = 4 + l (lane); odd a westwards (9 + offset, y) -> (1, y) -> (-2, y + 1.5) with
+                   y = -2 + l (lane): it reaches the crossing point CA_ENC_CROSS_OFFSET (+- stagger) metres of sailing after the northbound one
+      "head_on"    even a northwards on x = 4 + 2 l (lane); odd a southwards (x', 3) -> (x', -1) -> (x' - 1.5, -4) on
+                   x' = 4 + 2 l (lane) - CA_ENC_HEAD_ON_LATERAL: the two pass port to port and turn away from each other."""
+    if kind not in CA_ENC_KINDS:
+        raise ValueError("make_ca_encounters: kind must be one of %s" % (CA_ENC_KINDS,))
+    B = scenes * S
+    wp, pose = np.zeros((B, 3, 2)), np.zeros((B, 3))
+    for s in range(scenes):
+        rng = np.random.default_rng(seed + s)
+        for a in range(S):
+            b = s * S + a
+            jit = rng.uniform(-CA_ENC_LANE_JITTER, CA_ENC_LANE_JITTER)
+            stag = rng.uniform(-CA_ENC_STAGGER, CA_ENC_STAGGER)
+            lane = a // 2
+            if kind == "parallel" or a % 2 == 0:
+                x = 4.0 + (a * CA_ENC_LANE if kind == "parallel" else (2 * lane if kind == "head_on" else lane) * CA_ENC_LANE) + jit
+                wp[b] = [[x, -5.0], [x, -1.0], [x + 1.5, 2.0]]
+                pose[b] = (x, -5.0 + stag, np.pi / 2)
+            elif kind == "crossing":
+                y = -2.0 + lane * CA_ENC_LANE + jit
+                wp[b] = [[9.0 + CA_ENC_CROSS_OFFSET, y], [1.0, y], [-2.0, y + 1.5]]
+                pose[b] = (7.0 + CA_ENC_CROSS_OFFSET + stag, y, np.pi)
+            else:
+                x = 4.0 + 2 * lane * CA_ENC_LANE - CA_ENC_HEAD_ON_LATERAL + jit
+                wp[b] = [[x, 3.0], [x, -1.0], [x - 1.5, -4.0]]
+                pose[b] = (x, 3.0 + stag, -np.pi / 2)
+    vel = np.column_stack([np.full(B, CA_ENC_SPEED), np.zeros(B)])
+    x0 = np.zeros((B, 8))
+    x0[:, 0:2], x0[:, 5:8] = vel, pose
+    return dict(waypoints=wp, pose=pose, vel=vel, x0=x0, world=np.zeros((B, 0, 3)))

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""The vessel encounters of scenario.make_ca_encounters in closed loop ON THE CPU: the reference node's arithmetic from the CPU oracle
+(oracle.binding.obstacle_sim / guidance_prepare / guidance_publish, per instance), in front of it the numpy gather scenario.ca_fleet_world -
+every vessel's scene-mates as moving world entries, from the states the plant left -, numpy's per-stage prediction P + (k dt) v of the chosen
+entries, then the CPU oracle's SQP-RTI step on usv_model_guidance_ca1; the plant is the controller's prediction x_1.  The loop
+examples/ca_encounter_sweep.py runs on the device, restated without one.  No GPU, no solver library.
+
+Prints finish ticks, separations, clearances and failure counts per kind.  It is the yardstick the device's encounters are held against
+(profiles/guidance_encounter_oracle.txt; tests/test_gpu_guidance_fleet.py copies its figures) and the place where the generator's constants
+were settled (--lane / --cross-offset / --lateral override scenario.CA_ENC_LANE / CA_ENC_CROSS_OFFSET / CA_ENC_HEAD_ON_LATERAL).
+
+    python tools/guidance_encounter_oracle.py --scenes 32 --scene-size 2 --ticks 400 --write
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mpc_collisionavoidance_amd import scenario  # noqa: E402
+from oracle import binding as oracle  # noqa: E402
+
+MODEL_GUIDANCE_CA1 = 1
+
+
+def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=None, K=None, quiet=False, out=None):
+    cfg = scenario.CA_ENC_OCP
+    N, K, dt, max_radius = N or cfg["N"], K or cfg["K"], cfg["dt"], cfg["max_radius"]
+    m = scenario.make_ca_encounters(scenes, S, seed, kind)
+    B = scenes * S
+    wps = m["waypoints"]
+    npts = wps.shape[1]
+    fixed = m["world"].copy()
+    fvel = np.zeros((B, fixed.shape[1], 2))
+    spec = oracle.spec(MODEL_GUIDANCE_CA1, N, N * dt, K)
+    state = [oracle.guidance_reset(wps[b].ravel(), m["pose"][b, 2]) for b in range(B)]
+    k, pp = np.array([s[0] for s in state]), np.array([s[1] for s in state], dtype=np.float32)
+    X = m["x0"].copy()                                         # the plant's state, what the device keeps in x0
+    x = np.ascontiguousarray(np.tile(X[:, None, :], (1, N + 1, 1)))
+    u = np.zeros((B, N, 1))
+    p, lh = np.zeros((B, N + 1, 2 * K)), np.zeros((B, N, K))
+    yref, yref_e = np.zeros((B, N, spec_ny(spec, x, u))), np.zeros((B, x.shape[2]))
+    fails = np.zeros(ticks, dtype=int)
+    min_sep, sep_tick = np.full(B, 1e300), np.full(B, -1)
+    min_clear, finish = np.full(B, 1e300), np.full(B, -1)
+    status = np.zeros(B, dtype=np.int32)
+    kdt = (np.arange(N + 1, dtype=float) * dt)[:, None, None]
+    for t in range(ticks):
+        ent, vel, sep = scenario.ca_fleet_world(X, S, radius)
+        for e in range(S - 1):
+            win = sep[:, e] < min_sep
+            min_sep[win], sep_tick[win] = sep[win, e], t
+        world, wvel = np.concatenate([fixed, ent], axis=1), np.concatenate([fvel, vel], axis=1)
+        x0 = X.copy()
+        ak = np.zeros(B)
+        active = np.zeros(B, dtype=int)
+        for b in range(B):
+            if k[b] >= npts:                                   # over before this tick: x0, p and lh are kept
+                if finish[b] < 0:
+                    finish[b] = t
+                continue
+            pose = X[b, 5:8]
+            body, n = oracle.obstacle_sim(pose, world[b], max_radius)
+            r = oracle.guidance_prepare(K, X[b, 0:2], pose, wps[b].ravel(), body, k[b], pp[b])
+            vis = np.nonzero(np.sqrt((world[b, :, 0] - pose[0]) ** 2 + (world[b, :, 1] - pose[1]) ** 2) < max_radius)[0]
+            assert len(vis) == n
+            if n:
+                d = np.sqrt((pose[0] - world[b, vis, 0]) ** 2 + (pose[1] - world[b, vis, 1]) ** 2) - (world[b, vis, 2] + 0.5)
+                min_clear[b] = min(min_clear[b], d.min())
+            if predict:
+                _, _, ch = oracle.guidance_obstacles(K, pose[2], pose[0], pose[1], body)
+                v = np.array([wvel[b, vis[c]] if c >= 0 else (0.0, 0.0) for c in ch]).reshape(K, 2)
+                p[b] = (r["p_obs"].reshape(K, 2)[None] + kdt * v[None]).reshape(N + 1, 2 * K)
+            else:
+                p[b] = r["p_obs"][None]
+            lh[b] = r["r_obs"][None]
+            k[b], active[b] = r["k"], r["active"]
+            if r["active"]:
+                x0[b], pp[b], ak[b] = r["x0"], r["past_psied"], r["ak"]
+            else:
+                finish[b] = t
+        status, its = oracle.rti_batch(spec, x, u, x0, yref, yref_e, p, lh, threads=threads)
+        fails[t] = int((status != 0).sum())
+        for b in np.nonzero(active)[0]:
+            pp[b] = oracle.guidance_publish(x[b, 1, 4], u[b, 0, 0], ak[b], pp[b])["past_psied"]
+        X[:] = x[:, 1]                   # the hand-over: the plant is the controller's prediction, no trajectory shift
+        fixed[:, :, :2] = fixed[:, :, :2] + dt * fvel
+    res = dict(finish_tick=finish, min_clearance=min_clear, min_separation=min_sep, separation_tick=sep_tick, failures_per_tick=fails,
+               final_status=status, waypoint_index=k.copy())
+    if not quiet:
+        fin = finish >= 0
+        lines = ["kind %s: %d scenes of %d, seeds %d .. %d, %d ticks, N %d, K %d, %s" % (
+                     kind, scenes, S, seed, seed + scenes - 1, ticks, N, K, "predicted per stage" if predict else "held still inside the horizon"),
+                 "  constants: lane %.3g +- %.3g, stagger %.3g, crossing offset %.3g, head-on lateral offset %.3g" % (
+                     scenario.CA_ENC_LANE, scenario.CA_ENC_LANE_JITTER, scenario.CA_ENC_STAGGER, scenario.CA_ENC_CROSS_OFFSET,
+                     scenario.CA_ENC_HEAD_ON_LATERAL),
+                 "  finished %d of %d%s" % (fin.sum(), B, ", at ticks %d .. %d" % (finish[fin].min(), finish[fin].max()) if fin.any() else ""),
+                 "  smallest min_separation %.4f m (median %.4f), met at tick %d" % (min_sep.min(), np.median(min_sep), sep_tick[min_sep.argmin()]),
+                 "  smallest min_clearance %.4f m (median %.4f)" % (min_clear.min(), np.median(min_clear)),
+                 "  failed solves %d over all ticks (%d ticks with at least one)" % (fails.sum(), (fails > 0).sum()),
+                 "  not finished: instances %s, waypoint index %s" % (np.nonzero(~fin)[0].tolist(), k[~fin].tolist()),
+                 "  finish ticks %s" % finish.tolist(),
+                 "  min_separation %s" % np.round(min_sep, 4).tolist()]
+        print("\n".join(lines), flush=True)
+        if out is not None:
+            out.extend(lines)
+    return res
+
+
+def spec_ny(spec, x, u):
+    """rows of the stage reference: this model's y is (x, u)"""
+    return x.shape[2] + u.shape[2]
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--scenes", type=int, default=32)
+    ap.add_argument("--scene-size", type=int, default=2)
+    ap.add_argument("--ticks", type=int, default=400)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--horizon", type=int, default=None)
+    ap.add_argument("--kinds", default=",".join(scenario.CA_ENC_KINDS))
+    ap.add_argument("--no-predict", action="store_true", help="the scene held still inside the horizon (set_world(..., predict=False))")
+    ap.add_argument("--lane", type=float, default=None)
+    ap.add_argument("--cross-offset", type=float, default=None)
+    ap.add_argument("--lateral", type=float, default=None)
+    ap.add_argument("--write", action="store_true", help="also write profiles/guidance_encounter_oracle.txt")
+    a = ap.parse_args()
+    if a.lane is not None:
+        scenario.CA_ENC_LANE = a.lane
+    if a.cross_offset is not None:
+        scenario.CA_ENC_CROSS_OFFSET = a.cross_offset
+    if a.lateral is not None:
+        scenario.CA_ENC_HEAD_ON_LATERAL = a.lateral
+    text = ["# tools/guidance_encounter_oracle.py --scenes %d --scene-size %d --ticks %d --seed %d%s" % (
+        a.scenes, a.scene_size, a.ticks, a.seed, " --no-predict" if a.no_predict else ""),
+        "# the CPU oracle behind its own node arithmetic and the numpy gather: the yardstick of tests/test_gpu_guidance_fleet.py"]
+    for kind in a.kinds.split(","):
+        run(a.scenes, a.scene_size, a.ticks, kind, seed=a.seed, predict=not a.no_predict, threads=a.threads, N=a.horizon, out=text)
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "guidance_encounter_oracle.txt"), "w") as f:
+            f.write("\n".join(text) + "\n")

@@ -8,6 +8,13 @@ costs, three ways (needs an MI355X):
   moving    the same over a moving world that is predicted: prepare() writes p / lh of every stage
   held      the moving world held still inside the horizon (predict = 0): stage 0 only
 
+With --fleet S the batch is cut into scenes of S vessels that are each other's moving obstacles (GuidanceFrontEnd.set_fleet; vessel a of a
+scene starts 2 a metres to the side), the world of every resident mode moves, and two more modes exist: `fleet` is `moving` with the fleet
+on - prepare() gathers the scene-mates on the device ahead of usv_guidance_tick -, and `fleethost` is the loop a handle without the fleet
+needs for the same scenes: synchronise, read x0 and the world back, rebuild the S - 1 trailing entries and velocities in numpy
+(scenario.ca_fleet_world), upload, then the same four calls.  tick_net_of_qp_ms_median is the tick without the QP launch.  The JSON lines
+also go to --out (default with --fleet: profiles/guidance_fleet_probe.txt).
+
 Per run one JSON line: the median tick (a host clock around the loop's body, ending in a synchronisation for the resident modes), and for the
 resident modes the HIP-event time of the prepare's kernel (usv_guidance_tick: events on the solver's stream either side of it), the bytes a
 predicted tick streams divided by that time, usvmpc_pipeline_stats, and how many missions kept their clearance.  --runs alternating runs.
@@ -17,6 +24,7 @@ host-fed figures were taken at the commit before the resident mode existed.
 
     python tools/guidance_mission_probe.py --batch 8192
     python tools/guidance_mission_probe.py --batch 65536 --modes resident,moving,held
+    python tools/guidance_mission_probe.py --batch 65536 --fleet 4 --entries 4 --modes moving,fleet,fleethost
 """
 import argparse
 import json
@@ -44,9 +52,9 @@ def missions(B, L, seed):
                 world=world, world_vel=wvel)
 
 
-def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0):
+def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5):
     import torch
-    from mpc_collisionavoidance_amd import BatchOcpSolver, usv_models
+    from mpc_collisionavoidance_amd import BatchOcpSolver, scenario, usv_models
     from mpc_collisionavoidance_amd.guidance import GuidanceFrontEnd
     dt = 0.05
     m = missions(B, L, seed)
@@ -55,7 +63,9 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0):
     world, pose, vel = m["world"], m["pose"], m["vel"]
     fe.reset(m["waypoints"], pose[:, 2])
     times, tick_ms = [], []
-    out = dict(mode=mode, batch=B, N=N, K=K, L=L, ticks=ticks, warmup=warmup)
+    out = dict(mode=mode, batch=B, N=N, K=K, L=L, ticks=ticks, warmup=warmup, fleet=fleet)
+    if mode in ("fleet", "fleethost") and fleet < 2:
+        raise SystemExit("modes fleet and fleethost need --fleet S with S >= 2")
     if mode == "hostfed":
         min_clear = np.full(B, np.inf)
         for t in range(warmup + ticks):
@@ -72,11 +82,25 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0):
     else:
         x0 = np.zeros((B, 8))
         x0[:, 0:2], x0[:, 5:8] = vel, pose
+        if fleet:
+            x0[:, 5] += 2.0 * (np.arange(B) % fleet)
         s.set("x0", 0, x0)
-        fe.set_world(world, max_radius=100.0, vel=m["world_vel"] if mode in ("moving", "held") else None, predict=mode != "held")
+        if mode == "fleethost":            # the same list, the trailing S - 1 entries the host's to fill
+            fe.set_world(np.concatenate([world, np.tile([1000.0, 1000.0, 0.0], (B, fleet - 1, 1))], axis=1), max_radius=100.0,
+                         vel=np.concatenate([m["world_vel"], np.zeros((B, fleet - 1, 2))], axis=1))
+        else:
+            fe.set_world(world, max_radius=100.0, vel=m["world_vel"] if mode in ("moving", "held", "fleet") or fleet else None,
+                         predict=mode != "held")
+        if mode == "fleet":
+            fe.set_fleet(fleet, radius)
         s.sync()
         for t in range(warmup + ticks):
             t0 = time.perf_counter()
+            if mode == "fleethost":
+                xr = s.get("x0", 0)         # (synchronises)
+                w, v = fe.world()
+                w[:, L:], v[:, L:], _ = scenario.ca_fleet_world(xr, fleet, radius)
+                fe.set_world(w, max_radius=100.0, vel=v)
             fe.prepare()
             s.solve_async()
             fe.publish(fetch=False)
@@ -89,7 +113,7 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0):
         # caller's stream no longer pipelines its lineariser (usvmpc_set_stream)
         stream = torch.cuda.Stream()
         s.set_stream(stream.cuda_stream)
-        for t in range(warmup + ticks):
+        for t in range(0 if mode == "fleethost" else warmup + ticks):   # (fleethost: the kernels are those of `moving`)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             fe.prepare()
@@ -101,16 +125,17 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0):
             tick_ms.append(e0.elapsed_time(e1))
         st = fe.mission_state()
         min_clear = st["min_clearance"]
-        k_ms = statistics.median(tick_ms[warmup:])
-        nbytes = B * ((N + 1) * 2 * K + N * K) * 8 if mode == "moving" else 0
+        k_ms = statistics.median(tick_ms[warmup:]) if tick_ms else 0.0
+        tick_ms = tick_ms or [0.0] * (warmup + 1)
+        nbytes = B * ((N + 1) * 2 * K + N * K) * 8 if mode in ("moving", "fleet") else 0
         out.update(guidance_tick_ms_median=k_ms, guidance_tick_ms_min=min(tick_ms[warmup:]), streamed_bytes=nbytes,
-                   stream_TB_per_s=(nbytes / (k_ms * 1e-3) / 1e12) if nbytes else 0.0, pipelined_linearisations_used=int(used),
+                   stream_TB_per_s=(nbytes / (k_ms * 1e-3) / 1e12) if nbytes and k_ms else 0.0, pipelined_linearisations_used=int(used),
                    pipelined_linearisations_discarded=int(discarded))
     timed = times[warmup:]
     if mode == "hostfed":
         lin, qp = s.kernel_ms(ticks)
     out.update(tick_ms_median=statistics.median(timed), tick_ms_min=min(timed), tick_ms_max=max(timed), linearize_ms_median=float(np.median(lin)),
-               qp_ms_median=float(np.median(qp)), failed_last_tick=int(s.fail_counts(1)[0]),
+               qp_ms_median=float(np.median(qp)), tick_net_of_qp_ms_median=statistics.median(timed) - float(np.median(qp)), failed_last_tick=int(s.fail_counts(1)[0]),
                missions_clear_of_keepout=int((min_clear > 0.0).sum()), min_clearance_worst=float(min_clear.min()))
     s.close()
     return out
@@ -123,14 +148,22 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--modes", default="hostfed,resident,moving")
+    ap.add_argument("--fleet", type=int, default=0, help="scenes of this many vessels (modes fleet, fleethost); the world of every resident mode moves")
+    ap.add_argument("--entries", type=int, default=5, help="world entries per instance (with --fleet: the fixed ones)")
     ap.add_argument("--root", default=HERE, help="the checkout whose package is imported (default: this one)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well (the record: profiles/guidance_mission_probe.txt)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import torch  # noqa: F401  (before the solver library: one HIP runtime for both)
+    if a.fleet and not a.out:
+        a.out = os.path.join(HERE, "profiles", "guidance_fleet_probe.txt")
+    if a.fleet:
+        with open(a.out, "a") as f:
+            f.write("# tools/guidance_mission_probe.py --batch %d --fleet %d --entries %d --modes %s --ticks %d --warmup %d --runs %d\n" % (
+                a.batch, a.fleet, a.entries, a.modes, a.ticks, a.warmup, a.runs))
     for r in range(a.runs):
         for mode in a.modes.split(","):
-            line = run(mode, a.batch, a.ticks, a.warmup)
+            line = run(mode, a.batch, a.ticks, a.warmup, L=a.entries, fleet=a.fleet)
             line["run"] = r
             line["root"] = "this tree" if os.path.abspath(a.root) == HERE else "another checkout"
             print(json.dumps(line), flush=True)
