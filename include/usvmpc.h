@@ -622,6 +622,45 @@ int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr);
 int usvmpc_eval_cost(usvmpc_handle *h);
 int usvmpc_cost_track(usvmpc_handle *h, int on);
 int usvmpc_cost_tracked(usvmpc_handle *h, double *sum, long long *count);
+/* ---- Cascade: the two-layer control stack the reference deploys, closed on a vessel with inertia.  The guidance layer (a
+ * usv_model_guidance_ca1 handle of THIS library with its device-resident front end) runs every `ratio`-th tick and publishes a desired
+ * heading and speed; the low-level NMPC (OCP usv_model_low_level: nx = 8, nu = 2, no obstacles; the node: nmpc_low_level.cpp) runs every
+ * tick and turns them into thrusts; a 3-DOF vessel s = (nedx, nedy, psi, u, v, r) integrates the PUBLISHED thrusts over T in num_steps RK4
+ * steps, with the starboard factor c (0.78: the low-level model's).  The low-level solver lives in a library generated for its model, so it
+ * is handed over as raw device pointers (usvmpc_get_device_ptr of ITS library: "x0", "x", "yref", "yref_e"), its horizon ll_N and its batch;
+ * the caller keeps it on the guidance handle's stream, with options "pipeline_linearize" 0 and "host_mirror" 0 (its yref and x0 are written
+ * behind its back: every solve must linearise afresh from device memory).  One low-level tick t = 0, 1, ..:
+ *     [t % ratio == 0:  usvmpc_guidance_prepare(h, NULL ..) -> usvmpc_solve_async(h) -> usvmpc_guidance_publish(h, NULL ..)]
+ *     usvmpc_cascade_refs -> low-level usvmpc_solve_async -> usvmpc_cascade_step
+ * No usvmpc_advance of either solver: the closed-loop log and the tracked cost hang on the hand-overs and do not see cascade ticks.
+ *   create   USVMPC_E_ARG with a message (usvmpc_cascade_last_error(NULL)), nothing made: another guidance model; no usvmpc_guidance_reset
+ *            or no world list yet; ratio < 1, num_steps < 1, T <= 0; T or c not finite; ratio * T different from the guidance handle's
+ *            shooting interval; a null device pointer; ll_batch different from the guidance handle's batch; yref / yref_e not 16-byte
+ *            aligned.  The object owns its device buffers; the guidance handle allocates nothing and launches what it launched before.
+ *   reset    pose [batch][3] = (nedx, nedy, psi), vel [batch][3] = (u, v, r): the vessel's state; published and past thrusts 0, tick 0, error
+ *            sums 0, yref_writes 0, every instance's reference rows due at the first refs.  Writes the guidance handle's x0[0, 1, 5, 6, 7] =
+ *            (u, v, nedx, nedy, psi).  Synchronises.  The low-level initial iterate is the caller's business.
+ *   refs     kernel usv_cascade_refs, enqueued: low-level x0 = (psi, sin psi, cos psi, u (0 -> 0.001), v, r, past thrusts); yref rows
+ *            (psi_des, sin, cos, u_des, 0 ..) x ll_N and yref_e rewritten for the instances whose (heading, speed) bits differ from what was
+ *            last written - yref_writes counts them.
+ *   step     kernel usv_cascade_step, enqueued: thrusts = (x_1[6], x_1[7]) of the low-level iterate, both 0 while u_des == 0; past thrusts =
+ *            x_1[6], x_1[7] regardless; e_u = (float)(u_des - u), e_psi = (float)(psi_des - psi) into the running sums; one plant period;
+ *            sigma * N(0,1) on (u, v, r), drawn as usvmpc_advance draws (key (instance_offset + b) * 6 + j, j = 3, 4, 5).  When the next tick is
+ *            a guidance tick the vessel's state goes into the guidance handle's x0[0, 1, 5, 6, 7] and a moving guidance world moves on by
+ *            ratio * T (option "obstacle_step_on_advance").
+ *   state    state [batch][6], thrust [batch][2], past_thrust [batch][2], ticks [batch], yref_writes, err_sums [batch][4] = (sum |e_u|,
+ *            sum |e_psi|, sum e_u^2, sum e_psi^2); any may be NULL; synchronises.
+ *   destroy  before the guidance handle is destroyed. */
+typedef struct usvmpc_cascade usvmpc_cascade;
+int usvmpc_cascade_create(usvmpc_handle *guidance, int ratio, double T, int num_steps, double c, long long instance_offset, int ll_batch,
+                          int ll_N, void *ll_x0, void *ll_x, void *ll_yref, void *ll_yref_e, usvmpc_cascade **out);
+int usvmpc_cascade_destroy(usvmpc_cascade *c);
+int usvmpc_cascade_reset(usvmpc_cascade *c, const double *pose, const double *vel);
+int usvmpc_cascade_refs(usvmpc_cascade *c);
+int usvmpc_cascade_step(usvmpc_cascade *c, double sigma, unsigned long long seed);
+int usvmpc_cascade_state(usvmpc_cascade *c, double *state, double *thrust, double *past_thrust, int *ticks, long long *yref_writes,
+                         double *err_sums);
+const char *usvmpc_cascade_last_error(usvmpc_cascade *c);
 /* bytes of device memory held by the handle */
 size_t usvmpc_device_bytes(usvmpc_handle *h);
 const char *usvmpc_last_error(usvmpc_handle *h);

@@ -74,7 +74,9 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
            "usvmpc_guidance_mission_state", "usvmpc_guidance_fleet", "usvmpc_guidance_fleet_state",
            "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr",
-           "usvmpc_eval_cost", "usvmpc_cost_track", "usvmpc_cost_tracked"]
+           "usvmpc_eval_cost", "usvmpc_cost_track", "usvmpc_cost_tracked",
+           "usvmpc_cascade_create", "usvmpc_cascade_destroy", "usvmpc_cascade_reset", "usvmpc_cascade_refs", "usvmpc_cascade_step",
+           "usvmpc_cascade_state", "usvmpc_cascade_last_error"]
 
 
 class LogDesc(C.Structure):
@@ -182,6 +184,16 @@ def load(path):
     L.usvmpc_eval_cost.argtypes = [C.c_void_p]
     L.usvmpc_cost_track.argtypes = [C.c_void_p, C.c_int]
     L.usvmpc_cost_tracked.argtypes = [C.c_void_p, _dp, _llp]
+    if hasattr(L, "usvmpc_cascade_create"):
+        L.usvmpc_cascade_create.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_longlong, C.c_int, C.c_int] + \
+            [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
+        L.usvmpc_cascade_destroy.argtypes = [C.c_void_p]
+        L.usvmpc_cascade_reset.argtypes = [C.c_void_p, _dp, _dp]
+        L.usvmpc_cascade_refs.argtypes = [C.c_void_p]
+        L.usvmpc_cascade_step.argtypes = [C.c_void_p, C.c_double, C.c_ulonglong]
+        L.usvmpc_cascade_state.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _llp, _dp]
+        L.usvmpc_cascade_last_error.argtypes = [C.c_void_p]
+        L.usvmpc_cascade_last_error.restype = C.c_char_p
     L.usvmpc_device_bytes.argtypes = [C.c_void_p]
     L.usvmpc_device_bytes.restype = C.c_size_t
     L.usvmpc_last_error.argtypes = [C.c_void_p]

@@ -25,6 +25,7 @@
 #include "gfx950/lanes.hpp"
 
 #include "ca_fleet_world.hpp"
+#include "cascade.hpp"
 #include "closed_loop_log.hpp"
 #include "cost_eval.hpp"
 #include "fleet_world.hpp"
@@ -998,6 +999,127 @@ __global__ void __launch_bounds__(256) usv_guidance_tick(DevPtrs P, GuidancePtrs
             rem += 512;
             while (rem >= per) { rem -= per; inst++; }
         }
+    }
+}
+
+// ---- The two-layer control stack (usvmpc_cascade_*; the arithmetic: cascade.hpp): guidance layer -> low-level NMPC -> vessel.
+constexpr int CAS_GROUP = 64; // instances per workgroup of usv_cascade_refs
+
+static __global__ void usv_cascade_reset(CascadePtrs C, const double *pose, const double *vel, double *gx0, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) *C.yref_writes = 0ull;
+    if (b >= B) return;
+    double *s = C.s + (long)b * CAS_NS;
+    s[0] = pose[3 * b]; s[1] = pose[3 * b + 1]; s[2] = pose[3 * b + 2];
+    s[3] = vel[3 * b]; s[4] = vel[3 * b + 1]; s[5] = vel[3 * b + 2];
+    C.thr[2 * b] = 0.0; C.thr[2 * b + 1] = 0.0;
+    C.past[2 * b] = 0.0; C.past[2 * b + 1] = 0.0;
+    C.last[2 * b] = cas_never(); C.last[2 * b + 1] = cas_never();
+    C.ticks[b] = 0;
+    C.sums[4 * b] = C.sums[4 * b + 1] = C.sums[4 * b + 2] = C.sums[4 * b + 3] = 0.0;
+    double *x0 = gx0 + (long)b * CA_NX; // the entries usv_guidance_tick and usv_guidance_fleet_gather read
+    x0[0] = s[3]; x0[1] = s[4]; x0[5] = s[0]; x0[6] = s[1]; x0[7] = s[2];
+}
+
+// usv_cascade_refs: the low-level node's input side.  One workgroup per CAS_GROUP consecutive instances, laid out as usv_pf_prepare:
+// 1. Decide: the first wave, one lane per instance - the low-level x0 (eight doubles) from the vessel's state and the past thrusts, the
+//    guidance layer's published (heading, speed), and whether the instance's reference rows must be rewritten: only when the bits of the pair
+//    differ from what it last wrote.  One sine and one cosine per rewritten instance, by this lane; the row's four values go to LDS.
+// 2. Stream: the workgroup's yref rows are ONE contiguous run of CAS_GROUP * ll_N * 10 doubles (524 MB over 65 536 instances at N = 100, on
+//    every guidance tick: the heading moves every tick).  All 256 threads walk it in 16-byte stores, thread t the t-th pair of each 4 KiB
+//    pass (a wave's stores cover 1 KiB without gaps), skipping the instances that keep their rows.  yref_e (4 pairs per instance) likewise.
+// It writes memory of ANOTHER library's solver (CascadePtrs): that solver must linearise afresh from device memory at every solve.
+__global__ void __launch_bounds__(256) usv_cascade_refs(GuidancePtrs G, CascadePtrs C, int B)
+{
+    __shared__ double s_ref[CAS_GROUP][4];
+    __shared__ int s_write[CAS_GROUP];
+    __shared__ unsigned s_count;
+    const int t = (int)threadIdx.x, N = C.ll_N;
+    const long b0 = (long)blockIdx.x * CAS_GROUP;
+    const int cnt = (int)((long)B - b0 < (long)CAS_GROUP ? (long)B - b0 : (long)CAS_GROUP);
+    if (t == 0) s_count = 0u;
+    if (t < CAS_GROUP) s_write[t] = 0;
+    __syncthreads();
+    if (t < cnt) {
+        const long b = b0 + t;
+        cas_ll_x0(C.s + b * CAS_NS, C.past + 2 * b, C.ll_x0 + b * CAS_NX);
+        const double psi_des = G.heading[b], u_des = G.speed[b];
+        double *last = C.last + 2 * b;
+        if (cas_ref_changed(last, psi_des, u_des)) {
+            const CasRef r = cas_ref(psi_des, u_des);
+            last[0] = psi_des; last[1] = u_des;
+            s_ref[t][0] = r.psi; s_ref[t][1] = r.s; s_ref[t][2] = r.c; s_ref[t][3] = r.u;
+            s_write[t] = 1;
+            atomicAdd(&s_count, 1u);
+        }
+    }
+    __syncthreads();
+    const unsigned nwrite = s_count;
+    if (nwrite == 0u) return;
+    if (t == 0) atomicAdd(C.yref_writes, (unsigned long long)nwrite);
+    {
+        double2 *row = reinterpret_cast<double2 *>(C.ll_yref) + b0 * (long)N * (CAS_NY / 2);
+        const int per = N * (CAS_NY / 2), total = cnt * per; // pairs per instance / of the workgroup
+        int inst = 0, rem = t; // j = inst * per + rem
+        while (rem >= per) { rem -= per; inst++; }
+        for (int j = t; j < total; j += 256) {
+            if (s_write[inst]) {
+                const int pair = rem % (CAS_NY / 2);
+                const CasRef r = {s_ref[inst][0], s_ref[inst][1], s_ref[inst][2], s_ref[inst][3]};
+                double2 o;
+                o.x = cas_yref_entry(2 * pair, r);
+                o.y = cas_yref_entry(2 * pair + 1, r);
+                row[j] = o;
+            }
+            rem += 256;
+            while (rem >= per) { rem -= per; inst++; }
+        }
+    }
+    {
+        double2 *row = reinterpret_cast<double2 *>(C.ll_yref_e) + b0 * (long)(CAS_NX / 2);
+        for (int j = t; j < cnt * (CAS_NX / 2); j += 256) {
+            const int inst = j / (CAS_NX / 2), pair = j - inst * (CAS_NX / 2);
+            if (!s_write[inst]) continue;
+            const CasRef r = {s_ref[inst][0], s_ref[inst][1], s_ref[inst][2], s_ref[inst][3]};
+            double2 o;
+            o.x = cas_yref_entry(2 * pair, r);
+            o.y = cas_yref_entry(2 * pair + 1, r);
+            row[j] = o;
+        }
+    }
+}
+
+// usv_cascade_step: the low-level node's output side and the vessel.  One lane per instance: thrusts and past thrusts from stage 1 of the
+// low-level iterate, the errors against the state the solve saw, one plant period under the published thrusts, the optional disturbance on
+// (u, v, r) - keyed by the instance's GLOBAL index, as usv_advance -, and, when the NEXT low-level tick is a guidance tick (hand_over), the
+// vessel's state into the guidance solver's x0[0, 1, 5, 6, 7]: the entries usv_guidance_tick and usv_guidance_fleet_gather read, nothing a
+// lineariser reads.
+__global__ void __launch_bounds__(256) usv_cascade_step(CascadePtrs C, double *gx0, int B, double T, int steps, double c, double sigma,
+                                                        unsigned long long seed, long long offset, int hand_over)
+{
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= (long)B) return;
+    const double *x1 = C.ll_x + (b * (long)(C.ll_N + 1) + 1) * CAS_NX;
+    double s[CAS_NS], thr[2], past[2];
+    sfor<0, CAS_NS>([&](auto i) { s[i] = C.s[b * CAS_NS + i]; });
+    float e_u, e_psi;
+    cas_ll_outputs(x1, C.last[2 * b], C.last[2 * b + 1], s[2], cas_fix_u(s[3]), thr, past, e_u, e_psi);
+    C.thr[2 * b] = thr[0]; C.thr[2 * b + 1] = thr[1];
+    C.past[2 * b] = past[0]; C.past[2 * b + 1] = past[1];
+    {
+        double *sm = C.sums + 4 * b;
+        const double eu = (double)e_u, ep = (double)e_psi;
+        sm[0] = track_add(sm[0], fabs(eu)); sm[1] = track_add(sm[1], fabs(ep));
+        sm[2] = track_add(sm[2], track_mul(eu, eu)); sm[3] = track_add(sm[3], track_mul(ep, ep));
+    }
+    cas_plant_period(s, thr, c, T, steps);
+    if (sigma != 0.0) sfor<3, CAS_NS>([&](auto j) { s[j] += noise(sigma, seed, (unsigned long long)((offset + b) * CAS_NS + j)); });
+    sfor<0, CAS_NS>([&](auto i) { C.s[b * CAS_NS + i] = s[i]; });
+    C.ticks[b] += 1;
+    if (hand_over) {
+        double *x0 = gx0 + b * CA_NX;
+        x0[0] = s[3]; x0[1] = s[4]; x0[5] = s[0]; x0[6] = s[1]; x0[7] = s[2];
     }
 }
 
@@ -3877,6 +3999,165 @@ int usvmpc_calibrate_traffic(usvmpc_handle *h, int nplanes, double *bytes_read, 
     if (bytes_written) *bytes_written = (double)stride * 8.0;
     return 0;
 }
+
+// ---- the two-layer control stack (include/usvmpc.h, "Cascade"): kernels usv_cascade_refs / usv_cascade_step above, arithmetic cascade.hpp.
+// The object owns its buffers (plain hipMalloc: the guidance handle's allocation table and usvmpc_device_bytes are untouched) and works on
+// the guidance handle's stream as it is at each call; the low-level solver is a set of device pointers into another library's handle.
+struct usvmpc_cascade {
+    usvmpc_handle *g;
+    int ratio, num_steps;
+    double T, c;
+    long long offset;
+    long long tick;   // low-level ticks stepped since the last reset
+    bool ready;       // usvmpc_cascade_reset has run
+    CascadePtrs p;
+    double *d_pose, *d_vel; // [B][3] each: staging of usvmpc_cascade_reset
+    std::string err;
+};
+thread_local std::string g_cascade_create_err;
+
+#define CAS_TRY(c, call)                                                                          \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
+            return USVMPC_E_HIP;                                                                  \
+        }                                                                                         \
+    } while (0)
+
+static void cascade_free(usvmpc_cascade *c)
+{
+    CascadePtrs &p = c->p;
+    (void)hipFree(p.s); (void)hipFree(p.thr); (void)hipFree(p.past); (void)hipFree(p.last); (void)hipFree(p.ticks); (void)hipFree(p.sums);
+    (void)hipFree(p.yref_writes); (void)hipFree(c->d_pose); (void)hipFree(c->d_vel);
+}
+
+int usvmpc_cascade_create(usvmpc_handle *guidance, int ratio, double T, int num_steps, double c, long long instance_offset, int ll_batch,
+                          int ll_N, void *ll_x0, void *ll_x, void *ll_yref, void *ll_yref_e, usvmpc_cascade **out)
+{
+    std::string &err = g_cascade_create_err;
+    if (out) *out = nullptr;
+    if (!guidance || !out) { err = "usvmpc_cascade_create: null guidance handle or output"; return USVMPC_E_ARG; }
+    usvmpc_handle *h = guidance;
+    if (h->desc.model != USVMPC_MODEL_GUIDANCE_CA1) { err = "usvmpc_cascade_create: the upper layer must be a usv_model_guidance_ca1 handle"; return USVMPC_E_ARG; }
+    if (!h->gd_ready || h->gd.npts < 2) { err = "usvmpc_cascade_create: usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
+    if (!h->gd_world_set) { err = "usvmpc_cascade_create: the guidance handle needs a world list (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
+    if (T - T != 0.0 || c - c != 0.0) { err = "usvmpc_cascade_create: T and c must be finite"; return USVMPC_E_ARG; }
+    if (ratio < 1 || num_steps < 1 || !(T > 0.0) || instance_offset < 0) { err = "usvmpc_cascade_create: ratio >= 1, num_steps >= 1, T > 0 and instance_offset >= 0 are needed"; return USVMPC_E_ARG; }
+    if (fabs((double)ratio * T - h->spec.dt) > 1e-9 * h->spec.dt) {
+        err = "usvmpc_cascade_create: ratio * T = " + std::to_string((double)ratio * T) + " differs from the guidance layer's shooting interval " +
+              std::to_string(h->spec.dt);
+        return USVMPC_E_ARG;
+    }
+    if (!ll_x0 || !ll_x || !ll_yref || !ll_yref_e) { err = "usvmpc_cascade_create: null device pointer of the low-level solver (x0, x, yref, yref_e)"; return USVMPC_E_ARG; }
+    if (ll_N < 1 || ll_batch != h->B) {
+        err = "usvmpc_cascade_create: the low-level solver needs ll_N >= 1 and the guidance handle's batch (" + std::to_string(h->B) + "), got ll_N " +
+              std::to_string(ll_N) + ", batch " + std::to_string(ll_batch);
+        return USVMPC_E_ARG;
+    }
+    if (((uintptr_t)ll_yref | (uintptr_t)ll_yref_e) & 15u) { err = "usvmpc_cascade_create: yref and yref_e of the low-level solver must be 16-byte aligned"; return USVMPC_E_ARG; }
+    usvmpc_cascade *cs = new usvmpc_cascade();
+    cs->g = h; cs->ratio = ratio; cs->num_steps = num_steps; cs->T = T; cs->c = c; cs->offset = instance_offset; cs->tick = 0; cs->ready = false;
+    cs->p = CascadePtrs{};
+    cs->d_pose = cs->d_vel = nullptr;
+    cs->p.ll_x0 = (double *)ll_x0; cs->p.ll_x = (const double *)ll_x; cs->p.ll_yref = (double *)ll_yref; cs->p.ll_yref_e = (double *)ll_yref_e;
+    cs->p.ll_N = ll_N;
+    const size_t B = (size_t)h->B;
+    hipError_t e = hipSetDevice(h->device);
+    auto get = [&](auto **ptr, size_t n) { if (e == hipSuccess) e = hipMalloc((void **)ptr, n * sizeof(**ptr)); };
+    get(&cs->p.s, B * CAS_NS); get(&cs->p.thr, B * 2); get(&cs->p.past, B * 2); get(&cs->p.last, B * 2); get(&cs->p.ticks, B);
+    get(&cs->p.sums, B * 4); get(&cs->p.yref_writes, (size_t)1); get(&cs->d_pose, B * 3); get(&cs->d_vel, B * 3);
+    if (e != hipSuccess) {
+        err = std::string("usvmpc_cascade_create: ") + hipGetErrorString(e);
+        cascade_free(cs);
+        delete cs;
+        return USVMPC_E_HIP;
+    }
+    *out = cs;
+    return 0;
+}
+
+int usvmpc_cascade_destroy(usvmpc_cascade *c)
+{
+    if (!c) return USVMPC_E_ARG;
+    (void)hipSetDevice(c->g->device);
+    (void)hipStreamSynchronize(c->g->stream);
+    cascade_free(c);
+    delete c;
+    return 0;
+}
+
+int usvmpc_cascade_reset(usvmpc_cascade *c, const double *pose, const double *vel)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!pose || !vel) { c->err = "cascade_reset: null pose or vel"; return USVMPC_E_ARG; }
+    usvmpc_handle *h = c->g;
+    const size_t B = (size_t)h->B;
+    for (size_t i = 0; i < 3 * B; i++)
+        if (pose[i] - pose[i] != 0.0 || vel[i] - vel[i] != 0.0) { c->err = "cascade_reset: entry " + std::to_string(i) + " of pose or vel is not finite"; return USVMPC_E_ARG; }
+    CAS_TRY(c, hipSetDevice(h->device));
+    if (mirror_flush(h)) { c->err = "cascade_reset: " + h->err; return USVMPC_E_HIP; } // (a pending host write of the guidance x0 goes up first)
+    CAS_TRY(c, hipMemcpyAsync(c->d_pose, pose, 3 * B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CAS_TRY(c, hipMemcpyAsync(c->d_vel, vel, 3 * B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(usv_cascade_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, c->p, (const double *)c->d_pose,
+                       (const double *)c->d_vel, const_cast<double *>(h->ptrs.x0), (int)B);
+    CAS_TRY(c, hipGetLastError());
+    CAS_TRY(c, hipStreamSynchronize(h->stream)); // (the copies read caller memory)
+    c->tick = 0;
+    c->ready = true;
+    return 0;
+}
+
+int usvmpc_cascade_refs(usvmpc_cascade *c)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!c->ready) { c->err = "cascade_refs: usvmpc_cascade_reset must be called first"; return USVMPC_E_ARG; }
+    usvmpc_handle *h = c->g;
+    CAS_TRY(c, hipSetDevice(h->device));
+    hipLaunchKernelGGL(usv_cascade_refs, dim3((unsigned)((h->B + CAS_GROUP - 1) / CAS_GROUP)), dim3(256), 0, h->stream, h->gd, c->p, h->B);
+    CAS_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int usvmpc_cascade_step(usvmpc_cascade *c, double sigma, unsigned long long seed)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!c->ready) { c->err = "cascade_step: usvmpc_cascade_reset must be called first"; return USVMPC_E_ARG; }
+    if (sigma - sigma != 0.0) { c->err = "cascade_step: sigma is not finite"; return USVMPC_E_ARG; }
+    usvmpc_handle *h = c->g;
+    CAS_TRY(c, hipSetDevice(h->device));
+    const bool hand_over = cas_hands_over(c->tick, c->ratio);
+    if (hand_over && mirror_flush(h)) { c->err = "cascade_step: " + h->err; return USVMPC_E_HIP; }
+    hipLaunchKernelGGL(usv_cascade_step, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, c->p, const_cast<double *>(h->ptrs.x0),
+                       h->B, c->T, c->num_steps, c->c, sigma, seed, c->offset, hand_over ? 1 : 0);
+    CAS_TRY(c, hipGetLastError());
+    c->tick++;
+    // a guidance period has passed: the guidance layer's moving world follows, as usvmpc_advance would have moved it
+    if (hand_over && h->gd_moving && h->opt.step_on_advance && usvmpc_guidance_world_step(h, (double)c->ratio * c->T)) {
+        c->err = "cascade_step: " + h->err;
+        return USVMPC_E_HIP;
+    }
+    return 0;
+}
+
+int usvmpc_cascade_state(usvmpc_cascade *c, double *state, double *thrust, double *past_thrust, int *ticks, long long *yref_writes, double *err_sums)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!c->ready) { c->err = "cascade_state: usvmpc_cascade_reset must be called first"; return USVMPC_E_ARG; }
+    usvmpc_handle *h = c->g;
+    const size_t B = (size_t)h->B;
+    CAS_TRY(c, hipSetDevice(h->device));
+    if (state) CAS_TRY(c, hipMemcpyAsync(state, c->p.s, B * CAS_NS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (thrust) CAS_TRY(c, hipMemcpyAsync(thrust, c->p.thr, B * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (past_thrust) CAS_TRY(c, hipMemcpyAsync(past_thrust, c->p.past, B * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (ticks) CAS_TRY(c, hipMemcpyAsync(ticks, c->p.ticks, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (yref_writes) CAS_TRY(c, hipMemcpyAsync(yref_writes, c->p.yref_writes, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    if (err_sums) CAS_TRY(c, hipMemcpyAsync(err_sums, c->p.sums, B * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CAS_TRY(c, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+const char *usvmpc_cascade_last_error(usvmpc_cascade *c) { return c ? c->err.c_str() : g_cascade_create_err.c_str(); }
 
 int usvmpc_set_stream(usvmpc_handle *h, void *stream)
 {

@@ -312,3 +312,106 @@ def _as_rows(value, B, what):
     if a.size != 3 * B:
         raise Exception("%s: expected [%d, 3], got %s" % (what, B, list(a.shape)))
     return np.ascontiguousarray(a.reshape(B, 3))
+
+
+class Cascade:
+    """The two-layer control stack the reference deploys, closed on a vessel with inertia, all on the device (csrc/cascade.hpp; kernels
+    usv_cascade_refs, usv_cascade_step): the guidance layer - `front_end`, a device-resident GuidanceFrontEnd after reset() and set_world() -
+    publishes a desired heading and speed every `ratio`-th tick (nmpc_guidance_ca1.cpp, 20 Hz); `low_level`, a BatchOcpSolver of
+    usv_model_low_level with as many instances (nmpc_low_level.cpp, 100 Hz), turns them into thrusts at every tick; a 3-DOF vessel
+    (nedx, nedy, psi, u, v, r) integrates the published thrusts over the low-level shooting interval in num_steps RK4 steps, starboard
+    factor c.  ratio * low_level.dt must be the guidance solver's dt.
+
+        tick()   every ratio-th tick first  prepare() -> solve_async() -> publish(fetch=False)  of the guidance layer,
+                 then                       refs -> low_level.solve_async() -> step
+    No host array and no synchronisation in a tick.  Neither solver's advance is called: the closed-loop log and the tracked cost hang on
+    advance and do not see cascade ticks."""
+
+    def __init__(self, front_end, low_level, ratio=5, num_steps=1, c=0.78, instance_offset=0):
+        import torch
+        if not isinstance(front_end, GuidanceFrontEnd) or getattr(front_end.s, "generated", False):
+            raise Exception("Cascade: the upper layer is a GuidanceFrontEnd on a usv_model_guidance_ca1 solver of the stock library")
+        if low_level.ocp.model.name != "usv_model_low_level" or (low_level.nx, low_level.nu) != (8, 2):
+            raise Exception("Cascade: the lower layer is a solver of usv_model_low_level (this one's model: %s)" % low_level.ocp.model.name)
+        if low_level.B != front_end.B:
+            raise Exception("Cascade: the two layers need the same batch (guidance %d, low level %d)" % (front_end.B, low_level.B))
+        self.fe, self.g, self.ll = front_end, front_end.s, low_level
+        self.B, self.ratio = front_end.B, int(ratio)
+        self._lib = self.g._lib
+        # one stream for both solvers: the kernels of the two libraries are ordered by it and by nothing else
+        self._stream = torch.cuda.Stream(device=self.g._desc.device)
+        self.g.set_stream(self._stream.cuda_stream)
+        self.ll.set_stream(self._stream.cuda_stream)
+        # the low-level solver's yref and x0 are written behind its back, through device pointers, by a kernel of another library: every
+        # solve must linearise afresh from device memory ("pipeline_linearize" 0: no pass made a tick ahead on the old rows), and no host copy
+        # of its arrays may stand in for the device's ("host_mirror" 0: no deferred upload lands on top of what the cascade wrote, no
+        # read-back per solve)
+        self.ll.set_option("pipeline_linearize", 0)
+        self.ll.set_option("host_mirror", 0)
+        h = C.c_void_p()
+        rc = self._lib.usvmpc_cascade_create(self.g._h, self.ratio, float(self.ll.dt), int(num_steps), float(c), int(instance_offset), self.ll.B,
+                                             self.ll.N, *(C.c_void_p(self.ll.device_ptr(f)) for f in ("x0", "x", "yref", "yref_e")), C.byref(h))
+        if rc != 0:
+            raise Exception(self._lib.usvmpc_cascade_last_error(None).decode())
+        self._c = h
+        self._t = 0
+
+    def _check(self, rc):
+        if rc < 0:
+            raise Exception(self._lib.usvmpc_cascade_last_error(self._c).decode())
+        return rc
+
+    def reset(self, pose, vel):
+        """pose [B,3] = (nedx, nedy, psi), vel [B,3] = (u, v, r): the vessel's state.  Past thrusts 0, tick 0, sums 0; the guidance solver's
+        x0 gets (u, v) and the pose; the low-level initial iterate becomes x_k = x0 for every k, u = 0."""
+        from . import scenario
+        p, v = _as_rows(pose, self.B, "pose"), _as_rows(vel, self.B, "vel")
+        self._check(self._lib.usvmpc_cascade_reset(self._c, p.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp)))
+        x0, _ = scenario.cascade_ll_inputs(np.column_stack([p, v]), np.zeros((self.B, 2)), np.zeros(self.B), np.zeros(self.B))
+        self.ll.set("x0", 0, x0)
+        self.ll.set_all("x", np.tile(x0[:, None, :], (1, self.ll.N + 1, 1)))
+        self.ll.set_all("u", np.zeros((self.B, self.ll.N, 2)))
+        self._t = 0
+
+    def guidance_tick(self):
+        """whether the next tick() begins with a guidance solve"""
+        return self._t % self.ratio == 0
+
+    def guidance(self):
+        """the guidance layer's part of a tick (enqueued)"""
+        self.fe.prepare()
+        self.g.solve_async()
+        self.fe.publish(fetch=False)
+
+    def refs(self):
+        """kernel usv_cascade_refs (enqueued): the low-level solver's x0 and, where the set-points changed, its reference rows"""
+        self._check(self._lib.usvmpc_cascade_refs(self._c))
+
+    def step(self, sigma=0.0, seed=0):
+        """kernel usv_cascade_step (enqueued): thrusts from the low-level x_1, one plant period (+ sigma N(0,1) on u, v, r), the hand-over"""
+        self._check(self._lib.usvmpc_cascade_step(self._c, float(sigma), int(seed)))
+        self._t += 1
+
+    def tick(self, sigma=0.0, seed=0):
+        """One low-level tick; enqueues and returns."""
+        if self.guidance_tick():
+            self.guidance()
+        self.refs()
+        self.ll.solve_async()
+        self.step(sigma, seed)
+
+    def state(self):
+        """dict(state [B,6] = (nedx, nedy, psi, u, v, r), thrust [B,2] (published), past_thrust [B,2], ticks [B], yref_writes,
+        err_sums [B,4] = (sum |e_u|, sum |e_psi|, sum e_u^2, sum e_psi^2)); waits for the stream."""
+        s, th, pa, es = np.zeros((self.B, 6)), np.zeros((self.B, 2)), np.zeros((self.B, 2)), np.zeros((self.B, 4))
+        tk = np.zeros(self.B, dtype=np.int32)
+        n = C.c_longlong(0)
+        self._check(self._lib.usvmpc_cascade_state(self._c, s.ctypes.data_as(_capi._dp), th.ctypes.data_as(_capi._dp), pa.ctypes.data_as(_capi._dp),
+                                                   tk.ctypes.data_as(_capi._ip), C.byref(n), es.ctypes.data_as(_capi._dp)))
+        return dict(state=s, thrust=th, past_thrust=pa, ticks=tk, yref_writes=int(n.value), err_sums=es)
+
+    def close(self):
+        """before either solver is closed"""
+        if self._c is not None:
+            self._lib.usvmpc_cascade_destroy(self._c)
+            self._c = None

@@ -533,3 +533,84 @@ def make_ca_encounters(scenes, S, seed=0, kind="parallel"):
     x0 = np.zeros((B, 8))
     x0[:, 0:2], x0[:, 5:8] = vel, pose
     return dict(waypoints=wp, pose=pose, vel=vel, x0=x0, world=np.zeros((B, 0, 3)))
+
+
+# ---- the two-layer control stack (guidance.Cascade; csrc/cascade.hpp): guidance layer -> low-level NMPC (usv_model_low_level) -> vessel.
+# The numpy restatement of the coupling arithmetic, what the device's kernels usv_cascade_refs / usv_cascade_step are held against.
+CASCADE_C = 0.78          # the starboard thruster's factor of usv_model_low_level
+CASCADE_LL_OCP = dict(N=100, dt=0.01, ratio=5, num_steps=1)   # the reference's deployment: low level at 100 Hz, guidance at 20 Hz
+
+
+def _dof3(c, u, v, r, Tp, Ts):
+    """(udot, vdot, rdot) of the 3-DOF block (usv_models._dof3_sym in numpy), vectorised"""
+    m, Iz, Bw = 30.0, 4.1, 0.41
+    Xud, Yvd, Yrd, Nvd, Nrd = -2.25, -23.13, -1.31, -16.41, -2.79
+    Yvv, Yvr, Nrv, Nrr = -99.99, -5.49, -8.8, -3.49
+    fast = u > 1.25
+    Xu, Xuu = np.where(fast, 64.55, -25.0), np.where(fast, -70.92, 0.0)
+    au, av, ar = np.abs(u), np.abs(v), np.abs(r)
+    Nr = -0.52 * np.sqrt(u * u + v * v)
+    a = Yrd + Nvd
+    fu = ((Tp + c * Ts) - (-m + 2.0 * Yvd) * v - a * r * r - (-Xu * u - Xuu * au * u)) / (m - Xud)
+    fv = (-(m - Xud) * u * r - (-_CY * av - Yvv * av - Yvr * ar) * v) / (m - Yvd)
+    fr = ((Tp - c * Ts) * (Bw / 2.0) - (-2.0 * Yvd * u * v - a * r * u + Xud * u * r) - (-Nr * r - Nrv * av * r - Nrr * ar * r)) / (Iz - Nrd)
+    return fu, fv, fr
+
+
+def _cascade_rhs(s, thr, c):
+    psi, u, v, r = s[:, 2], s[:, 3], s[:, 4], s[:, 5]
+    sp, cp = np.sin(psi), np.cos(psi)
+    fu, fv, fr = _dof3(c, u, v, r, thr[:, 0], thr[:, 1])
+    return np.stack([u * cp - v * sp, u * sp + v * cp, r, fu, fv, fr], axis=1)
+
+
+def cascade_plant_step(s, thr, T, num_steps=1, c=CASCADE_C):
+    """One period T of the vessel s [B,6] = (nedx, nedy, psi, u, v, r) under the held thrusts thr [B,2] = (Tport, Tstbd): num_steps RK4
+    steps, summed in the device's order (k1 + 2 k2 + 2 k3, then + k4).  The device fuses its multiply-adds: agreement to 1e-12."""
+    s, thr = np.array(s, dtype=float).reshape(-1, 6), np.asarray(thr, dtype=float).reshape(-1, 2)
+    h = T / float(num_steps)
+    for _ in range(int(num_steps)):
+        k = _cascade_rhs(s, thr, c)
+        acc = k
+        k = _cascade_rhs(s + 0.5 * h * k, thr, c)
+        acc = acc + 2.0 * k
+        k = _cascade_rhs(s + 0.5 * h * k, thr, c)
+        acc = acc + 2.0 * k
+        k = _cascade_rhs(s + h * k, thr, c)
+        s = s + (h / 6.0) * (acc + k)
+    return s
+
+
+def cascade_ll_inputs(s, past, psi_des, u_des):
+    """The low-level node's input side (nmpc_low_level.cpp:177-245): vessel s [B,6], past thrusts [B,2], set-points [B] ->
+    (x0 [B,8] = (psi, sin psi, cos psi, u (0 -> 0.001), v, r, past thrusts), yref row [B,10] = (psi_des, sin, cos, u_des, 0 ..)); yref_e is
+    the row's first eight entries."""
+    s, past = np.asarray(s, dtype=float).reshape(-1, 6), np.asarray(past, dtype=float).reshape(-1, 2)
+    psi_des, u_des = np.asarray(psi_des, dtype=float).reshape(-1), np.asarray(u_des, dtype=float).reshape(-1)
+    psi = s[:, 2]
+    u = np.where(s[:, 3] == 0.0, 0.001, s[:, 3])
+    x0 = np.column_stack([psi, np.sin(psi), np.cos(psi), u, s[:, 4], s[:, 5], past[:, 0], past[:, 1]])
+    yref = np.zeros((len(psi_des), 10))
+    yref[:, 0], yref[:, 1], yref[:, 2], yref[:, 3] = psi_des, np.sin(psi_des), np.cos(psi_des), u_des
+    return x0, yref
+
+
+def cascade_ll_outputs(x1, psi_des, u_des, s):
+    """The low-level node's output side (:256-285) from stage 1 of its iterate x1 [B,8]: (published thrusts [B,2] - zero where u_des == 0 -,
+    past thrusts [B,2] = x1[6:8] regardless, e_u, e_psi [B] float32 against the state s the solve saw)."""
+    x1, s = np.asarray(x1, dtype=float).reshape(-1, 8), np.asarray(s, dtype=float).reshape(-1, 6)
+    psi_des, u_des = np.asarray(psi_des, dtype=float).reshape(-1), np.asarray(u_des, dtype=float).reshape(-1)
+    past = x1[:, 6:8].copy()
+    thr = np.where((u_des == 0.0)[:, None], 0.0, past)
+    u = np.where(s[:, 3] == 0.0, 0.001, s[:, 3])
+    return thr, past, (u_des - u).astype(np.float32), (psi_des - s[:, 2]).astype(np.float32)
+
+
+def cascade_guidance_tick(tick, ratio):
+    """Low-level tick `tick` (from 0) begins with a guidance solve"""
+    return tick % ratio == 0
+
+
+def cascade_hands_over(tick, ratio):
+    """... and the plant step of tick `tick` writes the vessel's state into the guidance layer's x0 when the NEXT tick is a guidance tick"""
+    return (tick + 1) % ratio == 0

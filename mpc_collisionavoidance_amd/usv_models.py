@@ -8,6 +8,10 @@ and each `acados_settings_*()` fills an AcadosOcp like the reference's `acados_s
     usv_guidance_ca1/usv_model.py:40-199    usv_guidance_ca1/acados_settings.py:40-209
     usv_pf_ca/usv_model.py:40-230           usv_pf_ca/acados_settings.py:40-190
 
+and a fourth one, the cascade's lower layer, which exists in its symbolic form only (no hand-written device model; guidance.Cascade):
+
+    usv_low_level/usv_model.py:61-165       usv_low_level/acados_settings.py:75-156
+
 CasADi is not needed: the dynamics are hand-written device functions selected by `model.name`
 (csrc/models.hpp), and the symbolic vectors are length-only placeholders.  Weights, selectors,
 bounds and soft-constraint data are plain numbers and are passed through unchanged, so a caller
@@ -299,11 +303,79 @@ def ocp_pf_ca(Tf, N, n_obstacles=4, symbolic=False):
     return constraint, model, ocp
 
 
-OCP_BUILDERS = {"usv_model": ocp_usv, "usv_model_guidance_ca1": ocp_guidance_ca1, "usv_model_pf_ca": ocp_pf_ca}
+# ------------------------------------------------------------------------------------------ low-level controller
+LOW_LEVEL_C = 0.78   # the starboard thruster's factor in this model (usv_low_level/usv_model.py; usv_model_pf_ca has 1.0)
+
+
+def usv_model_low_level():
+    """`usv_model_low_level`: the heading / speed controller below the guidance layer (usv_low_level/usv_model.py:61-165), 3-DOF dynamics
+    with the heading carried as (psi, sin psi, cos psi) and the thrusts as states driven by their rates.  No obstacles.  The model is
+    NOT in the registry of hand-written device models: it exists in its symbolic form only and its solver runs in a library generated
+    for it (codegen.py, genbuild.py), as any model file outside the three in-scope ones does."""
+    model = types.SimpleNamespace()
+    constraint = types.SimpleNamespace()
+    model.name = "usv_model_low_level"
+    psi, sinpsi, cospsi, u, v, r, Tport, Tstbd = (ca.MX.sym(n) for n in ("psi", "sinpsi", "cospsi", "u", "v", "r", "Tport", "Tstbd"))
+    U0, U1 = ca.MX.sym("UTportdot"), ca.MX.sym("UTstbddot")
+    fu, fv, fr = _dof3_sym(LOW_LEVEL_C, u, v, r, Tport, Tstbd)
+    model.x = ca.vertcat(psi, sinpsi, cospsi, u, v, r, Tport, Tstbd)
+    model.U, model.p, model.z = ca.vertcat(U0, U1), ca.vertcat([]), ca.vertcat([])
+    model.f_expl_expr = ca.vertcat(r, ca.cos(psi) * r, -ca.sin(psi) * r, fu, fv, fr, U0, U1 / LOW_LEVEL_C)
+    model.xdot = ca.MX.sym("xdot", 8)
+    model.f_impl_expr = model.xdot - model.f_expl_expr
+    model.u_min, model.u_max = -2.0, 2.0
+    model.Tport_min = model.Tstbd_min = -30
+    model.Tport_max = model.Tstbd_max = 35
+    model.r_min, model.r_max = -10.0, 10.0
+    model.Tstbddot_min = model.Tportdot_min = -30
+    model.Tstbddot_max = model.Tportdot_max = 30
+    model.x0 = np.array([0.0, 0.0, 1.0, 0.001, 0.0, 0.0, 0.0, 0.0])
+    constraint.expr = None
+    return model, constraint
+
+
+def ocp_low_level(Tf, N, symbolic=True):
+    """usv_low_level/acados_settings.py:75-156 (the reference: Tf = 1, N = 100).  Symbolic whatever `symbolic` says: there is no other form."""
+    model, constraint = usv_model_low_level()
+    ocp = _common(model, constraint, N, Tf)
+    nx, nu = 8, 2
+    ny = nx + nu
+    Q = np.diag([0, 0.1, 0.1, 0.1, 0, 0, 1e-7, 0])
+    R = np.zeros((nu, nu))
+    Qe = np.diag([0, 0.05, 0.05, 0.1, 0, 0, 1e-6, 0])
+    ocp.cost.W = scipy.linalg.block_diag(Q, R)
+    ocp.cost.W_e = Qe
+    Vx = np.zeros((ny, nx))
+    Vx[:nx, :nx] = np.eye(nx)
+    ocp.cost.Vx = Vx
+    Vu = np.zeros((ny, nu))
+    Vu[8, 0] = 1.0
+    Vu[9, 1] = 1.0
+    ocp.cost.Vu = Vu
+    ocp.cost.Vx_e = np.eye(nx)
+    ocp.cost.yref = np.zeros(ny)
+    ocp.cost.yref_e = np.zeros(nx)
+    ocp.constraints.lbx = np.array([model.u_min, model.u_min, model.r_min, model.Tport_min, model.Tstbd_min])
+    ocp.constraints.ubx = np.array([model.u_max, model.u_max, model.r_max, model.Tport_max, model.Tstbd_max])
+    ocp.constraints.idxbx = np.array([3, 4, 5, 6, 7])
+    ocp.constraints.lbu = np.array([model.Tportdot_min, model.Tstbddot_min])
+    ocp.constraints.ubu = np.array([model.Tportdot_max, model.Tstbddot_max])
+    ocp.constraints.idxbu = np.array([0, 1])
+    ocp.constraints.x0 = model.x0
+    return constraint, model, ocp
+
+
+OCP_BUILDERS = {"usv_model": ocp_usv, "usv_model_guidance_ca1": ocp_guidance_ca1, "usv_model_pf_ca": ocp_pf_ca,
+                "usv_model_low_level": ocp_low_level}
 
 
 def make_ocp(name, Tf, N, n_obstacles=None, symbolic=False):
-    """symbolic=True: attach the expression graphs and route the solver through the code generator."""
+    """symbolic=True: attach the expression graphs and route the solver through the code generator.  usv_model_low_level has no
+    obstacles and only a symbolic form."""
+    if name == "usv_model_low_level":
+        ocp = ocp_low_level(Tf, N)[2]
+        ocp.solver_options.model_source = "symbolic"
+        return ocp
     if name == "usv_model":
         ocp = ocp_usv(Tf, N, symbolic=symbolic)[2]
     elif n_obstacles is None:
@@ -319,6 +391,8 @@ def acados_settings(Tf, N, name="usv_model_guidance_ca1", n_obstacles=None, devi
     """`acados_settings(Tf, N)` of the reference: returns (constraint, model, acados_solver)."""
     if name == "usv_model":
         constraint, model, ocp = ocp_usv(Tf, N)
+    elif name == "usv_model_low_level":
+        constraint, model, ocp = ocp_low_level(Tf, N)
     elif n_obstacles is None:
         constraint, model, ocp = OCP_BUILDERS[name](Tf, N)
     else:
