@@ -516,6 +516,13 @@ int usvmpc_calibrate_traffic(usvmpc_handle *h, int nplanes, double *bytes_read, 
  * pos [n][2], p [n][2K] -> h [n][K], grad [n][K][2]. */
 int usvmpc_debug_model_eval(int model, int device, int n, const double *x, const double *u, double *f, double *J);
 int usvmpc_debug_obstacle_eval(int device, int n, int K, const double *pos, const double *p, double *h, double *grad);
+/* ... the same f and J as the kernels obtain them INSIDE a shooting interval: the model's per-interval preparation at x_start [n][nx]
+ * (ModelCall<M>::prepare), then the evaluation at x [n][nx] (ModelCall<M>::fjvp).  For usv_model_pf_ca this takes sin / cos(psi)
+ * from those at x_start by the series in d = x[0] - x_start[0] (or the library call beyond |d| > 0.125); models without a
+ * preparation give what usvmpc_debug_model_eval gives.  And the two fast-math primitives of the kernels on n operands:
+ * rcp[i] = lanes::frcp(x[i]), rsq[i] = lanes::frsqrt(x[i]) (hardware estimate + two Newton steps). */
+int usvmpc_debug_model_eval_from(int model, int device, int n, const double *x_start, const double *x, const double *u, double *f, double *J);
+int usvmpc_debug_fast_math(int device, int n, const double *x, double *rcp, double *rsq);
 /* ---- Integrator (acados_template.AcadosSimSolver): B instances of a model's explicit RK4 over one sampling period T, in num_steps
  * steps of T / num_steps, with the forward sensitivities when sens_forw != 0.  The same model functions and RK4 arithmetic as the
  * lineariser's (csrc/sim.hpp); x_next is the same bits with sens_forw on or off, and an instance's result does not depend on the batch.

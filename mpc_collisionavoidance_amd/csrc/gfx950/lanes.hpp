@@ -200,6 +200,9 @@ USV_DEV bool wave_any(bool p) { return __any((int)p) != 0; }
 // 1/x and 1/sqrt(x) from the hardware estimate + two Newton steps (full FP64 accuracy for the normal-range operands of the IPM;
 // ~10 instructions instead of the ~25 of an IEEE division).  The arithmetic of the shipped kernels is THIS, with no build-time
 // variant: the IEEE-division build of the parity experiment (profiles/r03_parity_tail.txt) is a patch, tools/experiments/exact_div.patch.
+// Measured against 40 digits on the MI355X (tests/test_gpu_model_edges.py, profiles/model_edges.txt): frcp within 0.5 ulp and frsqrt within 0.95 ulp
+// over 1e-300 .. 1e300, binade edges and exact squares included.  Outside the normal range they are NOT the IEEE operations: 0, inf and
+// subnormal operands of frcp, and 0 and inf of frsqrt, give NaN (the Newton step forms 0 * inf) where 1 / x and 1 / sqrt(x) give inf or 0.
 USV_DEV double frcp(double x)
 {
     double r = __builtin_amdgcn_rcp(x);

@@ -1151,6 +1151,37 @@ __global__ void usv_debug_model(int n, const double *x, const double *u, double 
     }
 }
 
+// ... and as the lineariser and the integrator call them INSIDE an interval: ModelCall<M>::prepare at the interval's start x_start, then
+// ModelCall<M>::fjvp at the point x.  For a model with a Pre (ModelM2) this evaluates what depends on the distance from the start -
+// sincos_near at d = x[0] - x_start[0] - which usv_debug_model, preparing at the point itself, never enters.
+template <class M>
+__global__ void usv_debug_model_from(int n, const double *x_start, const double *x, const double *u, double *f, double *J)
+{
+    constexpr int NX = M::NX, NU = M::NU, NZ = NX + NU;
+    using MC = ModelCall<M>;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * NZ) return;
+    const int pt = i / NZ, c = i - pt * NZ;
+    double x0[NX], xx[NX], uu[NU > 0 ? NU : 1], s[NX], su[NU > 0 ? NU : 1], ff[NX], js[NX];
+    for (int j = 0; j < NX; j++) { x0[j] = x_start[pt * NX + j]; xx[j] = x[pt * NX + j]; s[j] = (c == NU + j) ? 1.0 : 0.0; }
+    for (int j = 0; j < NU; j++) { uu[j] = u[pt * NU + j]; su[j] = (c == j) ? 1.0 : 0.0; }
+    const typename MC::Pre pre = MC::prepare(x0);
+    MC::fjvp(pre, xx, uu, s, su, ff, js);
+    for (int j = 0; j < NX; j++) {
+        J[((long)pt * NX + j) * NZ + c] = js[j];
+        if (c == 0) f[pt * NX + j] = ff[j];
+    }
+}
+
+// lanes::frcp and lanes::frsqrt on caller-supplied operands, one thread per operand
+__global__ void usv_debug_fast_math(int n, const double *x, double *rcp, double *rsq)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rcp[i] = lanes::frcp(x[i]);
+    rsq[i] = lanes::frsqrt(x[i]);
+}
+
 __global__ void usv_debug_obstacle(int n, int K, const double *pos, const double *p, double *h, double *grad)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2635,39 +2666,79 @@ int usvmpc_tick_ms(usvmpc_handle *h, int n, float *ms)
     return 0;
 }
 
-int usvmpc_debug_model_eval(int model, int device, int n, const double *x, const double *u, double *f, double *J)
+// x_start == nullptr: M::fjvp at x (usv_debug_model); otherwise ModelCall<M>::prepare(x_start), then ModelCall<M>::fjvp at x (usv_debug_model_from)
+static int debug_model_eval(int model, int device, int n, const double *x_start, const double *x, const double *u, double *f, double *J)
 {
     int nx, nu;
     if (model_dims(model, nx, nu) || n < 1 || !x || !f || !J || (nu > 0 && !u)) return USVMPC_E_ARG;
     if (hipSetDevice(device) != hipSuccess) return USVMPC_E_NODEVICE;
     const int nz = nx + nu;
-    double *dx = nullptr, *du = nullptr, *df = nullptr, *dJ = nullptr;
+    double *dx0 = nullptr, *dx = nullptr, *du = nullptr, *df = nullptr, *dJ = nullptr;
     int rc = 0;
     if (hipMalloc((void **)&dx, sizeof(double) * n * nx) != hipSuccess || hipMalloc((void **)&du, sizeof(double) * n * (nu ? nu : 1)) != hipSuccess ||
-        hipMalloc((void **)&df, sizeof(double) * n * nx) != hipSuccess || hipMalloc((void **)&dJ, sizeof(double) * n * nx * nz) != hipSuccess)
+        hipMalloc((void **)&df, sizeof(double) * n * nx) != hipSuccess || hipMalloc((void **)&dJ, sizeof(double) * n * nx * nz) != hipSuccess ||
+        (x_start && hipMalloc((void **)&dx0, sizeof(double) * n * nx) != hipSuccess))
         rc = USVMPC_E_HIP;
     if (!rc) {
         (void)hipMemcpy(dx, x, sizeof(double) * n * nx, hipMemcpyHostToDevice);
+        if (x_start) (void)hipMemcpy(dx0, x_start, sizeof(double) * n * nx, hipMemcpyHostToDevice);
         if (nu) (void)hipMemcpy(du, u, sizeof(double) * n * nu, hipMemcpyHostToDevice);
         const dim3 grid((unsigned)((n * nz + 63) / 64)), block(64);
+#define USV_DEBUG_LAUNCH(M) \
+    if (x_start) hipLaunchKernelGGL(usv_debug_model_from<M>, grid, block, 0, 0, n, dx0, dx, du, df, dJ); \
+    else hipLaunchKernelGGL(usv_debug_model<M>, grid, block, 0, 0, n, dx, du, df, dJ)
         switch (model) {
 #ifndef USV_GEN_ONLY
-        case USVMPC_MODEL_USV: hipLaunchKernelGGL(usv_debug_model<ModelM0>, grid, block, 0, 0, n, dx, du, df, dJ); break;
-        case USVMPC_MODEL_GUIDANCE_CA1: hipLaunchKernelGGL(usv_debug_model<ModelM1>, grid, block, 0, 0, n, dx, du, df, dJ); break;
-        case USVMPC_MODEL_PF_CA: hipLaunchKernelGGL(usv_debug_model<ModelM2>, grid, block, 0, 0, n, dx, du, df, dJ); break;
+        case USVMPC_MODEL_USV: USV_DEBUG_LAUNCH(ModelM0); break;
+        case USVMPC_MODEL_GUIDANCE_CA1: USV_DEBUG_LAUNCH(ModelM1); break;
+        case USVMPC_MODEL_PF_CA: USV_DEBUG_LAUNCH(ModelM2); break;
 #endif
 #ifdef USV_GEN_MODEL_HEADER
-        case USVMPC_MODEL_GENERATED: hipLaunchKernelGGL(usv_debug_model<ModelGen>, grid, block, 0, 0, n, dx, du, df, dJ); break;
+        case USVMPC_MODEL_GENERATED: USV_DEBUG_LAUNCH(ModelGen); break;
 #endif
         default: rc = USVMPC_E_ARG;
         }
+#undef USV_DEBUG_LAUNCH
         if (!rc && (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)) rc = USVMPC_E_HIP;
         if (!rc) {
             (void)hipMemcpy(f, df, sizeof(double) * n * nx, hipMemcpyDeviceToHost);
             (void)hipMemcpy(J, dJ, sizeof(double) * n * nx * nz, hipMemcpyDeviceToHost);
         }
     }
-    (void)hipFree(dx); (void)hipFree(du); (void)hipFree(df); (void)hipFree(dJ);
+    (void)hipFree(dx0); (void)hipFree(dx); (void)hipFree(du); (void)hipFree(df); (void)hipFree(dJ);
+    return rc;
+}
+
+int usvmpc_debug_model_eval(int model, int device, int n, const double *x, const double *u, double *f, double *J)
+{
+    return debug_model_eval(model, device, n, nullptr, x, u, f, J);
+}
+
+int usvmpc_debug_model_eval_from(int model, int device, int n, const double *x_start, const double *x, const double *u, double *f, double *J)
+{
+    if (!x_start) return USVMPC_E_ARG;
+    return debug_model_eval(model, device, n, x_start, x, u, f, J);
+}
+
+int usvmpc_debug_fast_math(int device, int n, const double *x, double *rcp, double *rsq)
+{
+    if (n < 1 || !x || !rcp || !rsq) return USVMPC_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return USVMPC_E_NODEVICE;
+    double *dx = nullptr, *drcp = nullptr, *drsq = nullptr;
+    int rc = 0;
+    if (hipMalloc((void **)&dx, sizeof(double) * n) != hipSuccess || hipMalloc((void **)&drcp, sizeof(double) * n) != hipSuccess ||
+        hipMalloc((void **)&drsq, sizeof(double) * n) != hipSuccess)
+        rc = USVMPC_E_HIP;
+    if (!rc) {
+        (void)hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice);
+        hipLaunchKernelGGL(usv_debug_fast_math, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, n, dx, drcp, drsq);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = USVMPC_E_HIP;
+        if (!rc) {
+            (void)hipMemcpy(rcp, drcp, sizeof(double) * n, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(rsq, drsq, sizeof(double) * n, hipMemcpyDeviceToHost);
+        }
+    }
+    (void)hipFree(dx); (void)hipFree(drcp); (void)hipFree(drsq);
     return rc;
 }
 

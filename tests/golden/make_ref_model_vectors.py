@@ -5,8 +5,10 @@ the three in-scope model files - catkin_ws/src/nmpc_ca/scripts/{usv_acados,usv_g
 is executed unchanged (its `from casadi import *` resolved to mpc_collisionavoidance_amd.casadi_lite), and its
 expression graphs are evaluated at seeded points:
     f      the explicit right-hand side model.f_expl_expr, by direct evaluation of the reference's graph;
-    J      d f / d [u; x], by SYMPY differentiation of that graph (independent of this repo's forward-mode generator);
-    h, dh  the obstacle rows constraint.expr (con_h_expr) and their derivative with respect to x, likewise.
+    J      d f / d [u; x], by SYMPY differentiation of that graph (independent of this repo's forward-mode generator), evaluated
+           with mpmath at 40 digits and rounded to double;
+    h, dh  the obstacle rows constraint.expr (con_h_expr) and their sympy derivative with respect to x, evaluated in double (no
+           cancellation there: they agree with 40 digits to 4e-16).
 The vectors are data (inputs and expected outputs); no reference source text is stored.  A `-m gpu` test
 (tests/test_gpu_ref_vectors.py) compares the device transcription (csrc/models.hpp, obs_dist in csrc/qp_ipm.hpp) with
 them through usvmpc_debug_model_eval / usvmpc_debug_obstacle_eval, and a CPU test does the same for the oracle.
@@ -19,6 +21,7 @@ import importlib.util
 import os
 import sys
 
+import mpmath
 import numpy as np
 import sympy as sp
 
@@ -71,14 +74,17 @@ def main():
         xs, us, ps = sp.symbols("x0:%d" % nx, real=True), sp.symbols("u0:%d" % nu, real=True), sp.symbols("p0:%d" % max(npar, 1), real=True)
         symmap = {**dict(zip(X, xs)), **dict(zip(U, us)), **dict(zip(P, ps))}
         fs = sp.Matrix(_to_sympy(F, symmap))
-        Jf = sp.lambdify((xs, us), fs.jacobian(sp.Matrix(list(us) + list(xs))), "numpy")
+        # the derivative holds sums of cancelling terms (d fr / d u, d ye' / d v): evaluated in double, single entries come out wrong in
+        # the 13th digit (found by tests/test_model_edges.py), so it is evaluated at 40 digits and rounded once
+        Jf = sp.lambdify((xs, us), fs.jacobian(sp.Matrix(list(us) + list(xs))).tolist(), "mpmath")
         rng = np.random.default_rng(20260929 + mid)
         x, u = points(variant, nx, nu, rng)
         f = np.zeros((NPTS, nx)); J = np.zeros((NPTS, nx, nu + nx))
         for i in range(NPTS):
             vals = {**dict(zip(X, x[i])), **dict(zip(U, u[i]))}
             f[i] = ca.evaluate(F, vals)
-            J[i] = np.asarray(Jf(x[i], u[i]), dtype=float)
+            with mpmath.workdps(40):
+                J[i] = np.array(Jf([mpmath.mpf(float(v)) for v in x[i]], [mpmath.mpf(float(v)) for v in u[i]]), dtype=object).astype(float)
         out = dict(model_id=mid, x=x, u=u, f=f, J=J, K=K)
         if K:
             hs = sp.Matrix(_to_sympy(H, symmap))

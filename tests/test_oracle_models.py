@@ -7,6 +7,8 @@ import pytest
 import sympy as sp
 from scipy.integrate import solve_ivp
 
+from tests.model_ref import _dof3_sym, _sym_model  # noqa: F401
+
 
 # ---- known answers derived by hand from the reference's formulas
 def test_known_answers_3dof(oracle):
@@ -34,51 +36,7 @@ def test_known_answers_guidance_ca1(oracle):
                             3.016064999001967, 0.408472761611062], rtol=1e-12)
 
 
-# ---- sympy restatement of the reference's CasADi expressions
-def _dof3_sym(c, u, v, r, Tp, Ts):
-    m, Iz, B = 30, sp.Rational(41, 10), sp.Rational(41, 100)
-    Xud, Yvd, Yrd, Nvd, Nrd = -2.25, -23.13, -1.31, -16.41, -2.79
-    Yvv, Yvr, Nrv, Nrr = -99.99, -5.49, -8.8, -3.49
-    Xu = sp.Piecewise((64.55, u > 1.25), (-25, True))
-    Xuu = sp.Piecewise((-70.92, u > 1.25), (0, True))
-    Yv = 0.5 * (-40 * 1000 * sp.Abs(v)) * (1.1 + 0.0045 * (1.01 / 0.09) - 0.1 * (0.27 / 0.09) + 0.016 * ((0.27 / 0.09) ** 2))
-    Nr = (-0.52) * sp.sqrt(u * u + v * v)
-    Tu = Tp + c * Ts
-    Tr = (Tp - c * Ts) * B / 2
-    fu = (Tu - (-m + 2 * Yvd) * v - (Yrd + Nvd) * r * r - (-Xu * u - Xuu * sp.Abs(u) * u)) / (m - Xud)
-    fv = (-(m - Xud) * u * r - (-Yv - Yvv * sp.Abs(v) - Yvr * sp.Abs(r)) * v) / (m - Yvd)
-    fr = (Tr - (-2 * Yvd * u * v - (Yrd + Nvd) * r * u + Xud * u * r) - (-Nr * r - Nrv * sp.Abs(v) * r - Nrr * sp.Abs(r) * r)) / (Iz - Nrd)
-    return fu, fv, fr
-
-
-def _sym_model(model):
-    if model == 0:
-        x = sp.symbols("u v r Tp Ts", real=True)
-        U = sp.symbols("U0 U1", real=True)
-        fu, fv, fr = _dof3_sym(0.78, *x)
-        f = [fu, fv, fr, U[0], U[1]]
-    elif model == 1:
-        x = sp.symbols("u v ye chie psied xned yned psi", real=True)
-        U = sp.symbols("U0,", real=True)
-        u, v, ye, chie, psied, xned, yned, psi = x
-        beta = sp.atan2(v, u + 0.001)
-        psie = chie - beta
-        f = [0, 0, u * sp.sin(psie) + v * sp.cos(psie), (psied - psie) / 1.0, U[0], u * sp.cos(psi) - v * sp.sin(psi),
-             u * sp.sin(psi) + v * sp.cos(psi), (psied - psie) / 1.0]
-    else:
-        x = sp.symbols("psi sinpsi cospsi u v r ye x1 y1 ak nedx nedy Tp Ts", real=True)
-        U = sp.symbols("U0 U1", real=True)
-        psi, sinpsi, cospsi, u, v, r, ye, x1, y1, ak, nedx, nedy, Tp, Ts = x
-        c = 1.0
-        fu, fv, fr = _dof3_sym(c, u, v, r, Tp, Ts)
-        chi = psi + sp.atan2(v, u + .001)
-        f = [r, sp.cos(chi) * r, -sp.sin(chi) * r, fu, fv, fr,
-             -(u * sp.cos(psi) - v * sp.sin(psi)) * sp.sin(ak) + (u * sp.sin(psi) + v * sp.cos(psi)) * sp.cos(ak),
-             0, 0, 0, u * sp.cos(psi) - v * sp.sin(psi), u * sp.sin(psi) + v * sp.cos(psi), U[0], U[1] / c]
-    f = sp.Matrix(f)
-    return x, U, f
-
-
+# ---- sympy restatement of the reference's CasADi expressions: tests/model_ref.py
 @pytest.mark.parametrize("model", [0, 1, 2])
 def test_jacobians_against_sympy(oracle, model):
     xs, Us, f = _sym_model(model)
