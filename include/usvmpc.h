@@ -620,6 +620,9 @@ int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr);
  *       While tracking runs every hand-over (usvmpc_advance, usvmpc_advance_sim) first enqueues usv_cost_track AHEAD of its own kernel (where
  *       the log's record goes):  sum[b] = sum[b] + c_0(x0[b], u[b][0], yref[b][0], sl[b][0], su[b][0]) - the stage function with z = [u_0; x0],
  *       the state the solve saw (after a status-4 solve x of stage 0 may be something else), in hand-over order.
+ *   usvmpc_cost_track_now: one step of the tracked sum outside a hand-over, for loops that never call usvmpc_advance (a cascade's two
+ *       solvers): uploads pending host writes, enqueues the same usv_cost_track and counts one.  USVMPC_E_ARG with a message while no tracking
+ *       runs.  Call it after the solve whose stage 0 it should cost and ahead of whatever overwrites x0.
  *   usvmpc_cost_tracked: sum [batch] (may be NULL) and the hand-overs counted; synchronises.  USVMPC_E_ARG with a message while no tracking
  *       runs.  usvmpc_get_device_ptr "cost_tracked" is the sum on the device (while tracking runs).
  * Neither kernel is a caller write: they read x, u, yref and write cost memory only, so the pipelined lineariser's pass made a tick ahead
@@ -628,6 +631,7 @@ int usvmpc_log_device_ptr(usvmpc_handle *h, const char *channel, void **dptr);
  * USVMPC_E_ARG, "cost: not built for soft state bounds".  No option and no channel of the log. */
 int usvmpc_eval_cost(usvmpc_handle *h);
 int usvmpc_cost_track(usvmpc_handle *h, int on);
+int usvmpc_cost_track_now(usvmpc_handle *h);
 int usvmpc_cost_tracked(usvmpc_handle *h, double *sum, long long *count);
 /* ---- Cascade: the two-layer control stack the reference deploys, closed on a vessel with inertia.  The guidance layer (a
  * usv_model_guidance_ca1 handle of THIS library with its device-resident front end) runs every `ratio`-th tick and publishes a desired
@@ -639,14 +643,17 @@ int usvmpc_cost_tracked(usvmpc_handle *h, double *sum, long long *count);
  * behind its back: every solve must linearise afresh from device memory).  One low-level tick t = 0, 1, ..:
  *     [t % ratio == 0:  usvmpc_guidance_prepare(h, NULL ..) -> usvmpc_solve_async(h) -> usvmpc_guidance_publish(h, NULL ..)]
  *     usvmpc_cascade_refs -> low-level usvmpc_solve_async -> usvmpc_cascade_step
- * No usvmpc_advance of either solver: the closed-loop log and the tracked cost hang on the hand-overs and do not see cascade ticks.
+ * No usvmpc_advance of either solver: the handles' closed-loop logs hang on the hand-overs and do not see cascade ticks.  A cascade's runs are
+ * recorded by its own log ("Cascade log" below) and costed by usvmpc_cost_track_now on either solver: the guidance handle's right after its
+ * usvmpc_solve_async, the low-level solver's right after its usvmpc_solve_async and ahead of usvmpc_cascade_step.
  *   create   USVMPC_E_ARG with a message (usvmpc_cascade_last_error(NULL)), nothing made: another guidance model; no usvmpc_guidance_reset
  *            or no world list yet; ratio < 1, num_steps < 1, T <= 0; T or c not finite; ratio * T different from the guidance handle's
  *            shooting interval; a null device pointer; ll_batch different from the guidance handle's batch; yref / yref_e not 16-byte
  *            aligned.  The object owns its device buffers; the guidance handle allocates nothing and launches what it launched before.
  *   reset    pose [batch][3] = (nedx, nedy, psi), vel [batch][3] = (u, v, r): the vessel's state; published and past thrusts 0, tick 0, error
  *            sums 0, yref_writes 0, every instance's reference rows due at the first refs.  Writes the guidance handle's x0[0, 1, 5, 6, 7] =
- *            (u, v, nedx, nedy, psi).  Synchronises.  The low-level initial iterate is the caller's business.
+ *            (u, v, nedx, nedy, psi).  Synchronises.  The low-level initial iterate is the caller's business.  Refused while a log runs
+ *            ("usvmpc_cascade_log_stop first").
  *   refs     kernel usv_cascade_refs, enqueued: low-level x0 = (psi, sin psi, cos psi, u (0 -> 0.001), v, r, past thrusts); yref rows
  *            (psi_des, sin, cos, u_des, 0 ..) x ll_N and yref_e rewritten for the instances whose (heading, speed) bits differ from what was
  *            last written - yref_writes counts them.
@@ -668,6 +675,49 @@ int usvmpc_cascade_step(usvmpc_cascade *c, double sigma, unsigned long long seed
 int usvmpc_cascade_state(usvmpc_cascade *c, double *state, double *thrust, double *past_thrust, int *ticks, long long *yref_writes,
                          double *err_sums);
 const char *usvmpc_cascade_last_error(usvmpc_cascade *c);
+/* ---- Cascade log: the trajectory a cascade leaves behind (the reference's simX[i], simU[i] and status, of the stack it deploys), kept on the
+ * device so that a tick stays free of host arrays and synchronisation (the schedule and layout: csrc/cascade_log_plan.hpp; the kernel:
+ * usv_cascade_record).  Low-level ticks are counted from 0 since usvmpc_cascade_log_start.  While a log runs, usvmpc_cascade_step of a tick that
+ * records first enqueues usv_cascade_record on the shared stream, AHEAD of usv_cascade_step; a cascade without a log launches exactly what
+ * it did before.
+ *   A RECORD is made at tick i when i >= first, (i - first) % every == 0 and fewer than `capacity` records exist; with the buffer full
+ *   `missed` counts it and nothing is stored (no ring).  Its channels, tick-major:
+ *     "state"  [capacity][batch][nsel] FP64   the selected entries of (nedx, nedy, psi, u, v, r) as the tick's low-level solve saw them,
+ *                                             before the plant period
+ *     "thrust" [capacity][batch][2]    FP64   the thrusts the tick publishes: what usv_cascade_step is about to write, 0 while u_des == 0
+ *     "ref"    [capacity][batch][2]    FP64   the (heading, speed) the low level tracks at the tick: the guidance layer's last published pair
+ *     "err"    [capacity][batch][2]    FP32   (e_u, e_psi) of the tick: the values usv_cascade_step feeds into its sums
+ *     "status" [capacity][batch]       int32  low-level status in bits 0-7 and qp_iter in bits 8-15, guidance status in bits 16-23 and
+ *                                             qp_iter in bits 24-30, both of the guidance layer's most recent solve
+ *   Thrusts and errors are computed by the function usv_cascade_step calls, on the same values: the recorded bits are the published bits.
+ *   log_start : allocates the buffers through the guidance handle (usvmpc_device_bytes of it counts them), zeroes the counters.  ll_status
+ *               and ll_qp_iter are the low-level solver's device pointers (usvmpc_get_device_ptr of ITS library: "status", "qp_iter"), needed
+ *               only when record_status is set.  USVMPC_E_ARG with a message, nothing changed: a log already runs
+ *               ("usvmpc_cascade_log_stop first"); capacity < 1, every < 1, first < 0; a state_mask bit >= 6; a descriptor that records
+ *               nothing; sizes that overflow 64 bits; record_status with a null pointer.  A failed allocation: USVMPC_E_HIP, nothing changed.
+ *   log_stop  : frees the buffers (usvmpc_cascade_destroy does too).
+ *   log_info  : records made, ticks counted, ticks missed, states per record; any output may be NULL.
+ *   log_read  : channel -> out [nrec][nb][n], tick-major, for records rec0 .. rec0 + nrec - 1 and instances b0 .. b0 + nb - 1; n = nsel, 2, 2,
+ *               2 or 1; `bytes` must be exactly that size; records not made yet, instances outside the batch and a channel that is not
+ *               recorded are refused.  One 2-D copy; synchronises the stream.
+ *   log_device_ptr: the channel's buffer on the device.
+ * The record kernel reads the cascade's state, the low-level iterate and both solvers' status and writes log memory only.
+ * Not provided: a ring mode; error sums (usvmpc_cascade_state has the cascade's own); a cascade's ticks in the handles' own logs. */
+typedef struct usvmpc_cascade_log_desc {
+    int capacity;        /* records kept, >= 1 */
+    int every;           /* one record every `every`-th low-level tick, >= 1 */
+    int first;           /* first tick recorded, counted from 0 since usvmpc_cascade_log_start, >= 0 */
+    unsigned state_mask; /* bit j: entry j of (nedx, nedy, psi, u, v, r) is recorded (bits >= 6 refused); 0: no state channel */
+    int record_thrust;   /* 1: the two published thrusts */
+    int record_ref;      /* 1: the tracked (heading, speed) */
+    int record_err;      /* 1: (e_u, e_psi) as float32 */
+    int record_status;   /* 1: one int32 per instance, both layers' status and qp_iter */
+} usvmpc_cascade_log_desc;
+int usvmpc_cascade_log_start(usvmpc_cascade *c, const usvmpc_cascade_log_desc *d, const int *ll_status, const int *ll_qp_iter);
+int usvmpc_cascade_log_stop(usvmpc_cascade *c);
+int usvmpc_cascade_log_info(usvmpc_cascade *c, int *records, long long *ticks, long long *missed, int *nsel);
+int usvmpc_cascade_log_read(usvmpc_cascade *c, const char *channel, int rec0, int nrec, int b0, int nb, void *out, size_t bytes);
+int usvmpc_cascade_log_device_ptr(usvmpc_cascade *c, const char *channel, void **dptr);
 /* bytes of device memory held by the handle */
 size_t usvmpc_device_bytes(usvmpc_handle *h);
 const char *usvmpc_last_error(usvmpc_handle *h);

@@ -74,9 +74,11 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
            "usvmpc_guidance_mission_state", "usvmpc_guidance_fleet", "usvmpc_guidance_fleet_state",
            "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr",
-           "usvmpc_eval_cost", "usvmpc_cost_track", "usvmpc_cost_tracked",
+           "usvmpc_eval_cost", "usvmpc_cost_track", "usvmpc_cost_track_now", "usvmpc_cost_tracked",
            "usvmpc_cascade_create", "usvmpc_cascade_destroy", "usvmpc_cascade_reset", "usvmpc_cascade_refs", "usvmpc_cascade_step",
-           "usvmpc_cascade_state", "usvmpc_cascade_last_error"]
+           "usvmpc_cascade_state", "usvmpc_cascade_last_error",
+           "usvmpc_cascade_log_start", "usvmpc_cascade_log_stop", "usvmpc_cascade_log_info", "usvmpc_cascade_log_read",
+           "usvmpc_cascade_log_device_ptr"]
 
 
 class LogDesc(C.Structure):
@@ -84,6 +86,12 @@ class LogDesc(C.Structure):
     _fields_ = [("capacity", C.c_int), ("every", C.c_int), ("first", C.c_int), ("state_mask", C.c_uint),
                 ("record_u", C.c_int), ("record_status", C.c_int), ("n_err", C.c_int),
                 ("err_a", C.c_int * 4), ("err_b", C.c_int * 4), ("err_c", C.c_double * 4), ("err_first", C.c_int)]
+
+
+class CascadeLogDesc(C.Structure):
+    """usvmpc_cascade_log_desc"""
+    _fields_ = [("capacity", C.c_int), ("every", C.c_int), ("first", C.c_int), ("state_mask", C.c_uint),
+                ("record_thrust", C.c_int), ("record_ref", C.c_int), ("record_err", C.c_int), ("record_status", C.c_int)]
 
 
 _libs = {}
@@ -186,6 +194,7 @@ def load(path):
     L.usvmpc_eval_cost.argtypes = [C.c_void_p]
     L.usvmpc_cost_track.argtypes = [C.c_void_p, C.c_int]
     L.usvmpc_cost_tracked.argtypes = [C.c_void_p, _dp, _llp]
+    L.usvmpc_cost_track_now.argtypes = [C.c_void_p]
     if hasattr(L, "usvmpc_cascade_create"):
         L.usvmpc_cascade_create.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_longlong, C.c_int, C.c_int] + \
             [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
@@ -196,6 +205,11 @@ def load(path):
         L.usvmpc_cascade_state.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _llp, _dp]
         L.usvmpc_cascade_last_error.argtypes = [C.c_void_p]
         L.usvmpc_cascade_last_error.restype = C.c_char_p
+        L.usvmpc_cascade_log_start.argtypes = [C.c_void_p, C.POINTER(CascadeLogDesc), C.c_void_p, C.c_void_p]
+        L.usvmpc_cascade_log_stop.argtypes = [C.c_void_p]
+        L.usvmpc_cascade_log_info.argtypes = [C.c_void_p, _ip, _llp, _llp, _ip]
+        L.usvmpc_cascade_log_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        L.usvmpc_cascade_log_device_ptr.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
     L.usvmpc_device_bytes.argtypes = [C.c_void_p]
     L.usvmpc_device_bytes.restype = C.c_size_t
     L.usvmpc_last_error.argtypes = [C.c_void_p]

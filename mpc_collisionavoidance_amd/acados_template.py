@@ -562,6 +562,11 @@ class BatchOcpSolver:
         per-instance sum on the device.  on=True (again) zeroes sum and count; on=False stops and frees."""
         self._check(self._lib.usvmpc_cost_track(self._h, 1 if on else 0))
 
+    def track_cost_now(self):
+        """One step of the tracked sum outside a hand-over (enqueued): c_0 of the arrays as the device holds them now, counted as one.  For
+        loops that never call advance (guidance.Cascade); refused unless track_cost() is on."""
+        self._check(self._lib.usvmpc_cost_track_now(self._h))
+
     def tracked_cost(self):
         """(sum [B], count): the tracked sums and the hand-overs they hold (synchronises); device_ptr("cost_tracked") is the sum on the device."""
         s = np.zeros(self.B)

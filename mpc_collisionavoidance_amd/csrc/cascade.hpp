@@ -1,7 +1,7 @@
 // cascade.hpp — the coupling arithmetic of the two-layer control stack the reference deploys: the guidance NMPC (nmpc_guidance_ca1.cpp, 20 Hz)
 // publishes a desired heading and speed, the low-level NMPC (catkin_ws/src/nmpc_ca/src/nmpc_low_level.cpp, 100 Hz; OCP usv_model_low_level)
 // turns them into thruster commands, and a vessel with 3-DOF dynamics answers.  Per instance, as pure functions: host + device, no dependency
-// on the kernels (usvmpc.hip: usv_cascade_refs, usv_cascade_step; tests/cascade_harness.cpp).
+// on the kernels (usvmpc.hip: usv_cascade_refs, usv_cascade_step, usv_cascade_record; tests/cascade_harness.cpp).
 //     low-level inputs   velocityCallback :177-185, positionCallback :187-192, desired*Callback :194-204, control :206-245
 //     low-level outputs  control :256-285
 //     the vessel         state s = (nedx, nedy, psi, u, v, r), input the two published thrusts held over the period:
@@ -133,6 +133,20 @@ struct CascadePtrs {
     int *ticks;           // [B]
     double *sums;         // [B][4] sum |e_u|, sum |e_psi|, sum e_u^2, sum e_psi^2
     unsigned long long *yref_writes;
+};
+
+// ---- the arguments of usv_cascade_record (usvmpc.hip; the schedule and layout: cascade_log_plan.hpp).  Nothing in here is indexed at run
+// time - the selected states are a nibble list (closed_loop_log.hpp) - so that the kernel needs no scratch.
+struct CasLogRec {
+    const double *s, *last, *ll_x;     // CascadePtrs' s, last and ll_x
+    const int *ll_status, *ll_qp_iter; // [B] of the low-level solver (its library's device pointers); read only when r_status is set
+    const int *g_status, *g_qp_iter;   // [B] of the guidance handle
+    double *r_state, *r_thrust, *r_ref; // the record's slabs [B][nsel], [B][2], [B][2]; nullptr: channel not recorded
+    float *r_err;                      // [B][2]
+    int *r_status;                     // [B]
+    long B;
+    int ll_N, nsel;
+    unsigned long long sel;            // nibble list: the selected states, ascending
 };
 
 } // namespace usv

@@ -26,6 +26,7 @@
 
 #include "ca_fleet_world.hpp"
 #include "cascade.hpp"
+#include "cascade_log_plan.hpp"
 #include "closed_loop_log.hpp"
 #include "cost_eval.hpp"
 #include "fleet_world.hpp"
@@ -1121,6 +1122,34 @@ __global__ void __launch_bounds__(256) usv_cascade_step(CascadePtrs C, double *g
         double *x0 = gx0 + b * CA_NX;
         x0[0] = s[3]; x0[1] = s[4]; x0[5] = s[0]; x0[6] = s[1]; x0[7] = s[2];
     }
+}
+
+// usv_cascade_record: one launch per logged low-level tick (usvmpc_cascade_log_*; the schedule and layout: cascade_log_plan.hpp), enqueued
+// AHEAD of usv_cascade_step, so that C.s is still the state the tick's low-level solve saw and stage 1 of its iterate is final.  It reads
+// the cascade's state, the low-level iterate and both solvers' status and writes log memory only.  Shaped like usv_log_record: thread t
+// serves element t of each of the record's five slabs (five guards), so every store of a wave is one contiguous run; the selected states
+// travel as a nibble list in one 64-bit argument and nothing in the argument struct is indexed at run time (that kernel's scratch trap).
+// Thrusts and errors come from cas_ll_outputs on the very arguments usv_cascade_step hands it: the recorded bits are the published bits.
+__global__ void __launch_bounds__(256) usv_cascade_record(CasLogRec R)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (R.r_state && t < R.B * R.nsel) {
+        const long b = t / R.nsel;
+        const int j = (int)(t - b * R.nsel);
+        R.r_state[t] = R.s[b * CAS_NS + log_nibble(R.sel, j)];
+    }
+    if ((R.r_thrust || R.r_err) && t < 2 * R.B) {
+        const long b = t >> 1;
+        const bool second = (t & 1) != 0;
+        const double *x1 = R.ll_x + (b * (long)(R.ll_N + 1) + 1) * CAS_NX;
+        double thr[2], past[2];
+        float e_u, e_psi;
+        cas_ll_outputs(x1, R.last[2 * b], R.last[2 * b + 1], R.s[b * CAS_NS + 2], cas_fix_u(R.s[b * CAS_NS + 3]), thr, past, e_u, e_psi);
+        if (R.r_thrust) R.r_thrust[t] = second ? thr[1] : thr[0];
+        if (R.r_err) R.r_err[t] = second ? e_psi : e_u;
+    }
+    if (R.r_ref && t < 2 * R.B) R.r_ref[t] = R.last[t];
+    if (R.r_status && t < R.B) R.r_status[t] = cas_log_status_word(R.ll_status[t], R.ll_qp_iter[t], R.g_status[t], R.g_qp_iter[t]);
 }
 
 // AcadosSimSolver's solve (usvmpc_sim_solve): x, u -> x_next (and S_forw = [Sx | Su] when SENS), sim.hpp
@@ -3048,6 +3077,19 @@ int usvmpc_cost_tracked(usvmpc_handle *h, double *sum, long long *count)
     return 0;
 }
 
+// one step of the tracked sum outside a hand-over: for loops that never call usvmpc_advance (a cascade's two solvers)
+int usvmpc_cost_track_now(usvmpc_handle *h)
+{
+    if (!h) return USVMPC_E_ARG;
+    if (!h->d_cost_sum) { h->err = "cost_track_now: no tracking is running (usvmpc_cost_track)"; return USVMPC_E_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        const int rcf = mirror_flush(h);
+        if (rcf) return rcf;
+    }
+    return cost_handover(h);
+}
+
 int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
 {
     if (!h) return USVMPC_E_ARG;
@@ -4072,8 +4114,9 @@ int usvmpc_calibrate_traffic(usvmpc_handle *h, int nplanes, double *bytes_read, 
 }
 
 // ---- the two-layer control stack (include/usvmpc.h, "Cascade"): kernels usv_cascade_refs / usv_cascade_step above, arithmetic cascade.hpp.
-// The object owns its buffers (plain hipMalloc: the guidance handle's allocation table and usvmpc_device_bytes are untouched) and works on
-// the guidance handle's stream as it is at each call; the low-level solver is a set of device pointers into another library's handle.
+// The object owns its buffers (plain hipMalloc: the guidance handle's allocation table and usvmpc_device_bytes are untouched; the log's
+// buffers alone come from the guidance handle's dev_alloc, so that usvmpc_device_bytes counts them) and works on the guidance handle's
+// stream as it is at each call; the low-level solver is a set of device pointers into another library's handle.
 struct usvmpc_cascade {
     usvmpc_handle *g;
     int ratio, num_steps;
@@ -4083,6 +4126,12 @@ struct usvmpc_cascade {
     bool ready;       // usvmpc_cascade_reset has run
     CascadePtrs p;
     double *d_pose, *d_vel; // [B][3] each: staging of usvmpc_cascade_reset
+    // The log (usvmpc_cascade_log_*): which tick records, the counters and the layout are cascade_log_plan.hpp's - CasLogPlan, host-only and
+    // checked on the CPU by tests/test_cascade_log_plan.py; no field of it is assigned in this file.  Here: the buffers its layout sizes, from
+    // the guidance handle's dev_alloc (nullptr: channel not recorded), and the kernel arguments that do not change from tick to tick.
+    CasLogPlan log;
+    void *log_buf[CAS_LOG_CHANNELS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    CasLogRec log_rec = {};
     std::string err;
 };
 thread_local std::string g_cascade_create_err;
@@ -4101,6 +4150,37 @@ static void cascade_free(usvmpc_cascade *c)
     CascadePtrs &p = c->p;
     (void)hipFree(p.s); (void)hipFree(p.thr); (void)hipFree(p.past); (void)hipFree(p.last); (void)hipFree(p.ticks); (void)hipFree(p.sums);
     (void)hipFree(p.yref_writes); (void)hipFree(c->d_pose); (void)hipFree(c->d_vel);
+}
+
+// ---- the cascade's log: cascade_log_plan.hpp says what a tick does and what a read copies; here: the buffers, the launch, the copies
+static void cascade_log_release(usvmpc_cascade *c)
+{
+    const CasLogLayout &l = c->log.lay;
+    const long long have[CAS_LOG_CHANNELS] = {l.state_bytes, l.thrust_bytes, l.ref_bytes, l.err_bytes, l.status_bytes};
+    for (int i = 0; i < CAS_LOG_CHANNELS; i++) {
+        if (c->log_buf[i]) dev_free(c->g, c->log_buf[i], (size_t)have[i]);
+        c->log_buf[i] = nullptr;
+    }
+}
+
+// a low-level tick of a cascade whose log runs (usvmpc_cascade_step, ahead of usv_cascade_step)
+static int cascade_log_tick(usvmpc_cascade *c)
+{
+    const LogTick t = c->log.on_tick();
+    if (t.slot < 0) return 0;
+    usvmpc_handle *h = c->g;
+    const CasLogLayout &l = c->log.lay;
+    CasLogRec r = c->log_rec;
+    const long at = (long)t.slot * l.B;
+    long n = 0;
+    if (c->log_buf[CAS_LOG_STATE]) { r.r_state = (double *)c->log_buf[CAS_LOG_STATE] + at * l.nsel; n = std::max(n, (long)l.B * l.nsel); }
+    if (c->log_buf[CAS_LOG_THRUST]) { r.r_thrust = (double *)c->log_buf[CAS_LOG_THRUST] + at * 2; n = std::max(n, (long)l.B * 2); }
+    if (c->log_buf[CAS_LOG_REF]) { r.r_ref = (double *)c->log_buf[CAS_LOG_REF] + at * 2; n = std::max(n, (long)l.B * 2); }
+    if (c->log_buf[CAS_LOG_ERR]) { r.r_err = (float *)c->log_buf[CAS_LOG_ERR] + at * 2; n = std::max(n, (long)l.B * 2); }
+    if (c->log_buf[CAS_LOG_STATUS]) { r.r_status = (int *)c->log_buf[CAS_LOG_STATUS] + at; n = std::max(n, (long)l.B); }
+    hipLaunchKernelGGL(usv_cascade_record, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r);
+    CAS_TRY(c, hipGetLastError());
+    return 0;
 }
 
 int usvmpc_cascade_create(usvmpc_handle *guidance, int ratio, double T, int num_steps, double c, long long instance_offset, int ll_batch,
@@ -4153,6 +4233,7 @@ int usvmpc_cascade_destroy(usvmpc_cascade *c)
     if (!c) return USVMPC_E_ARG;
     (void)hipSetDevice(c->g->device);
     (void)hipStreamSynchronize(c->g->stream);
+    if (c->log.on()) { cascade_log_release(c); c->log.stop(); }
     cascade_free(c);
     delete c;
     return 0;
@@ -4162,6 +4243,7 @@ int usvmpc_cascade_reset(usvmpc_cascade *c, const double *pose, const double *ve
 {
     if (!c) return USVMPC_E_ARG;
     if (!pose || !vel) { c->err = "cascade_reset: null pose or vel"; return USVMPC_E_ARG; }
+    if (c->log.on()) { c->err = "cascade_reset: a log is running (usvmpc_cascade_log_stop first)"; return USVMPC_E_ARG; }
     usvmpc_handle *h = c->g;
     const size_t B = (size_t)h->B;
     for (size_t i = 0; i < 3 * B; i++)
@@ -4199,6 +4281,10 @@ int usvmpc_cascade_step(usvmpc_cascade *c, double sigma, unsigned long long seed
     CAS_TRY(c, hipSetDevice(h->device));
     const bool hand_over = cas_hands_over(c->tick, c->ratio);
     if (hand_over && mirror_flush(h)) { c->err = "cascade_step: " + h->err; return USVMPC_E_HIP; }
+    if (c->log.on()) { // (ahead of the kernel that overwrites the vessel's state)
+        const int rcl = cascade_log_tick(c);
+        if (rcl) return rcl;
+    }
     hipLaunchKernelGGL(usv_cascade_step, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, c->p, const_cast<double *>(h->ptrs.x0),
                        h->B, c->T, c->num_steps, c->c, sigma, seed, c->offset, hand_over ? 1 : 0);
     CAS_TRY(c, hipGetLastError());
@@ -4225,6 +4311,99 @@ int usvmpc_cascade_state(usvmpc_cascade *c, double *state, double *thrust, doubl
     if (yref_writes) CAS_TRY(c, hipMemcpyAsync(yref_writes, c->p.yref_writes, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     if (err_sums) CAS_TRY(c, hipMemcpyAsync(err_sums, c->p.sums, B * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     CAS_TRY(c, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int usvmpc_cascade_log_start(usvmpc_cascade *c, const usvmpc_cascade_log_desc *d, const int *ll_status, const int *ll_qp_iter)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!d) { c->err = "cascade_log_start: null descriptor"; return USVMPC_E_ARG; }
+    if (c->log.on()) { c->err = "cascade_log_start: a log is running (usvmpc_cascade_log_stop first)"; return USVMPC_E_ARG; }
+    usvmpc_handle *h = c->g;
+    CasLogDesc ld = {};
+    ld.capacity = d->capacity; ld.every = d->every; ld.first = d->first; ld.state_mask = d->state_mask;
+    ld.record_thrust = d->record_thrust; ld.record_ref = d->record_ref; ld.record_err = d->record_err; ld.record_status = d->record_status;
+    CasLogLayout lay;
+    if (const char *why = check_cas_log_desc(ld, h->B, &lay)) { c->err = why; return USVMPC_E_ARG; }
+    if (lay.status_bytes && (!ll_status || !ll_qp_iter)) {
+        c->err = "cascade_log_start: the status channel needs the low-level solver's device pointers (status, qp_iter)";
+        return USVMPC_E_ARG;
+    }
+    CAS_TRY(c, hipSetDevice(h->device));
+    // all five buffers or none: a failed allocation leaves the cascade and the guidance handle's count as they were
+    const long long want[CAS_LOG_CHANNELS] = {lay.state_bytes, lay.thrust_bytes, lay.ref_bytes, lay.err_bytes, lay.status_bytes};
+    char *buf[CAS_LOG_CHANNELS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < CAS_LOG_CHANNELS; i++) {
+        if (want[i] == 0) continue;
+        if (dev_alloc(h, &buf[i], (size_t)want[i], false)) {
+            (void)hipGetLastError();
+            c->err = "cascade_log_start: allocation of " + std::to_string(want[i]) + " bytes: " + h->err;
+            for (int j = 0; j < i; j++) dev_free(h, buf[j], (size_t)want[j]);
+            return USVMPC_E_HIP;
+        }
+    }
+    for (int i = 0; i < CAS_LOG_CHANNELS; i++) c->log_buf[i] = buf[i];
+    c->log.start(ld, lay);
+    CasLogRec r = {};
+    r.s = c->p.s; r.last = c->p.last; r.ll_x = c->p.ll_x;
+    r.ll_status = ll_status; r.ll_qp_iter = ll_qp_iter;
+    r.g_status = h->ptrs.status; r.g_qp_iter = h->ptrs.qp_iter;
+    r.B = h->B; r.ll_N = c->p.ll_N;
+    int nsel = 0;
+    r.sel = log_pack_mask(ld.state_mask, &nsel);
+    r.nsel = nsel;
+    c->log_rec = r;
+    return 0;
+}
+
+int usvmpc_cascade_log_stop(usvmpc_cascade *c)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!c->log.on()) { c->err = "cascade_log_stop: no log is running"; return USVMPC_E_ARG; }
+    CAS_TRY(c, hipSetDevice(c->g->device));
+    cascade_log_release(c);
+    c->log.stop();
+    return 0;
+}
+
+int usvmpc_cascade_log_info(usvmpc_cascade *c, int *records, long long *ticks, long long *missed, int *nsel)
+{
+    if (!c) return USVMPC_E_ARG;
+    if (!c->log.on()) { c->err = "cascade_log_info: no log is running (usvmpc_cascade_log_start)"; return USVMPC_E_ARG; }
+    if (records) *records = c->log.records();
+    if (ticks) *ticks = c->log.ticks();
+    if (missed) *missed = c->log.missed();
+    if (nsel) *nsel = c->log.lay.nsel;
+    return 0;
+}
+
+int usvmpc_cascade_log_read(usvmpc_cascade *c, const char *channel, int rec0, int nrec, int b0, int nb, void *out, size_t bytes)
+{
+    if (!c) return USVMPC_E_ARG;
+    CasLogCopy cp;
+    if (const char *why = c->log.read_desc(channel, rec0, nrec, b0, nb, &cp)) { c->err = why; return USVMPC_E_ARG; }
+    if (!out || (long long)bytes != cp.bytes()) {
+        c->err = "cascade_log_read: out must hold exactly " + std::to_string(cp.bytes()) + " bytes ([nrec][nb][" + std::to_string(cp.n) + "])";
+        return USVMPC_E_ARG;
+    }
+    usvmpc_handle *h = c->g;
+    const char *src = (const char *)c->log_buf[cp.channel];
+    CAS_TRY(c, hipSetDevice(h->device));
+    CAS_TRY(c, hipMemcpy2DAsync(out, (size_t)cp.width, src + cp.offset, (size_t)cp.pitch, (size_t)cp.width, (size_t)cp.rows, hipMemcpyDeviceToHost,
+                                h->stream));
+    CAS_TRY(c, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int usvmpc_cascade_log_device_ptr(usvmpc_cascade *c, const char *channel, void **dptr)
+{
+    if (!c || !dptr) return USVMPC_E_ARG;
+    if (!c->log.on()) { c->err = "cascade_log_device_ptr: no log is running (usvmpc_cascade_log_start)"; return USVMPC_E_ARG; }
+    const std::string s = channel ? channel : "";
+    void *p = s == "state" ? c->log_buf[CAS_LOG_STATE] : s == "thrust" ? c->log_buf[CAS_LOG_THRUST] : s == "ref" ? c->log_buf[CAS_LOG_REF]
+            : s == "err" ? c->log_buf[CAS_LOG_ERR] : s == "status" ? c->log_buf[CAS_LOG_STATUS] : nullptr;
+    if (!p) { c->err = "cascade_log_device_ptr: '" + s + "' is no channel of the running log"; return USVMPC_E_ARG; }
+    *dptr = p;
     return 0;
 }
 

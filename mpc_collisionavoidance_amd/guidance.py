@@ -324,8 +324,9 @@ class Cascade:
 
         tick()   every ratio-th tick first  prepare() -> solve_async() -> publish(fetch=False)  of the guidance layer,
                  then                       refs -> low_level.solve_async() -> step
-    No host array and no synchronisation in a tick.  Neither solver's advance is called: the closed-loop log and the tracked cost hang on
-    advance and do not see cascade ticks."""
+    No host array and no synchronisation in a tick.  Neither solver's advance is called, so the solvers' own closed-loop logs do not see
+    cascade ticks: a cascade's runs are recorded by its own log - start_log() / read_log(), kernel usv_cascade_record ahead of every logged
+    step - and costed by track_cost() / tracked_cost(), the realised cost of either layer, both on the device and without synchronising."""
 
     def __init__(self, front_end, low_level, ratio=5, num_steps=1, c=0.78, instance_offset=0):
         import torch
@@ -355,6 +356,8 @@ class Cascade:
             raise Exception(self._lib.usvmpc_cascade_last_error(None).decode())
         self._c = h
         self._t = 0
+        self._log = None
+        self._track = False
 
     def _check(self, rc):
         if rc < 0:
@@ -381,6 +384,8 @@ class Cascade:
         """the guidance layer's part of a tick (enqueued)"""
         self.fe.prepare()
         self.g.solve_async()
+        if self._track:
+            self.g.track_cost_now()
         self.fe.publish(fetch=False)
 
     def refs(self):
@@ -398,6 +403,8 @@ class Cascade:
             self.guidance()
         self.refs()
         self.ll.solve_async()
+        if self._track:
+            self.ll.track_cost_now()
         self.step(sigma, seed)
 
     def state(self):
@@ -410,8 +417,87 @@ class Cascade:
                                                    tk.ctypes.data_as(_capi._ip), C.byref(n), es.ctypes.data_as(_capi._dp)))
         return dict(state=s, thrust=th, past_thrust=pa, ticks=tk, yref_writes=int(n.value), err_sums=es)
 
+    # -- the log (include/usvmpc.h, "Cascade log"): states, thrusts, set-points, errors and both layers' status kept on the device
+    STATES = ("nedx", "nedy", "psi", "u", "v", "r")
+
+    def start_log(self, capacity, every=1, first=0, states=None, thrust=True, ref=True, err=False, status=True):
+        """From now on every step (a low-level tick, counted from 0) first records, on the device and without synchronising: tick i makes a
+        record when i >= first, (i - first) % every == 0 and fewer than `capacity` exist.  states: None (all six) or a list of indices into
+        (nedx, nedy, psi, u, v, r) (stored in ascending order; an empty list: no state channel) - the vessel's state as the tick's low-level
+        solve saw it; thrust: the two thrusts the tick publishes; ref: the (heading, speed) the low level tracks; err: (e_u, e_psi) as
+        float32; status: status and qp_iter of both layers' last solves."""
+        d = _capi.CascadeLogDesc()
+        d.capacity, d.every, d.first = int(capacity), int(every), int(first)
+        sel = list(range(6)) if states is None else sorted(set(int(j) for j in states))
+        if any(j < 0 or j >= 32 for j in sel):
+            raise Exception("start_log: states must be indices of the vessel's state (nedx, nedy, psi, u, v, r)")
+        d.state_mask = sum(1 << j for j in sel)
+        d.record_thrust, d.record_ref, d.record_err, d.record_status = (int(bool(v)) for v in (thrust, ref, err, status))
+        ptrs = [C.c_void_p(self.ll.device_ptr(f)) for f in ("status", "qp_iter")] if status else [None, None]
+        self._check(self._lib.usvmpc_cascade_log_start(self._c, C.byref(d), *ptrs))
+        self._log = dict(states=sel, first=d.first, every=d.every, thrust=bool(thrust), ref=bool(ref), err=bool(err), status=bool(status))
+
+    def log_info(self):
+        """dict: records made, ticks counted since start_log, missed (due for a record when the buffer was full), nsel."""
+        r, n = C.c_int(), C.c_int()
+        tk, mi = C.c_longlong(), C.c_longlong()
+        self._check(self._lib.usvmpc_cascade_log_info(self._c, C.byref(r), C.byref(tk), C.byref(mi), C.byref(n)))
+        return dict(records=r.value, ticks=tk.value, missed=mi.value, nsel=n.value)
+
+    def read_log(self, records=None, instances=None):
+        """The log so far (synchronises).  records / instances: None (all made so far / the batch) or a half-open (start, stop) pair or range.
+        dict: state [nb][nrec][nsel], thrust, ref [nb][nrec][2] (float64), err [nb][nrec][2] (float32) - instance-major views of the
+        tick-major copy -, ll_status, ll_qp_iter, g_status, g_qp_iter [nb][nrec] (the status word, unpacked), tick [nrec] (the tick of each
+        record), states (the indices of state's last axis).  Channels not recorded are absent."""
+        made = self.log_info()["records"]    # (raises when no log runs)
+        lg = self._log
+        rng = self.ll._log_range
+        r0, nr = rng(records, made, "records")
+        b0, nb = rng(instances, self.B, "instances")
+        out = dict(tick=lg["first"] + lg["every"] * np.arange(r0, r0 + nr), states=list(lg["states"]))
+        chans = [("state", len(lg["states"]), np.float64)] if lg["states"] else []
+        chans += [(name, 2, dt) for name, dt in (("thrust", np.float64), ("ref", np.float64), ("err", np.float32)) if lg[name]]
+        chans += [("status", 1, np.int32)] if lg["status"] else []
+        for name, n, dt in chans:
+            a = np.zeros((nr, nb, n), dtype=dt)
+            if nr > 0 or records is not None:
+                self._check(self._lib.usvmpc_cascade_log_read(self._c, name.encode(), r0, nr, b0, nb, a.ctypes.data_as(C.c_void_p), a.nbytes))
+            if name == "status":
+                w = a[:, :, 0].T
+                out["ll_status"], out["ll_qp_iter"] = w & 0xff, (w >> 8) & 0xff
+                out["g_status"], out["g_qp_iter"] = (w >> 16) & 0xff, (w >> 24) & 0x7f
+            else:
+                out[name] = a.transpose(1, 0, 2)
+        return out
+
+    def log_device_ptr(self, channel):
+        """Device address of a log channel ("state", "thrust", "ref", "err", "status") for zero-copy views."""
+        p = C.c_void_p()
+        self._check(self._lib.usvmpc_cascade_log_device_ptr(self._c, channel.encode(), C.byref(p)))
+        return p.value
+
+    def stop_log(self):
+        self._check(self._lib.usvmpc_cascade_log_stop(self._c))
+        self._log = None
+
+    # -- the realised cost of both layers (include/usvmpc.h, "Objective value": usvmpc_cost_track_now)
+    def track_cost(self, on=True):
+        """While on, tick() adds c_0(x0, u_0, yref_0, sl_0, su_0) of the guidance layer to its tracked sum right after every guidance solve,
+        and that of the low level right after every low-level solve, ahead of the step.  on=True (again) zeroes sums and counts; on=False
+        stops and frees.  (A hand-written loop calls g.track_cost_now() / ll.track_cost_now() at the same places.)"""
+        self.g.track_cost(on)
+        self.ll.track_cost(on)
+        self._track = bool(on)
+
+    def tracked_cost(self):
+        """dict(guidance=(sum [B], count), low_level=(sum [B], count)); synchronises."""
+        return dict(guidance=self.g.tracked_cost(), low_level=self.ll.tracked_cost())
+
     def close(self):
         """before either solver is closed"""
         if self._c is not None:
+            if self._log is not None:
+                self._lib.usvmpc_cascade_log_stop(self._c)
+                self._log = None
             self._lib.usvmpc_cascade_destroy(self._c)
             self._c = None

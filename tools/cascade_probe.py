@@ -6,8 +6,13 @@
   - the coupling done by the HOST instead: synchronise, read x_1, heading and speed back, numpy (scenario.cascade_ll_outputs /
     cascade_plant_step / cascade_ll_inputs), upload x0, yref and yref_e.
 
+--log: the same with the cascade's log (every channel, every tick: kernel usv_cascade_record ahead of usv_cascade_step) and the tracked cost
+of both layers (one more usv_cost_track launch per solve) switched on, the launches they add timed on their own, and the alternative they
+replace: the host synchronises at every tick and reads state, thrusts, set-points, errors and both layers' status back.
+
     python tools/cascade_probe.py --batch 8192 65536 --write          -> profiles/cascade_probe.txt
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/cascade_probe.py --batch 8192 --trace-only     (a run of its own)
+    python tools/cascade_probe.py --batch 8192 65536 --log --write    -> profiles/cascade_log_probe.txt
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/cascade_probe.py --batch 8192 --trace-only [--log]    (a run of its own)
 """
 import argparse
 import os
@@ -46,21 +51,48 @@ def timed(stream, fn):
     return a.elapsed_time(b)
 
 
-def probe(B, periods, lines):
+def log_on(cas, ticks):
+    """every channel at every tick, and the realised cost of both layers"""
+    cas.start_log(ticks, err=True)
+    cas.track_cost()
+
+
+def host_log(g, fe, ll, cas):
+    """what a logged tick keeps on the device, read back by the host instead (ms)"""
+    t0 = time.perf_counter()
+    ll.sync()
+    st = cas.state()
+    pub = fe.publish()
+    _, _, eu, epsi = scenario.cascade_ll_outputs(ll.get("x", 1), pub["heading"], pub["speed"], st["state"])
+    word = [s.get_int(f) for s in (ll, g) for f in ("status", "qp_iter")]
+    rec = (st["state"], st["thrust"], pub["heading"], pub["speed"], eu, epsi, word)
+    return 1e3 * (time.perf_counter() - t0), rec
+
+
+def probe(B, periods, lines, log=False):
     g, fe, ll, cas = stack(B)
     st = cas._stream
+    if log:
+        log_on(cas, RATIO * (periods + 1))
     for _ in range(RATIO):                                        # warm-up: one guidance period
         cas.tick()
     g.sync()
-    refs_w, refs_i, step, tick_ll, tick_g, solve = [], [], [], [], [], []
+    refs_w, refs_i, step, tick_ll, tick_g, solve, trk_g, trk_l = [], [], [], [], [], [], [], []
     for p in range(periods):
         for i in range(RATIO):
             gt = cas.guidance_tick()
-            t0 = timed(st, cas.guidance) if gt else 0.0
+            if gt and log:                                       # (Cascade.guidance, the tracking launch timed on its own)
+                t0 = timed(st, lambda: (fe.prepare(), g.solve_async()))
+                trk_g.append(timed(st, g.track_cost_now))
+                t0 += trk_g[-1] + timed(st, lambda: fe.publish(fetch=False))
+            else:
+                t0 = timed(st, cas.guidance) if gt else 0.0
             (refs_w if gt else refs_i).append(timed(st, cas.refs))
             solve.append(timed(st, ll.solve_async))
-            step.append(timed(st, cas.step))
-            (tick_g if gt else tick_ll).append(t0 + (refs_w if gt else refs_i)[-1] + solve[-1] + step[-1])
+            if log:
+                trk_l.append(timed(st, ll.track_cost_now))
+            step.append(timed(st, cas.step))                     # (with a log: usv_cascade_record and usv_cascade_step)
+            (tick_g if gt else tick_ll).append(t0 + (refs_w if gt else refs_i)[-1] + solve[-1] + step[-1] + (trk_l[-1] if log else 0.0))
     writes = cas.state()["yref_writes"]
     lin, qp = ll.kernel_ms(min(len(solve), 32))
     # ---- the same coupling through the host
@@ -81,6 +113,10 @@ def probe(B, periods, lines):
         ll.sync()
         host.append(1e3 * (time.perf_counter() - t0))
     med = lambda v: float(np.median(v)) if len(v) else float("nan")
+    if log:
+        info = cas.log_info()
+        host_rec = [host_log(g, fe, ll, cas)[0] for _ in range(3)]
+        rbytes = B * (6 + 2 + 2) * 8 + B * 2 * 4 + B * 4         # a record: 92 bytes per instance
     wbytes = B * (LN * 10 + 8 + 8) * 8 + B * (6 + 2 + 2 + 2) * 8      # yref + yref_e + x0 written; vessel, past, set-points, last read
     ibytes = B * 8 * 8 + B * (6 + 2 + 2 + 2) * 8
     sbytes = B * (8 + 6 + 2 + 4) * 8 + B * (6 + 2 + 2 + 4) * 8 + B * 4
@@ -92,6 +128,13 @@ def probe(B, periods, lines):
               "  low-level tick                     %8.3f ms   guidance tick %8.3f ms" % (med(tick_ll), med(tick_g)),
               "  coupling net of the QP launches    %8.3f ms (rewriting)  %8.3f ms (idle);  done by the host instead: %8.1f ms" % (
                   med(refs_w) + med(step), med(refs_i) + med(step), med(host))]
+    if log:
+        lines += ["  with the log (every channel, every tick: %d records, %d missed) and the tracked cost of both layers on:" % (info["records"], info["missed"]),
+                  "  usv_cascade_record + usv_cascade_step  %6.3f ms (the step line above)   a record: %.1f MB, %d B per instance" % (med(step), rbytes / 1e6, rbytes // B),
+                  "  usv_cost_track, low level          %8.3f ms   guidance %8.3f ms (guidance ticks only)" % (med(trk_l), med(trk_g)),
+                  "  coupling net of the QP launches, log and tracking included  %8.3f ms (rewriting)  %8.3f ms (idle)" % (
+                      med(refs_w) + med(step) + med(trk_l) + med(trk_g), med(refs_i) + med(step) + med(trk_l)),
+                  "  the same quantities read back by the host at a tick (synchronise, state, publish, x_1, status x 4): %8.1f ms" % med(host_rec)]
     cas.close(); ll.close(); g.close()
 
 
@@ -100,20 +143,25 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, nargs="+", default=[8192, 65536])
     ap.add_argument("--periods", type=int, default=4)
     ap.add_argument("--trace-only", action="store_true", help="run the ticks and print nothing (under rocprofv3 --kernel-trace --stats)")
-    ap.add_argument("--write", nargs="?", const=os.path.join(ROOT, "profiles", "cascade_probe.txt"), default=None, metavar="FILE",
-                    help="also write the lines to FILE (default profiles/cascade_probe.txt)")
+    ap.add_argument("--log", action="store_true", help="the cascade's log and the tracked cost of both layers switched on")
+    ap.add_argument("--write", nargs="?", const="", default=None, metavar="FILE",
+                    help="also write the lines to FILE (default profiles/cascade_probe.txt, with --log profiles/cascade_log_probe.txt)")
     a = ap.parse_args()
-    lines = ["# tools/cascade_probe.py --batch %s --periods %d" % (" ".join(map(str, a.batch)), a.periods)]
+    if a.write == "":
+        a.write = os.path.join(ROOT, "profiles", "cascade_log_probe.txt" if a.log else "cascade_probe.txt")
+    lines = ["# tools/cascade_probe.py --batch %s --periods %d%s" % (" ".join(map(str, a.batch)), a.periods, " --log" if a.log else "")]
     for B in a.batch:
         if a.trace_only:
             g, fe, ll, cas = stack(B)
+            if a.log:
+                log_on(cas, RATIO * a.periods)
             for _ in range(RATIO * a.periods):
                 cas.tick()
             g.sync()
             cas.close(); ll.close(); g.close()
         else:
-            probe(B, a.periods, lines)
-            print("\n".join(lines[-7:]), flush=True)
+            probe(B, a.periods, lines, a.log)
+            print("\n".join(lines[-(12 if a.log else 7):]), flush=True)
     if a.write and not a.trace_only:
         with open(a.write, "w") as f:
             f.write("\n".join(lines) + "\n")
