@@ -523,6 +523,14 @@ int usvmpc_debug_obstacle_eval(int device, int n, int K, const double *pos, cons
  * rcp[i] = lanes::frcp(x[i]), rsq[i] = lanes::frsqrt(x[i]) (hardware estimate + two Newton steps). */
 int usvmpc_debug_model_eval_from(int model, int device, int n, const double *x_start, const double *x, const double *u, double *f, double *J);
 int usvmpc_debug_fast_math(int device, int n, const double *x, double *rcp, double *rsq);
+/* ... and every cross-lane primitive the kernels are written against (csrc/gfx950/lanes.hpp) on caller-supplied operands, through the probe
+ * body of csrc/lanes_probe.hpp: in [ngroups][NIN][16], iin [ngroups][NIIN][16] -> out [ngroups][NOUT][16], iout [ngroups][NIOUT][16] (both
+ * in/out: a result the workgroup shape does not produce keeps the caller's value; the atomics start from the caller's entries).
+ * block_threads is 64 (one wave per workgroup) or 256 (four).  planes is an allocation of planes_doubles doubles that holds the probe's
+ * plane window of ngroups * 3 * 16 doubles from element 64 on, with at least 64 more behind it; it is copied back, so that the caller
+ * sees what the stores changed and that nothing outside the window was touched. */
+int usvmpc_debug_lanes(int device, int ngroups, int block_threads, const double *in, const int *iin, double *out, int *iout, double *planes,
+                       long planes_doubles);
 /* ---- Integrator (acados_template.AcadosSimSolver): B instances of a model's explicit RK4 over one sampling period T, in num_steps
  * steps of T / num_steps, with the forward sensitivities when sens_forw != 0.  The same model functions and RK4 arithmetic as the
  * lineariser's (csrc/sim.hpp); x_next is the same bits with sens_forw on or off, and an instance's result does not depend on the batch.

@@ -65,7 +65,7 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_sync", "usvmpc_get_device_ptr", "usvmpc_last_kernel_ms", "usvmpc_kernel_ms", "usvmpc_tick_ms", "usvmpc_fail_counts", "usvmpc_unconverged_counts", "usvmpc_unconverged_total", "usvmpc_handover_counts", "usvmpc_handover_co_counts", "usvmpc_followup_ms", "usvmpc_pipeline_stats", "usvmpc_lin_pair_launches", "usvmpc_last_mapping",
            "usvmpc_advance", "usvmpc_set_stream", "usvmpc_set_option", "usvmpc_calibrate_traffic", "usvmpc_guidance_reset", "usvmpc_guidance_prepare", "usvmpc_guidance_sense",
            "usvmpc_guidance_publish", "usvmpc_guidance_state", "usvmpc_device_bytes", "usvmpc_last_error",
-           "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval", "usvmpc_debug_model_eval_from", "usvmpc_debug_fast_math",
+           "usvmpc_debug_model_eval", "usvmpc_debug_obstacle_eval", "usvmpc_debug_model_eval_from", "usvmpc_debug_fast_math", "usvmpc_debug_lanes",
            "usvmpc_sim_create", "usvmpc_sim_destroy", "usvmpc_sim_set", "usvmpc_sim_solve", "usvmpc_sim_get", "usvmpc_sim_get_device_ptr",
            "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step",
            "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state",
@@ -173,6 +173,7 @@ def load(path):
     L.usvmpc_debug_obstacle_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_model_eval_from.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_fast_math.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
+    L.usvmpc_debug_lanes.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _ip, _dp, _ip, _dp, C.c_long]
     L.usvmpc_sim_create.argtypes = [C.POINTER(SimDesc), C.POINTER(C.c_void_p)]
     L.usvmpc_sim_destroy.argtypes = [C.c_void_p]
     L.usvmpc_sim_set.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_size_t]

@@ -136,7 +136,9 @@ USV_DEV double gsum(double v)
 }
 // max(a, b), max(a, |b|), max(|a|, |b|) as ONE v_max_f64 each.  fmax() costs two where the compiler cannot prove an operand
 // canonical (anything that went through a select or a load): it puts a v_max_f64 x, x, x in front - half of the kernel's
-// v_max_f64 were those.  The instruction itself returns the other operand for a NaN one, as fmax does.
+// v_max_f64 were those.  The instruction itself returns the other operand for a QUIET NaN one, as fmax does; for a signalling NaN operand it
+// returns NaN, and max(-0, +0) = max(+0, -0) = +0, where fmax may return either (measured: tests/test_gpu_lanes.py,
+// profiles/lanes_conformance.txt).  The |.| modifier applies before all of that: |NaN| is a NaN, |-0| is +0.
 USV_DEV double vmax(double a, double b)
 {
     double r;
@@ -163,6 +165,8 @@ USV_DEV double gmax(double v)
     v = vmax(v, ror<1>(v));
     return v;
 }
+// (fmin, not an asm twin of vmax.  Measured, same record: the rules of vmax mirrored - min(-0, +0) = min(+0, -0) = -0, a quiet NaN
+// operand gives the other operand)
 USV_DEV double gmin(double v)
 {
     v = fmin(v, ror<8>(v));

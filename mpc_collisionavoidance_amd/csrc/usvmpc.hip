@@ -32,6 +32,7 @@
 #include "fleet_world.hpp"
 #include "guidance.hpp"
 #include "host_spec.hpp"
+#include "lanes_probe.hpp"
 #include "lin_plan.hpp"
 #include "log_plan.hpp"
 #include "linearize.hpp"
@@ -1219,6 +1220,14 @@ __global__ void usv_debug_obstacle(int n, int K, const double *pos, const double
     double d, ux, uy;
     usv::obs_dist(pos[2 * pt] - p[(long)pt * 2 * K + 2 * k], pos[2 * pt + 1] - p[(long)pt * 2 * K + 2 * k + 1], d, ux, uy);
     h[i] = d; grad[2 * i] = ux; grad[2 * i + 1] = uy;
+}
+
+// Every primitive of lanes.hpp on caller-supplied operands (lanes_probe.hpp: the same body runs on the CPU emulator of the test suite):
+// a workgroup of WAVES waves takes 4 * WAVES groups, one per 16-lane row
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) usv_debug_lanes(lanes_probe::Args a)
+{
+    lanes_probe::run<WAVES>(a, (long)blockIdx.x * (long)(4 * WAVES));
 }
 
 // Traffic calibration for the rocprofv3 FETCH_SIZE / WRITE_SIZE counters: streams a KNOWN number of
@@ -2768,6 +2777,44 @@ int usvmpc_debug_fast_math(int device, int n, const double *x, double *rcp, doub
         }
     }
     (void)hipFree(dx); (void)hipFree(drcp); (void)hipFree(drsq);
+    return rc;
+}
+
+int usvmpc_debug_lanes(int device, int ngroups, int block_threads, const double *in, const int *iin, double *out, int *iout, double *planes, long planes_doubles)
+{
+    namespace lp = lanes_probe;
+    if (ngroups < 1 || ngroups > (1 << 20) || (block_threads != 64 && block_threads != 256) || !in || !iin || !out || !iout || !planes ||
+        planes_doubles < 2L * lp::PL_PAD + (long)ngroups * lp::NPL * 16)
+        return USVMPC_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return USVMPC_E_NODEVICE;
+    const size_t n_in = sizeof(double) * ngroups * lp::NIN * 16, n_iin = sizeof(int) * ngroups * lp::NIIN * 16, n_out = sizeof(double) * ngroups * lp::NOUT * 16,
+                 n_iout = sizeof(int) * ngroups * lp::NIOUT * 16, n_pl = sizeof(double) * (size_t)planes_doubles;
+    double *din = nullptr, *dout = nullptr, *dpl = nullptr;
+    int *diin = nullptr, *diout = nullptr;
+    int rc = 0;
+    if (hipMalloc((void **)&din, n_in) != hipSuccess || hipMalloc((void **)&diin, n_iin) != hipSuccess || hipMalloc((void **)&dout, n_out) != hipSuccess ||
+        hipMalloc((void **)&diout, n_iout) != hipSuccess || hipMalloc((void **)&dpl, n_pl) != hipSuccess)
+        rc = USVMPC_E_HIP;
+    if (!rc) {
+        (void)hipMemcpy(din, in, n_in, hipMemcpyHostToDevice);
+        (void)hipMemcpy(diin, iin, n_iin, hipMemcpyHostToDevice);
+        (void)hipMemcpy(dout, out, n_out, hipMemcpyHostToDevice);
+        (void)hipMemcpy(diout, iout, n_iout, hipMemcpyHostToDevice);
+        (void)hipMemcpy(dpl, planes, n_pl, hipMemcpyHostToDevice);
+        const lp::Args a{din, diin, dout, diout, dpl, ngroups};
+        const int rows = block_threads / 16;
+        const dim3 grid((unsigned)((ngroups + rows - 1) / rows)), block((unsigned)block_threads);
+        const size_t lds = sizeof(double) * rows * lp::NPL_LDS * 16;
+        if (block_threads == 64) hipLaunchKernelGGL(usv_debug_lanes<1>, grid, block, lds, 0, a);
+        else hipLaunchKernelGGL(usv_debug_lanes<4>, grid, block, lds, 0, a);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = USVMPC_E_HIP;
+        if (!rc) {
+            (void)hipMemcpy(out, dout, n_out, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(iout, diout, n_iout, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(planes, dpl, n_pl, hipMemcpyDeviceToHost);
+        }
+    }
+    (void)hipFree(din); (void)hipFree(diin); (void)hipFree(dout); (void)hipFree(diout); (void)hipFree(dpl);
     return rc;
 }
 

@@ -5,6 +5,7 @@
 #include "lanes.hpp"
 
 #include "host_spec.hpp"
+#include "lanes_probe.hpp"
 #include "linearize.hpp"
 #include "models.hpp"
 #include "qp_ipm.hpp"
@@ -565,5 +566,41 @@ extern "C" int usv_emu_lin_modes(const usvmpc_desc *d, const double *x, const do
     if (d->model == USVMPC_MODEL_PF_CA) return lin_modes<ModelM2, 1, false>(P, S, ready, perm_next, perm_cur, ws_plain, ws_piped, redo_out);
 #endif
     return -3;
+}
+
+// ---- the probe of the lanes:: interface itself (lanes_probe.hpp; the device's usvmpc_debug_lanes, same arguments): one emulated workgroup
+// after the other - the 4 rows of a wave (block_threads 64) or the 16 rows of four waves (256) side by side
+namespace {
+template <int WAVES>
+void lanes_body(void *a)
+{
+    lanes_probe::run<WAVES>(*(const lanes_probe::Args *)a, lanes::group_linear());
+}
+} // namespace
+
+extern "C" int usv_emu_lanes(int device, int ngroups, int block_threads, const double *in, const int *iin, double *out, int *iout, double *planes,
+                             long planes_doubles)
+{
+    namespace lp = lanes_probe;
+    (void)device;
+    if (ngroups < 1 || (block_threads != 64 && block_threads != 256) || !in || !iin || !out || !iout || !planes ||
+        planes_doubles < 2L * lp::PL_PAD + (long)ngroups * lp::NPL * 16)
+        return -1;
+    const int rows = block_threads / 16;
+    std::vector<double> lds((size_t)rows * lp::NPL_LDS * 16, 0.0);
+    lanes::g_emu_lds = lds.data();
+    lp::Args a{in, iin, out, iout, planes, ngroups};
+    for (long base = 0; base < ngroups; base += rows) {
+        if (rows == 4) lanes::run_group(base, &lanes_body<1>, &a, 4);
+        else lanes::run_group(base, &lanes_body<4>, &a, 16);
+    }
+    lanes::g_emu_lds = nullptr;
+    return 0;
+}
+// the probe's dimensions, for the tests: NIN, NIIN, NOUT, NIOUT, NPL, PL_PAD
+extern "C" void usv_emu_lanes_dims(int *d)
+{
+    namespace lp = lanes_probe;
+    d[0] = lp::NIN; d[1] = lp::NIIN; d[2] = lp::NOUT; d[3] = lp::NIOUT; d[4] = lp::NPL; d[5] = lp::PL_PAD;
 }
 #endif // EMU_MAIN

@@ -4,11 +4,18 @@
 // on the CPU.  Selected by include path (-Itests/emu before csrc/gfx950); never part of the
 // shipped library.  Every cross-lane primitive is a rendezvous of all 16 lanes: a lane that
 // skips one (divergent control flow around a DPP op — undefined on the GPU) is detected.
+//
+// This header is the project's model of the hardware, and it is held to the device by test: the probe body of
+// csrc/lanes_probe.hpp runs every primitive below on both, tests/test_lanes_emu.py compares the emulator's results bit for bit with the
+// plain reference of tests/lanes_ref.py, and tests/test_gpu_lanes.py compares the MI355X's with the same reference and with the
+// emulator's in one process (the reciprocals excepted: IEEE division here, estimate + Newton steps there, measured in ulp).  A
+// primitive added to gfx950/lanes.hpp gets its twin here AND its results in the probe.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #define USV_DEV inline __attribute__((always_inline))
 
@@ -78,29 +85,55 @@ inline double gsum(double v)
     v += ror<1>(v);
     return v;
 }
-inline double vmax(double a, double b) { return std::fmax(a, b); }
-inline double vmax_abs(double a, double b) { return std::fmax(a, std::fabs(b)); }
-inline double vmax_abs2(double a, double b) { return std::fmax(std::fabs(a), std::fabs(b)); }
+// v_max_f64 / v_min_f64 as the MI355X executes them (profiles/lanes_conformance.txt, asserted by tests/test_gpu_lanes.py), where
+// std::fmax / std::fmin are free to differ: +0 is larger than -0 whichever operand comes first (glibc returns the first operand), a
+// signalling NaN operand gives NaN, a quiet one the other operand.
+inline bool is_snan(double x)
+{
+    uint64_t b;
+    std::memcpy(&b, &x, sizeof b);
+    return x != x && !(b & 0x0008000000000000ull);
+}
+inline double hw_max(double a, double b)
+{
+    if (is_snan(a) || is_snan(b)) return __builtin_nan("");
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return std::signbit(a) ? b : a;
+    return a > b ? a : b;
+}
+inline double hw_min(double a, double b)
+{
+    if (is_snan(a) || is_snan(b)) return __builtin_nan("");
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return std::signbit(a) ? a : b;
+    return a < b ? a : b;
+}
+inline double vmax(double a, double b) { return hw_max(a, b); }
+inline double vmax_abs(double a, double b) { return hw_max(a, std::fabs(b)); }
+inline double vmax_abs2(double a, double b) { return hw_max(std::fabs(a), std::fabs(b)); }
 inline double gmax(double v)
 {
-    v = std::fmax(v, ror<8>(v));
-    v = std::fmax(v, ror<4>(v));
-    v = std::fmax(v, ror<2>(v));
-    v = std::fmax(v, ror<1>(v));
+    v = vmax(v, ror<8>(v));
+    v = vmax(v, ror<4>(v));
+    v = vmax(v, ror<2>(v));
+    v = vmax(v, ror<1>(v));
     return v;
 }
 inline double gmin(double v)
 {
-    v = std::fmin(v, ror<8>(v));
-    v = std::fmin(v, ror<4>(v));
-    v = std::fmin(v, ror<2>(v));
-    v = std::fmin(v, ror<1>(v));
+    v = hw_min(v, ror<8>(v));
+    v = hw_min(v, ror<4>(v));
+    v = hw_min(v, ror<2>(v));
+    v = hw_min(v, ror<1>(v));
     return v;
 }
 
-// the emulator runs one group at a time, so "any lane of the wave" is "any lane of the group";
-// finished instances are frozen by the kernels, so results do not depend on the grouping
-inline bool wave_any(bool p) { return gmax(p ? 1.0 : 0.0) > 0.5; }
+// one emulated row: "any lane of the wave" is "any lane of the group" (finished instances are frozen by the kernels, so results do
+// not depend on the grouping); a whole emulated wave (rows >= 4): any lane of its four rows, as on the device
+inline double xrow_max(double v);
+inline bool wave_any(bool p) { return xrow_max(gmax(p ? 1.0 : 0.0)) > 0.5; }
 
 inline int uniform(int v) { return v; }
 inline void sched_fence() {}
@@ -129,7 +162,7 @@ inline double xrow_shfl(double v, unsigned mask) { return exchange_wave(v, (int)
 inline double xrow_max(double v)
 {
     if (g_emu.rows < 4) return v;
-    v = std::fmax(v, xrow_shfl(v, 16u)); v = std::fmax(v, xrow_shfl(v, 32u));
+    v = vmax(v, xrow_shfl(v, 16u)); v = vmax(v, xrow_shfl(v, 32u));
     return v;
 }
 inline double xrow_sum(double v)
@@ -158,8 +191,6 @@ struct Planes {
         if (plane < 0 || o + 8 > nbytes) { std::fprintf(stderr, "Planes::ld out of window (plane %d)\n", plane); std::abort(); }
         return base[o / 8];
     }
-    template <int AUX>
-    double ld_policy(int plane) const { return ld(plane); }
     void st(int plane, double x) const
     {
         const unsigned o = voff + (unsigned)plane * 128u;
