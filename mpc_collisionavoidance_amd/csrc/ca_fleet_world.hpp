@@ -42,6 +42,13 @@ USV_HD double ca_fleet_separation(const double *xi, const double *xj)
     return sqrt(track_add(track_mul(dx, dx), track_mul(dy, dy)));
 }
 
+// this model for the gather written once for both (fleet_world.hpp: PfFleet)
+struct CaFleet {
+    static constexpr int NX = CA_FLEET_NX;
+    static USV_HD void entry(const double *xj, double radius, double *w, double *wv) { ca_fleet_entry(xj, radius, w, wv); }
+    static USV_HD double separation(const double *xi, const double *xj) { return ca_fleet_separation(xi, xj); }
+};
+
 // One instance's gather, as the kernel's lanes do it between them: the S - 1 fleet entries behind the n_fixed fixed ones of its world list
 // w ([nworld][3]) / wv ([nworld][2]) and the separation bookkeeping.  x0: the whole batch's states [B][8].
 USV_HD void ca_fleet_gather(const double *x0, long i, int S, int n_fixed, double radius, int tick, double *w, double *wv, double &min_separation,

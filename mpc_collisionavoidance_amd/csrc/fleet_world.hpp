@@ -67,6 +67,13 @@ USV_HD double fleet_separation(const double *xi, const double *xj)
     return sqrt(dx * dx + dy * dy);
 }
 
+// this model for a gather written once for both front ends' models (usvmpc.hip: fleet_gather_body; ca_fleet_world.hpp: CaFleet)
+struct PfFleet {
+    static constexpr int NX = FLEET_NX;
+    static USV_HD void entry(const double *xj, double radius, double *w, double *wv) { fleet_entry(xj, radius, w, wv); }
+    static USV_HD double separation(const double *xi, const double *xj) { return fleet_separation(xi, xj); }
+};
+
 // the running minimum and the tick it was met at (a NaN never wins)
 USV_HD void fleet_closest(double d, int tick, double &min_separation, int &separation_tick)
 {

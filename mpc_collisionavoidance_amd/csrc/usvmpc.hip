@@ -13,7 +13,8 @@
 // bookkeeping, the launches (launch_qp carries out the plan of qp_plan.hpp, where the launch policy lives as a host-only function of plain
 // numbers: tests/test_qp_plan.py; launch_solve likewise the plan of lin_plan.hpp - the lineariser's schedule, maps and grids:
 // tests/test_lin_plan.py; copy_field the field table and the host mirror's bookkeeping of field_plan.hpp: tests/test_field_plan.py;
-// usvmpc_set_option the option table of option_plan.hpp: tests/test_option_plan.py)
+// usvmpc_set_option the option table of option_plan.hpp: tests/test_option_plan.py; carry_world the front ends' world list of
+// world_plan.hpp: tests/test_world_plan.py)
 // and the small kernels, -DUSV_PART=1 .. 5 for the kernels of one pair each - the kernel table
 // kernels_for<M, KCH, SOFT> (explicit instantiation in its part, extern template in part 0, which calls it) - and links the objects.
 // Without USV_PART everything is one translation unit (the generated-model libraries of genbuild.py).
@@ -43,6 +44,7 @@
 #include "qp_ipm.hpp"
 #include "qp_plan.hpp"
 #include "sim.hpp"
+#include "world_plan.hpp"
 #include "cond_launch.hpp"
 #include "field_plan.hpp"
 #ifdef USV_GEN_MODEL_HEADER // a model generated from a symbolic definition (codegen.py): struct ModelGen
@@ -814,8 +816,11 @@ __global__ void __launch_bounds__(256) usv_pf_world_step(double *world, const do
 // entry (24 bytes) and one velocity (16 bytes); the threads of an instance store its S - 1 entries as one run, a wave's runs lying
 // 24 nworld bytes apart.  The separation bookkeeping needs all S - 1 distances of an instance in one place: its slot-0 thread takes the
 // S - 1 positions again (lines its own wave has just loaded) - no atomics, no LDS.
-__global__ void __launch_bounds__(256) usv_pf_fleet_gather(const double *x0, double *world, double *wvel, double *min_sep, int *sep_tick,
-                                                           long B, int S, int n_fixed, double radius, int tick)
+// The body is the same for both front ends' models (usv_guidance_fleet_gather below): Fleet says how wide a state is and how an entry and a
+// separation are made of it (fleet_world.hpp: PfFleet; ca_fleet_world.hpp: CaFleet).
+template <class Fleet>
+__device__ __forceinline__ void fleet_gather_body(const double *x0, double *world, double *wvel, double *min_sep, int *sep_tick, long B, int S,
+                                                  int n_fixed, double radius, int tick)
 {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int f = S - 1;
@@ -823,13 +828,19 @@ __global__ void __launch_bounds__(256) usv_pf_fleet_gather(const double *x0, dou
     const long i = t / f;
     const int e = (int)(t - i * f);
     const long at = i * (n_fixed + f) + n_fixed + e; // the entry's place in the [B][nworld] lists
-    fleet_entry(x0 + fleet_vessel(i, e, S) * FLEET_NX, radius, world + 3 * at, wvel + 2 * at);
+    Fleet::entry(x0 + fleet_vessel(i, e, S) * Fleet::NX, radius, world + 3 * at, wvel + 2 * at);
     if (e != 0) return;
     double m = min_sep[i];
     int mt = sep_tick[i];
-    for (int q = 0; q < f; q++) fleet_closest(fleet_separation(x0 + i * FLEET_NX, x0 + fleet_vessel(i, q, S) * FLEET_NX), tick, m, mt);
+    for (int q = 0; q < f; q++) fleet_closest(Fleet::separation(x0 + i * Fleet::NX, x0 + fleet_vessel(i, q, S) * Fleet::NX), tick, m, mt);
     min_sep[i] = m;
     sep_tick[i] = mt;
+}
+
+__global__ void __launch_bounds__(256) usv_pf_fleet_gather(const double *x0, double *world, double *wvel, double *min_sep, int *sep_tick,
+                                                           long B, int S, int n_fixed, double radius, int tick)
+{
+    fleet_gather_body<PfFleet>(x0, world, wvel, min_sep, sep_tick, B, S, n_fixed, radius, tick);
 }
 
 // usv_pf_publish: the node's outputs after the solve, one lane per instance (a dozen scalars each).  An active instance reads the thrusters
@@ -856,47 +867,24 @@ __global__ void __launch_bounds__(256) usv_pf_publish(DevPtrs P, PfPtrs F)
 // ---- Guidance front end, device-resident (model usv_model_guidance_ca1; the arithmetic: ca_guidance.hpp; host-fed kernels: guidance.hpp).
 constexpr int CA_GROUP = 64; // instances per workgroup of usv_guidance_tick
 
-static __global__ void usv_guidance_mission_reset(double *min_clear, int *finish_tick, int B)
+// "none yet": a running minimum and the tick it was met at (the mission's clearance and finish tick, a fleet's separation)
+static __global__ void usv_guidance_none_yet(double *minimum, int *tick, int B)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    min_clear[b] = 1e300;
-    finish_tick[b] = -1;
-}
-
-static __global__ void usv_guidance_fleet_reset(double *min_sep, int *sep_tick, int B)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    min_sep[b] = 1e300;
-    sep_tick[b] = -1;
+    minimum[b] = 1e300;
+    tick[b] = -1;
 }
 
 // usv_guidance_fleet_gather: vessel encounters (ca_fleet_world.hpp) - the other S - 1 vessels of an instance's scene, as the plant left them
 // in x0, become the fleet entries behind the n_fixed fixed ones of its world list.  A kernel of its own ahead of usv_guidance_tick, which
 // rewrites x0 (ca_x0) while a scene-mate in another workgroup would still be reading it; this one reads x0 only and writes the world lists
-// and the separation bookkeeping only - nothing a lineariser reads.  One thread per (instance, fleet slot), the slot fastest: a thread
-// loads five doubles of one scene-mate (the scene's states are S neighbouring 64-byte rows), takes one sine and one cosine, and stores one
-// entry (24 bytes) and one velocity (16 bytes); the threads of an instance store its S - 1 entries as one run, a wave's runs lying
-// 24 nworld bytes apart.  The separation bookkeeping needs all S - 1 distances of an instance in one place: its slot-0 thread takes the
-// S - 1 positions again (lines its own wave has just loaded) - no atomics, no LDS.
+// and the separation bookkeeping only - nothing a lineariser reads.  Threads and stores as usv_pf_fleet_gather (one body, fleet_gather_body);
+// a thread loads five doubles of one scene-mate (the scene's states are S neighbouring 64-byte rows) and takes one sine and one cosine.
 __global__ void __launch_bounds__(256) usv_guidance_fleet_gather(const double *x0, double *world, double *wvel, double *min_sep, int *sep_tick,
                                                                  long B, int S, int n_fixed, double radius, int tick)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int f = S - 1;
-    if (t >= B * f) return;
-    const long i = t / f;
-    const int e = (int)(t - i * f);
-    const long at = i * (n_fixed + f) + n_fixed + e; // the entry's place in the [B][nworld] lists
-    ca_fleet_entry(x0 + fleet_vessel(i, e, S) * CA_FLEET_NX, radius, world + 3 * at, wvel + 2 * at);
-    if (e != 0) return;
-    double m = min_sep[i];
-    int mt = sep_tick[i];
-    for (int q = 0; q < f; q++)
-        fleet_closest(ca_fleet_separation(x0 + i * CA_FLEET_NX, x0 + fleet_vessel(i, q, S) * CA_FLEET_NX), tick, m, mt);
-    min_sep[i] = m;
-    sep_tick[i] = mt;
+    fleet_gather_body<CaFleet>(x0, world, wvel, min_sep, sep_tick, B, S, n_fixed, radius, tick);
 }
 
 // usv_guidance_tick: the node's input side for a vessel whose state is the solver's own x0 (as usv_advance / usv_advance_sim left it) against
@@ -1332,27 +1320,28 @@ struct usvmpc_handle {
     bool gd_ready;
     int gd_npts_cap;
     double *gd_psi;
-    double *gd_world;   // [B][n_world][3] world obstacles of the last usvmpc_guidance_sense
-    size_t gd_world_cap;
+    double *gd_sense_world;   // [B][n_world][3] the host-fed world obstacles of the last usvmpc_guidance_sense (not the resident list: `world`)
+    size_t gd_sense_world_cap;
     // Path-following front end (usvmpc_pf_*, model usv_model_pf_ca): device buffers on first use; pf_ready after usvmpc_pf_reset
     PfPtrs pf;
     bool pf_alloc, pf_ready;
     bool pf_stale = true;     // the caller may have written yref / yref_e since the front end last did: the next prepare rewrites every active instance
     int pf_tick;              // prepares since the last reset
     int pf_npts_cap;
-    size_t pf_world_cap;      // doubles
     double *pf_vel, *pf_pose; // [B][3] staging of the host-fed mode
-    // A moving world (usvmpc_pf_world_vel): velocities per world entry; prepare then writes every stage of p / lh ("static_obstacles" off)
-    // unless option "pf_predict" is 0, and usvmpc_advance / _advance_sim move the world (option "obstacle_step_on_advance")
-    double *pf_wvel;          // [B][nworld][2]
-    size_t pf_wvel_cap;       // doubles
-    bool pf_world_set;        // usvmpc_pf_world has been called
-    bool pf_moving;           // velocities are set for the current list
-    // Vessel encounters (usvmpc_pf_fleet, fleet_world.hpp): scenes of pf_fleet_S consecutive instances; the world list is then the caller's
-    // pf_nfixed entries followed by pf_fleet_S - 1 fleet slots (pf.nworld counts both), which a resident prepare gathers from x0
-    int pf_fleet_S = 0;       // 0: no fleet
-    int pf_nfixed = 0;        // (meaningful while a fleet is on)
-    double pf_fleet_radius = 0.0;
+    // The front end's resident world (usvmpc_guidance_world / usvmpc_pf_world and their _world_vel, _world_step, _world_read, _fleet and
+    // _fleet_state): a handle has one model, so one front end and ONE world.  What a call refuses, what it does and what the list is afterwards
+    // is world_plan.hpp's: the state machine WorldPlan (no field of it is assigned in this file - the entry points ask it to judge, carry_world
+    // does what it answers and commits), host-only and checked on the CPU by tests/test_world_plan.py.  Here: the device buffers it speaks of.
+    // The world members of PfPtrs / CaTickPtrs (kernel arguments) are filled from these where a launch is made: pf_args, guidance_tick.
+    WorldPlan world;
+    struct WorldBufs {
+        double *list;         // [B][nworld][3] NED (X, Y, R): the caller's fixed entries, a fleet's slots behind them (fleet_world.hpp)
+        double *vel;          // [B][nworld][2] NED m/s
+        double *trk_pv, *trk_lh; // [B][K][4], [B][K] the slot tracks a predicted prepare leaves between its two steps
+        double *min_sep;      // [B] smallest distance to a vessel of the instance's scene (1e300 after a reset)
+        int *sep_tick;        // [B] the prepare it was met at (-1: none yet)
+    } wb;
     int last_wide;            // the last RTI launch ran on the wide kernel
     // hand-over of long runners to a follow-up launch (option "handover_iter")
     int *d_susp_count, *d_susp_list; // [RING] instances each of the last launches handed over / [B] their groups
@@ -1412,21 +1401,8 @@ struct usvmpc_handle {
     // The guidance front end's device-resident mode (usvmpc_guidance_world; the kernel: usv_guidance_tick): the world list lives on the device
     // and a prepare without host arrays reads the vessel's state from x0.  A moving world (usvmpc_guidance_world_vel) as the path-following
     // front end's: velocities per entry, every stage of p / lh written when it is predicted, moved on by usvmpc_advance / _advance_sim.
-    CaTickPtrs gd_tickp = {};   // world, its size and radius, the slot tracks, min_clear, finish_tick (wvel and tick: filled per launch)
-    size_t gd_rworld_cap = 0;   // doubles
-    double *gd_wvel = nullptr;  // [B][nworld][2]
-    size_t gd_wvel_cap = 0;     // doubles
-    bool gd_world_set = false;  // usvmpc_guidance_world has been called
-    bool gd_moving = false;     // velocities are set for the current list
-    bool gd_predict = false;    // ... and the horizon sees them ("static_obstacles" off)
+    CaTickPtrs gd_tickp = {};   // min_clear, finish_tick (the world, its tracks and tick: filled per launch)
     int gd_tick = 0;            // device-resident prepares since the last reset
-    // Vessel encounters (usvmpc_guidance_fleet, ca_fleet_world.hpp): scenes of gd_fleet_S consecutive instances; the world list is then the
-    // caller's gd_nfixed entries followed by gd_fleet_S - 1 fleet slots (gd_tickp.nworld counts both), which a resident prepare gathers from x0
-    int gd_fleet_S = 0;         // 0: no fleet
-    int gd_nfixed = 0;          // (meaningful while a fleet is on)
-    double gd_fleet_radius = 0.0;
-    double *gd_min_sep = nullptr; // [B] smallest distance to a vessel of the instance's scene (allocated by the first usvmpc_guidance_fleet)
-    int *gd_sep_tick = nullptr;   // [B] the prepare it was met at (-1: none yet)
     // Closed-loop log (usvmpc_log_*): which hand-over records, the counters and the layout are log_plan.hpp's - the state machine LogPlan (no
     // field of it is assigned in this file: usvmpc_log_start / _stop and log_handover call its methods), host-only and checked on the CPU by
     // tests/test_log_plan.py.  Here: the buffers its layout sizes (nullptr: channel not recorded) and the kernel arguments that do not change.
@@ -2934,7 +2910,8 @@ int usvmpc_last_kernel_ms(usvmpc_handle *h, float *linearize_ms, float *qp_ms)
     return usvmpc_kernel_ms(h, 1, linearize_ms, qp_ms);
 }
 
-static int pf_apply_static(usvmpc_handle *h);
+static int apply_static(usvmpc_handle *h);
+static int world_step(usvmpc_handle *h, double T);
 
 // ---- the closed-loop log: log_plan.hpp says what a hand-over does and what a read copies; here: the buffers, the launch, the copies
 static void log_release(usvmpc_handle *h)
@@ -3158,8 +3135,7 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
                        h->opt.instance_offset);
     HIP_TRY(h, hipGetLastError());
     if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
-    if (h->pf_moving && h->opt.step_on_advance) return usvmpc_pf_world_step(h, h->spec.dt); // (the front end's world likewise)
-    if (h->gd_moving && h->opt.step_on_advance) return usvmpc_guidance_world_step(h, h->spec.dt);
+    if (h->world.steps_on_advance(h->opt.step_on_advance != 0)) return world_step(h, h->spec.dt); // (the front end's world likewise)
     return 0;
 }
 
@@ -3222,8 +3198,7 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     }
     HIP_TRY(h, hipGetLastError());
     if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
-    if (h->pf_moving && h->opt.step_on_advance) return usvmpc_pf_world_step(h, plant->T);
-    if (h->gd_moving && h->opt.step_on_advance) return usvmpc_guidance_world_step(h, plant->T);
+    if (h->world.steps_on_advance(h->opt.step_on_advance != 0)) return world_step(h, plant->T);
     return 0;
 }
 
@@ -3246,14 +3221,16 @@ static int upload_spec(usvmpc_handle *h)
 static const char *option_refused(const usvmpc_handle *h, OptId id, double v)
 {
     switch (id) {
-    case OPT_OBSTACLE_TRACKS: // (off: p stays as it stands and is the caller's again)
+    case OPT_OBSTACLE_TRACKS: { // (off: p stays as it stands and is the caller's again)
         if (v == 0.0) break;
-        if (h->pf_fleet_S) return "obstacle_tracks: a fleet is on (usvmpc_pf_fleet) and the path-following front end owns p on this handle";
+        const bool pf = h->desc.model == USVMPC_MODEL_PF_CA; // (whose world h->world is)
+        if (pf && h->world.fleet_S()) return "obstacle_tracks: a fleet is on (usvmpc_pf_fleet) and the path-following front end owns p on this handle";
         if (!h->tracks_pos_set) return "obstacle_tracks: set \"obs_pos\" before switching the option on";
         if (h->pf_ready) return "obstacle_tracks: the path-following front end owns p on this handle";
-        if (h->pf_moving) return "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle";
-        if (h->gd_moving) return "obstacle_tracks: the guidance front end's world moves (usvmpc_guidance_world_vel) and owns p on this handle";
+        if (pf && h->world.moving()) return "obstacle_tracks: the path-following front end's world moves (usvmpc_pf_world_vel) and owns p on this handle";
+        if (!pf && h->world.moving()) return "obstacle_tracks: the guidance front end's world moves (usvmpc_guidance_world_vel) and owns p on this handle";
         break;
+    }
     case OPT_HOST_MIRROR:
         if (v != 0.0 && !h->mirror) return "host_mirror cannot be switched on again";
         break;
@@ -3269,7 +3246,7 @@ static int option_hook(usvmpc_handle *h, OptId id, double v)
     case OPT_OBSTACLE_TRACKS:
         if (v != 0.0) h->tracks_dirty = true;
         break;
-    case OPT_PF_PREDICT: return h->pf_ready ? pf_apply_static(h) : 0;
+    case OPT_PF_PREDICT: return h->pf_ready ? apply_static(h) : 0;
     case OPT_SORT_BY_DIFFICULTY:
         if (v == 0.0 && h->ptrs.perm) { h->ptrs.perm = nullptr; h->map_changed = true; }
         break;
@@ -3301,7 +3278,7 @@ static int option_hook(usvmpc_handle *h, OptId id, double v)
 }
 
 // an accepted value (parse_option's) takes effect: the steps in this order for every option, each where the row asks for it.  Also the
-// typed way in for the library's own switches ("static_obstacles": guidance_reset, pf_apply_static).
+// typed way in for the library's own switches ("static_obstacles": apply_static).
 static int apply_option(usvmpc_handle *h, OptId id, double v)
 {
     const OptRow &row = OPTION_TABLE[id];
@@ -3349,52 +3326,200 @@ int usvmpc_set_option(usvmpc_handle *h, const char *name, double value)
 }
 
 
-// Vessel encounters, either front end: a world list ([B][n][3] at *world, velocities [B][n][2] at *wvel - read only when `moving` -, capacities
-// in doubles) laid out anew through the host: n0 entries of which the last f0 are fleet slots -> n1_fixed fixed entries and f1 fleet slots
-// (fleet_world.hpp: fleet_relayout, which says what is kept).  fixed: the new fixed entries [B][n1_fixed][3]; null keeps the present ones.
-// Afterwards the list has velocities, whether the world moved before or not.  A set-up call, never part of a tick.
-static int world_relayout(usvmpc_handle *h, const double **world, size_t *world_cap, double **wvel, size_t *wvel_cap, bool moving, int n0, int f0,
-                          const double *fixed, int n1_fixed, int f1)
+// ---- the front ends' resident world (include/usvmpc.h: usvmpc_guidance_world .. _fleet_state, usvmpc_pf_world .. _fleet_state): world_plan.hpp
+// judges a call and says what is to be done; here it is done.  Set-up calls all, a world step apart: they wait for the stream.
+static const WorldKind &world_kind(const usvmpc_handle *h) { return h->desc.model == USVMPC_MODEL_PF_CA ? WORLD_PF : WORLD_GUIDANCE; } // (whose world h->world is)
+
+static WorldFacts world_facts(const usvmpc_handle *h, const WorldKind &k)
 {
-    const size_t B = h->B;
-    const int n0_fixed = n0 - f0, n1 = n1_fixed + f1;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step on the old list may be in flight)
-    std::vector<double> w0(B * (size_t)n0 * 3), v0(B * (size_t)n0 * 2), w1(B * (size_t)n1 * 3), v1(B * (size_t)n1 * 2);
-    if (!w0.empty()) HIP_TRY(h, hipMemcpyAsync(w0.data(), *world, w0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (!v0.empty() && moving) HIP_TRY(h, hipMemcpyAsync(v0.data(), *wvel, v0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (size_t b = 0; b < B; b++)
-        fleet_relayout(w0.data() + b * (size_t)n0 * 3, moving ? v0.data() + b * (size_t)n0 * 2 : nullptr, n0_fixed, f0,
-                       fixed ? fixed + b * (size_t)n1_fixed * 3 : nullptr, n1_fixed, f1, w1.data() + b * (size_t)n1 * 3, v1.data() + b * (size_t)n1 * 2);
-    if (w1.size() > *world_cap) {
-        dev_free(h, const_cast<double *>(*world), *world_cap * sizeof(double));
-        *world = nullptr; *world_cap = 0;
-        double *d = nullptr;
-        if (dev_alloc(h, &d, w1.size(), false)) return USVMPC_E_HIP;
-        *world = d;
-        *world_cap = w1.size();
-    }
-    if (v1.size() > *wvel_cap || !*wvel) {
-        dev_free(h, *wvel, *wvel_cap * sizeof(double));
-        *wvel = nullptr; *wvel_cap = 0;
-        if (dev_alloc(h, wvel, v1.size(), false)) return USVMPC_E_HIP;
-        *wvel_cap = v1.size();
-    }
-    if (!w1.empty()) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(*world), w1.data(), w1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!v1.empty()) HIP_TRY(h, hipMemcpyAsync(*wvel, v1.data(), v1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
+    const bool pf = &k == &WORLD_PF;
+    return WorldFacts{&k, h->B, h->desc.model == (pf ? USVMPC_MODEL_PF_CA : USVMPC_MODEL_GUIDANCE_CA1), pf ? h->pf_ready : h->gd_ready,
+                      h->opt.tracks_on != 0, h->opt.pf_predict != 0};
 }
 
-// ---- guidance front end (M1 only): see ca_guidance.hpp (the arithmetic), guidance.hpp (the host-fed kernels), usv_guidance_tick above
-// "static_obstacles" as the front end needs it: off only while its world moves AND is predicted per stage (the tick then writes all stages)
-static int gd_apply_static(usvmpc_handle *h)
+// "static_obstacles" as the front end needs it: off only while its world moves AND is predicted per stage (a prepare then writes all stages)
+static int apply_static(usvmpc_handle *h)
 {
-    const bool want = !(h->gd_moving && h->gd_predict);
+    const bool want = h->world.want_static(world_kind(h), h->opt.pf_predict != 0);
     if ((h->spec.p_static != 0) == want) return 0;
     return apply_option(h, OPT_STATIC_OBSTACLES, want ? 1.0 : 0.0);
 }
+
+static int pf_alloc(usvmpc_handle *h);
+
+// a world buffer (the list, or the velocities) of `need` doubles in place of the present one, which is released first; the plan hears of both
+static int world_buffer(usvmpc_handle *h, double **buf, size_t need, bool vel)
+{
+    dev_free(h, *buf, (vel ? h->world.vel_cap() : h->world.list_cap()) * sizeof(double));
+    *buf = nullptr;
+    vel ? h->world.vel_buffer(0, false) : h->world.list_buffer(0);
+    if (dev_alloc(h, buf, need, false)) return USVMPC_E_HIP;
+    vel ? h->world.vel_buffer(need, true) : h->world.list_buffer(need);
+    return 0;
+}
+
+// what a judged call does on the device.  in: the caller's list or velocities; out, out2: where a read or a fleet_state answers
+static int carry_world(usvmpc_handle *h, const WorldAct &a, const double *in, double T, double *out, void *out2)
+{
+    usvmpc_handle::WorldBufs &D = h->wb;
+    const size_t B = h->B, n = B * (size_t)a.n;
+    if (a.what == WORLD_NOTHING) return 0;
+    if (a.what == WORLD_FLEET_STATE && a.host_answer) {
+        if (out) std::fill(out, out + B, 1e300);
+        if (out2) std::fill((int *)out2, (int *)out2 + B, -1);
+        return 0;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (a.make_front_end) {
+        const int rc = pf_alloc(h);
+        if (rc) return rc;
+    }
+    const size_t slots = B * (size_t)(h->K ? h->K : 1);
+    if (a.make_tracks && !D.trk_pv && (dev_alloc(h, &D.trk_pv, slots * 4, true) || dev_alloc(h, &D.trk_lh, slots, true))) return USVMPC_E_HIP;
+    if (a.make_sep && !D.min_sep) {
+        if (dev_alloc(h, &D.min_sep, B, true) || dev_alloc(h, &D.sep_tick, B, true)) return USVMPC_E_HIP;
+        hipLaunchKernelGGL(usv_guidance_none_yet, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, D.min_sep, D.sep_tick, (int)B);
+        HIP_TRY(h, hipGetLastError());
+    }
+    switch (a.what) {
+    case WORLD_UPLOAD_LIST:
+    case WORLD_UPLOAD_VEL: {
+        const bool vel = a.what == WORLD_UPLOAD_VEL;
+        HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step that reads the old ones may be in flight)
+        if (a.grow && world_buffer(h, vel ? &D.vel : &D.list, a.need, vel)) return USVMPC_E_HIP;
+        if (a.need) HIP_TRY(h, hipMemcpyAsync(vel ? D.vel : D.list, in, a.need * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
+    case WORLD_RELAYOUT: { // the list laid out anew through the host (fleet_world.hpp: fleet_relayout, which says what is kept; in: the new fixed
+        // entries [B][n1_fixed][3]).  Afterwards the list has velocities, whether the world moved before or not.
+        const double *fixed = a.new_fixed ? in : nullptr;
+        const bool moving = h->world.moving();
+        const int n0 = a.n0, n1 = a.n1_fixed + a.f1;
+        HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step on the old list may be in flight)
+        std::vector<double> w0(B * (size_t)n0 * 3), v0(B * (size_t)n0 * 2), w1(a.need), v1(a.need_vel);
+        if (!w0.empty()) HIP_TRY(h, hipMemcpyAsync(w0.data(), D.list, w0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (!v0.empty() && moving) HIP_TRY(h, hipMemcpyAsync(v0.data(), D.vel, v0.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < B; b++)
+            fleet_relayout(w0.data() + b * (size_t)n0 * 3, moving ? v0.data() + b * (size_t)n0 * 2 : nullptr, n0 - a.f0, a.f0,
+                           fixed ? fixed + b * (size_t)a.n1_fixed * 3 : nullptr, a.n1_fixed, a.f1, w1.data() + b * (size_t)n1 * 3, v1.data() + b * (size_t)n1 * 2);
+        if (a.grow && world_buffer(h, &D.list, a.need, false)) return USVMPC_E_HIP;
+        if (a.grow_vel && world_buffer(h, &D.vel, a.need_vel, true)) return USVMPC_E_HIP;
+        if (!w1.empty()) HIP_TRY(h, hipMemcpyAsync(D.list, w1.data(), w1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (!v1.empty()) HIP_TRY(h, hipMemcpyAsync(D.vel, v1.data(), v1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
+    case WORLD_MERGE_VEL: { // [B][nvel][2] into the head of every instance's [n][2]
+        const size_t row = (size_t)a.n * 2, head = (size_t)a.nvel * 2;
+        std::vector<double> v(B * row);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipMemcpyAsync(v.data(), D.vel, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < B; b++) std::copy(in + b * head, in + (b + 1) * head, v.begin() + (long)(b * row));
+        HIP_TRY(h, hipMemcpyAsync(D.vel, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
+    case WORLD_STEP: // (one kernel for both front ends' worlds: pos += T vel per entry, track_step; no wait - it is part of a tick)
+        hipLaunchKernelGGL(usv_pf_world_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, D.list, (const double *)D.vel, (long)n, T);
+        HIP_TRY(h, hipGetLastError());
+        return 0;
+    case WORLD_READ: {
+        double *vel = (double *)out2;
+        if (out && n) HIP_TRY(h, hipMemcpyAsync(out, D.list, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (vel && n && a.vel_on_device) HIP_TRY(h, hipMemcpyAsync(vel, D.vel, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (vel && !a.vel_on_device) std::fill(vel, vel + n * 2, 0.0); // (a world at rest)
+        return 0;
+    }
+    case WORLD_FLEET_STATE:
+        if (out) HIP_TRY(h, hipMemcpyAsync(out, D.min_sep, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (out2) HIP_TRY(h, hipMemcpyAsync(out2, D.sep_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return 0;
+    default: return 0;
+    }
+}
+
+// an entry point after its null check: the judged call is refused, or carried out and then made to stand
+static int world_call(usvmpc_handle *h, const WorldAct &a, const double *in = nullptr, double T = 0.0, double *out = nullptr, void *out2 = nullptr)
+{
+    if (!a.refused.empty()) { h->err = a.refused; return USVMPC_E_ARG; }
+    const int rc = carry_world(h, a, in, T, out, out2);
+    if (rc) return rc;
+    h->world.commit(a);
+    return a.apply_static ? apply_static(h) : 0;
+}
+
+int usvmpc_guidance_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
+{
+    return h ? world_call(h, h->world.world(world_facts(h, WORLD_GUIDANCE), world, n_world, max_radius), world) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
+{
+    return h ? world_call(h, h->world.world(world_facts(h, WORLD_PF), world, n_world, max_radius), world) : USVMPC_E_ARG;
+}
+
+int usvmpc_guidance_world_vel(usvmpc_handle *h, const double *vel, int predict)
+{
+    return h ? world_call(h, h->world.vel(world_facts(h, WORLD_GUIDANCE), vel, predict), vel) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel)
+{
+    return h ? world_call(h, h->world.vel(world_facts(h, WORLD_PF), vel, 0), vel) : USVMPC_E_ARG;
+}
+
+int usvmpc_guidance_world_step(usvmpc_handle *h, double T)
+{
+    return h ? world_call(h, h->world.step(world_facts(h, WORLD_GUIDANCE), T), nullptr, T) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_world_step(usvmpc_handle *h, double T)
+{
+    return h ? world_call(h, h->world.step(world_facts(h, WORLD_PF), T), nullptr, T) : USVMPC_E_ARG;
+}
+
+// usvmpc_advance, _advance_sim and the cascade's hand-over: the world of the handle's own front end moves with the vessel
+static int world_step(usvmpc_handle *h, double T)
+{
+    return world_call(h, h->world.step(world_facts(h, world_kind(h)), T), nullptr, T);
+}
+
+int usvmpc_guidance_world_read(usvmpc_handle *h, double *world, double *vel)
+{
+    return h ? world_call(h, h->world.read(world_facts(h, WORLD_GUIDANCE)), nullptr, 0.0, world, vel) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_world_read(usvmpc_handle *h, double *world, double *vel)
+{
+    return h ? world_call(h, h->world.read(world_facts(h, WORLD_PF)), nullptr, 0.0, world, vel) : USVMPC_E_ARG;
+}
+
+int usvmpc_guidance_fleet(usvmpc_handle *h, int scene_size, double radius)
+{
+    return h ? world_call(h, h->world.fleet(world_facts(h, WORLD_GUIDANCE), scene_size, radius)) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_fleet(usvmpc_handle *h, int scene_size, double radius)
+{
+    return h ? world_call(h, h->world.fleet(world_facts(h, WORLD_PF), scene_size, radius)) : USVMPC_E_ARG;
+}
+
+int usvmpc_guidance_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick)
+{
+    return h ? world_call(h, h->world.fleet_state(world_facts(h, WORLD_GUIDANCE)), nullptr, 0.0, min_separation, separation_tick) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick)
+{
+    return h ? world_call(h, h->world.fleet_state(world_facts(h, WORLD_PF)), nullptr, 0.0, min_separation, separation_tick) : USVMPC_E_ARG;
+}
+
+// ---- guidance front end (M1 only): see ca_guidance.hpp (the arithmetic), guidance.hpp (the host-fed kernels), usv_guidance_tick above
 
 static int guidance_alloc(usvmpc_handle *h, int npts)
 {
@@ -3444,16 +3569,16 @@ int usvmpc_guidance_reset(usvmpc_handle *h, const double *waypoints, int npts, c
     HIP_TRY(h, hipMemcpyAsync(h->gd_psi, psi, B * sizeof(double), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(usv_guidance_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, G, h->gd_psi, (int)B);
     HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(usv_guidance_mission_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->gd_tickp.min_clear,
+    hipLaunchKernelGGL(usv_guidance_none_yet, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->gd_tickp.min_clear,
                        h->gd_tickp.finish_tick, (int)B);
     HIP_TRY(h, hipGetLastError());
-    if (h->gd_min_sep) {
-        hipLaunchKernelGGL(usv_guidance_fleet_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->gd_min_sep, h->gd_sep_tick, (int)B);
+    if (h->wb.min_sep) { // (a fleet has been on)
+        hipLaunchKernelGGL(usv_guidance_none_yet, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->wb.min_sep, h->wb.sep_tick, (int)B);
         HIP_TRY(h, hipGetLastError());
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->gd_tick = 0;
-    return gd_apply_static(h);
+    return apply_static(h);
 }
 
 static int guidance_tick(usvmpc_handle *h);
@@ -3467,7 +3592,7 @@ int usvmpc_guidance_prepare(usvmpc_handle *h, const double *vel_uv, const double
     if (lmax < 0 || lmax > GUIDANCE_LMAX) return USVMPC_E_ARG;
     if (!h->gd_ready || h->gd.npts < 2) { h->err = "usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
     if (!vel_uv) return guidance_tick(h);
-    if (h->gd_fleet_S) {
+    if (h->world.fleet_S()) {
         h->err = "guidance_prepare: a fleet is on and its scene exists on the device only; prepare device-resident (vel_uv and pose NULL)";
         return USVMPC_E_ARG;
     }
@@ -3501,19 +3626,22 @@ int usvmpc_guidance_prepare(usvmpc_handle *h, const double *vel_uv, const double
 // writes x0, p and lh only - nothing a lineariser reads - so a linearisation made a tick ahead stands (no spec_cancel, unlike usvmpc_pf_prepare).
 static int guidance_tick(usvmpc_handle *h)
 {
-    if (!h->gd_world_set) { h->err = "guidance_prepare: the device-resident tick needs a world list (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
+    if (!h->world.exists()) { h->err = "guidance_prepare: the device-resident tick needs a world list (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
     HIP_TRY(h, hipSetDevice(h->device));
     const int rcf = mirror_flush(h);
     if (rcf) return rcf;
+    const WorldPlan &w = h->world;
+    const usvmpc_handle::WorldBufs &D = h->wb;
     CaTickPtrs W = h->gd_tickp;
-    W.wvel = (h->gd_moving && h->gd_predict) ? h->gd_wvel : nullptr; // (held still inside the horizon: the tick of a world at rest)
+    W.world = D.list; W.nworld = w.nworld(); W.max_radius = w.max_radius();
+    W.trk_pv = D.trk_pv; W.trk_lh = D.trk_lh;
+    W.wvel = w.want_static(WORLD_GUIDANCE, false) ? nullptr : D.vel; // (held still inside the horizon: the tick of a world at rest)
     W.tick = h->gd_tick;
     const size_t B = h->B;
-    if (h->gd_fleet_S) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_guidance_tick rewrites x0
-        const long n = (long)B * fleet_slots(h->gd_fleet_S);
-        hipLaunchKernelGGL(usv_guidance_fleet_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs.x0,
-                           const_cast<double *>(W.world), h->gd_wvel, h->gd_min_sep, h->gd_sep_tick, (long)B, h->gd_fleet_S, h->gd_nfixed,
-                           h->gd_fleet_radius, h->gd_tick);
+    if (w.fleet_S()) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_guidance_tick rewrites x0
+        const long n = (long)B * fleet_slots(w.fleet_S());
+        hipLaunchKernelGGL(usv_guidance_fleet_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs.x0, D.list, D.vel,
+                           D.min_sep, D.sep_tick, (long)B, w.fleet_S(), w.nfixed(), w.fleet_radius(), h->gd_tick);
         HIP_TRY(h, hipGetLastError());
     }
     hipLaunchKernelGGL(usv_guidance_tick, dim3((unsigned)((B + CA_GROUP - 1) / CA_GROUP)), dim3(256), 0, h->stream, h->ptrs, h->gd, W);
@@ -3527,23 +3655,23 @@ int usvmpc_guidance_sense(usvmpc_handle *h, const double *pose, const double *wo
 {
     if (!h || !pose || n_world < 0 || (n_world > 0 && !world)) return USVMPC_E_ARG;
     if (!h->gd_ready) { h->err = "usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
-    if (h->gd_fleet_S) {
+    if (h->world.fleet_S()) {
         h->err = "guidance_sense: a fleet is on and its scene exists on the device only; prepare device-resident (usvmpc_guidance_prepare, vel_uv and pose NULL)";
         return USVMPC_E_ARG;
     }
     HIP_TRY(h, hipSetDevice(h->device));
     GuidancePtrs &G = h->gd;
     const size_t B = h->B;
-    if ((size_t)n_world > h->gd_world_cap) {
-        dev_free(h, h->gd_world, B * h->gd_world_cap * 3 * sizeof(double));
-        h->gd_world = nullptr;
-        if (dev_alloc(h, &h->gd_world, B * (size_t)n_world * 3, true)) return USVMPC_E_HIP;
-        h->gd_world_cap = (size_t)n_world;
+    if ((size_t)n_world > h->gd_sense_world_cap) {
+        dev_free(h, h->gd_sense_world, B * h->gd_sense_world_cap * 3 * sizeof(double));
+        h->gd_sense_world = nullptr;
+        if (dev_alloc(h, &h->gd_sense_world, B * (size_t)n_world * 3, true)) return USVMPC_E_HIP;
+        h->gd_sense_world_cap = (size_t)n_world;
     }
     HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(G.pose), pose, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (n_world > 0)
-        HIP_TRY(h, hipMemcpyAsync(h->gd_world, world, B * (size_t)n_world * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(usv_obstacle_sim, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, h->stream, G, h->gd_world, n_world,
+        HIP_TRY(h, hipMemcpyAsync(h->gd_sense_world, world, B * (size_t)n_world * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(usv_obstacle_sim, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, h->stream, G, h->gd_sense_world, n_world,
                        max_radius, (int)B);
     HIP_TRY(h, hipGetLastError());
     if (obstacles)
@@ -3584,136 +3712,11 @@ int usvmpc_guidance_state(usvmpc_handle *h, int *wp_index, float *past_psied)
     return 0;
 }
 
-// ---- the guidance front end's resident world and mission state (include/usvmpc.h)
+// ---- the guidance front end's mission state (include/usvmpc.h; its resident world: carry_world above)
 static int gd_check(usvmpc_handle *h, const char *who)
 {
     if (h->desc.model != USVMPC_MODEL_GUIDANCE_CA1) { h->err = std::string(who) + ": the guidance front end belongs to usv_model_guidance_ca1"; return USVMPC_E_ARG; }
     if (!h->gd_ready) { h->err = std::string(who) + ": usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
-    return 0;
-}
-
-int usvmpc_guidance_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = gd_check(h, "guidance_world");
-    if (rc) return rc;
-    if (n_world < 0 || n_world > GUIDANCE_LMAX) { h->err = "guidance_world: n_world must lie in 0.." + std::to_string(GUIDANCE_LMAX); return USVMPC_E_ARG; }
-    if (n_world > 0 && !world) { h->err = "guidance_world: null world list"; return USVMPC_E_ARG; }
-    if (!(max_radius == max_radius)) { h->err = "guidance_world: max_radius is NaN"; return USVMPC_E_ARG; }
-    const size_t need = (size_t)h->B * (size_t)n_world * 3;
-    for (size_t i = 0; i < need; i++)
-        if (!(world[i] == world[i])) { h->err = "guidance_world: entry " + std::to_string(i) + " is NaN"; return USVMPC_E_ARG; }
-    CaTickPtrs &W = h->gd_tickp;
-    if (h->gd_fleet_S) { // (the fixed entries only; the fleet slots stay)
-        if (!fleet_fits(n_world, h->gd_fleet_S)) {
-            h->err = "guidance_world: a fleet is on and owns " + std::to_string(fleet_slots(h->gd_fleet_S)) +
-                     " entries of the list: n_world must lie in 0.." + std::to_string(GUIDANCE_LMAX - fleet_slots(h->gd_fleet_S));
-            return USVMPC_E_ARG;
-        }
-        rc = world_relayout(h, &W.world, &h->gd_rworld_cap, &h->gd_wvel, &h->gd_wvel_cap, h->gd_moving, W.nworld, fleet_slots(h->gd_fleet_S), world,
-                            n_world, fleet_slots(h->gd_fleet_S));
-        if (rc) return rc;
-        W.nworld = n_world + fleet_slots(h->gd_fleet_S);
-        h->gd_nfixed = n_world;
-        W.max_radius = max_radius;
-        return 0;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a tick that reads the old list may be in flight)
-    if (need > h->gd_rworld_cap) {
-        dev_free(h, const_cast<double *>(W.world), h->gd_rworld_cap * sizeof(double));
-        W.world = nullptr; h->gd_rworld_cap = 0;
-        double *d = nullptr;
-        if (dev_alloc(h, &d, need, false)) return USVMPC_E_HIP;
-        W.world = d;
-        h->gd_rworld_cap = need;
-    }
-    if (!W.trk_pv && (dev_alloc(h, &W.trk_pv, (size_t)h->B * (size_t)(h->K ? h->K : 1) * 4, true) ||
-                      dev_alloc(h, &W.trk_lh, (size_t)h->B * (size_t)(h->K ? h->K : 1), true)))
-        return USVMPC_E_HIP;
-    if (need) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(W.world), world, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const bool same = h->gd_world_set && W.nworld == n_world;
-    W.nworld = n_world;
-    W.max_radius = max_radius;
-    h->gd_world_set = true;
-    if (h->gd_moving && !same) { // (velocities belong to a list: another n_world is at rest until its own are given)
-        h->gd_moving = false;
-        return gd_apply_static(h);
-    }
-    return 0;
-}
-
-int usvmpc_guidance_world_vel(usvmpc_handle *h, const double *vel, int predict)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = gd_check(h, "guidance_world_vel");
-    if (rc) return rc;
-    if (!vel) { // back to a world at rest
-        if (h->gd_fleet_S) { h->err = "guidance_world_vel: a fleet is on and its world moves; switch it off first (usvmpc_guidance_fleet with scene_size 0)"; return USVMPC_E_ARG; }
-        h->gd_moving = false;
-        return gd_apply_static(h);
-    }
-    if (!h->gd_world_set) { h->err = "guidance_world_vel: no world list yet (usvmpc_guidance_world first)"; return USVMPC_E_ARG; }
-    if (h->opt.tracks_on) { h->err = "guidance_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
-    const int nvel = h->gd_fleet_S ? h->gd_nfixed : h->gd_tickp.nworld; // (a fleet's slots have the velocities the gather gave them)
-    const size_t need = (size_t)h->B * (size_t)nvel * 2;
-    for (size_t i = 0; i < need; i++)
-        if (vel[i] - vel[i] != 0.0) { h->err = "guidance_world_vel: entry " + std::to_string(i) + " is not finite"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a tick or a world step that reads the old velocities may be in flight)
-    if (h->gd_fleet_S) { // [B][n_fixed][2] into the head of every instance's [nworld][2]
-        const size_t row = (size_t)h->gd_tickp.nworld * 2, head = (size_t)nvel * 2;
-        std::vector<double> v(h->B * row);
-        HIP_TRY(h, hipMemcpyAsync(v.data(), h->gd_wvel, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (size_t b = 0; b < (size_t)h->B; b++) std::copy(vel + b * head, vel + (b + 1) * head, v.begin() + (long)(b * row));
-        HIP_TRY(h, hipMemcpyAsync(h->gd_wvel, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->gd_predict = predict != 0;
-        return gd_apply_static(h);
-    }
-    if (need > h->gd_wvel_cap || !h->gd_wvel) { // (an empty list moves too: a non-null pointer is what tells the tick so)
-        dev_free(h, h->gd_wvel, h->gd_wvel_cap * sizeof(double));
-        h->gd_wvel = nullptr; h->gd_wvel_cap = 0;
-        if (dev_alloc(h, &h->gd_wvel, need, false)) return USVMPC_E_HIP;
-        h->gd_wvel_cap = need;
-    }
-    if (need) HIP_TRY(h, hipMemcpyAsync(h->gd_wvel, vel, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->gd_moving = true;
-    h->gd_predict = predict != 0;
-    return gd_apply_static(h);
-}
-
-int usvmpc_guidance_world_step(usvmpc_handle *h, double T)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = gd_check(h, "guidance_world_step");
-    if (rc) return rc;
-    if (!h->gd_moving) { h->err = "guidance_world_step: the world is at rest (usvmpc_guidance_world_vel first)"; return USVMPC_E_ARG; }
-    if (T - T != 0.0) { h->err = "guidance_world_step: T is not finite"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const long n = (long)h->B * h->gd_tickp.nworld;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(usv_pf_world_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, const_cast<double *>(h->gd_tickp.world),
-                       (const double *)h->gd_wvel, n, T); // (one kernel for both front ends' worlds: pos += T vel per entry, track_step)
-    HIP_TRY(h, hipGetLastError());
-    return 0;
-}
-
-int usvmpc_guidance_world_read(usvmpc_handle *h, double *world, double *vel)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = gd_check(h, "guidance_world_read");
-    if (rc) return rc;
-    if (!h->gd_world_set) { h->err = "guidance_world_read: no world list yet (usvmpc_guidance_world first)"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)h->B * (size_t)h->gd_tickp.nworld;
-    if (world && n) HIP_TRY(h, hipMemcpyAsync(world, h->gd_tickp.world, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (vel && n && h->gd_moving) HIP_TRY(h, hipMemcpyAsync(vel, h->gd_wvel, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (vel && !h->gd_moving) std::fill(vel, vel + n * 2, 0.0); // (a world at rest)
     return 0;
 }
 
@@ -3732,85 +3735,11 @@ int usvmpc_guidance_mission_state(usvmpc_handle *h, int *wp_index, float *past_p
     return 0;
 }
 
-int usvmpc_guidance_fleet(usvmpc_handle *h, int scene_size, double radius)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = gd_check(h, "guidance_fleet");
-    if (rc) return rc;
-    if (!h->gd_world_set) { h->err = "guidance_fleet: no world list yet (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
-    if (scene_size < 0) { h->err = "guidance_fleet: scene_size must not be negative"; return USVMPC_E_ARG; }
-    CaTickPtrs &W = h->gd_tickp;
-    if (!fleet_on(scene_size)) { // off: the list is cut back to the fixed entries, which keep their velocities
-        if (!h->gd_fleet_S) return 0;
-        rc = world_relayout(h, &W.world, &h->gd_rworld_cap, &h->gd_wvel, &h->gd_wvel_cap, h->gd_moving, W.nworld, fleet_slots(h->gd_fleet_S), nullptr,
-                            h->gd_nfixed, 0);
-        if (rc) return rc;
-        W.nworld = h->gd_nfixed;
-        h->gd_fleet_S = 0;
-        return 0;
-    }
-    const int n_fixed = h->gd_fleet_S ? h->gd_nfixed : W.nworld;
-    if (h->opt.tracks_on) { h->err = "guidance_fleet: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
-    if (!fleet_scene_ok(h->B, scene_size)) {
-        h->err = "guidance_fleet: the batch of " + std::to_string(h->B) + " is not a whole number of scenes of " + std::to_string(scene_size);
-        return USVMPC_E_ARG;
-    }
-    if (!fleet_fits(n_fixed, scene_size)) {
-        h->err = "guidance_fleet: " + std::to_string(n_fixed) + " fixed entries and " + std::to_string(scene_size - 1) + " fleet entries exceed the " +
-                 std::to_string(GUIDANCE_LMAX) + " of a world list";
-        return USVMPC_E_ARG;
-    }
-    if (!fleet_radius_ok(radius)) { h->err = "guidance_fleet: radius must be finite and not negative"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->gd_min_sep) {
-        if (dev_alloc(h, &h->gd_min_sep, h->B, true) || dev_alloc(h, &h->gd_sep_tick, h->B, true)) return USVMPC_E_HIP;
-        hipLaunchKernelGGL(usv_guidance_fleet_reset, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->gd_min_sep, h->gd_sep_tick,
-                           (int)h->B);
-        HIP_TRY(h, hipGetLastError());
-    }
-    rc = world_relayout(h, &W.world, &h->gd_rworld_cap, &h->gd_wvel, &h->gd_wvel_cap, h->gd_moving, W.nworld, fleet_slots(h->gd_fleet_S), nullptr,
-                        n_fixed, scene_size - 1);
-    if (rc) return rc;
-    W.nworld = n_fixed + scene_size - 1;
-    if (!h->gd_moving) h->gd_predict = true; // (a world at rest had no say in it; usvmpc_guidance_world_vel changes it)
-    h->gd_fleet_S = scene_size;
-    h->gd_nfixed = n_fixed;
-    h->gd_fleet_radius = radius;
-    h->gd_moving = true;
-    return gd_apply_static(h);
-}
-
-int usvmpc_guidance_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = gd_check(h, "guidance_fleet_state");
-    if (rc) return rc;
-    const size_t B = h->B;
-    if (!h->gd_min_sep) { // no fleet yet: as after a reset
-        if (min_separation) std::fill(min_separation, min_separation + B, 1e300);
-        if (separation_tick) std::fill(separation_tick, separation_tick + B, -1);
-        return 0;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (min_separation) HIP_TRY(h, hipMemcpyAsync(min_separation, h->gd_min_sep, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (separation_tick) HIP_TRY(h, hipMemcpyAsync(separation_tick, h->gd_sep_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-
 // ---- path-following front end (usv_model_pf_ca only): see pf_guidance.hpp
 static int pf_check(usvmpc_handle *h)
 {
     if (h->desc.model != USVMPC_MODEL_PF_CA) { h->err = "the path-following front end (usvmpc_pf_*) belongs to usv_model_pf_ca"; return USVMPC_E_ARG; }
     return 0;
-}
-
-// "static_obstacles" as the front end needs it: off only while the world moves AND is predicted per stage (prepare then writes all stages)
-static int pf_apply_static(usvmpc_handle *h)
-{
-    const bool want = !(h->pf_moving && h->opt.pf_predict);
-    if ((h->spec.p_static != 0) == want) return 0;
-    return apply_option(h, OPT_STATIC_OBSTACLES, want ? 1.0 : 0.0);
 }
 
 static int pf_alloc(usvmpc_handle *h)
@@ -3824,11 +3753,20 @@ static int pf_alloc(usvmpc_handle *h)
         dev_alloc(h, &F.yref_writes, 1, true) || dev_alloc(h, &F.thr_port, B, true) || dev_alloc(h, &F.thr_stbd, B, true) ||
         dev_alloc(h, &F.Tx, B, true) || dev_alloc(h, &F.Tz, B, true) || dev_alloc(h, &F.speed, B, true) || dev_alloc(h, &F.e_u, B, true) ||
         dev_alloc(h, &F.e_ye, B, true) || dev_alloc(h, &F.active, B, true) || dev_alloc(h, &h->pf_vel, B * 3, true) ||
-        dev_alloc(h, &h->pf_pose, B * 3, true) || dev_alloc(h, &F.min_sep, B, true) || dev_alloc(h, &F.sep_tick, B, true))
+        dev_alloc(h, &h->pf_pose, B * 3, true) || dev_alloc(h, &h->wb.min_sep, B, true) || dev_alloc(h, &h->wb.sep_tick, B, true))
         return USVMPC_E_HIP;
-    F.max_radius = 100.0;
     h->pf_alloc = true;
     return 0;
+}
+
+// the front end's kernel arguments: its own buffers and the handle's world (wvel: null, a world at rest, unless the caller says otherwise)
+static PfPtrs pf_args(const usvmpc_handle *h)
+{
+    PfPtrs F = h->pf;
+    F.world = h->wb.list; F.nworld = h->world.nworld(); F.max_radius = h->world.max_radius();
+    F.trk_pv = h->wb.trk_pv; F.trk_lh = h->wb.trk_lh;
+    F.min_sep = h->wb.min_sep; F.sep_tick = h->wb.sep_tick;
+    return F;
 }
 
 int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
@@ -3852,154 +3790,11 @@ int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
     }
     F.npts = npts;
     HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.wp), waypoints, B * 2 * (size_t)npts * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(usv_pf_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, F, (int)B);
+    hipLaunchKernelGGL(usv_pf_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, pf_args(h), (int)B);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->pf_ready = true; h->pf_stale = true; h->pf_tick = 0;
-    return pf_apply_static(h);
-}
-
-// the [B][K] slot tracks a moving prepare leaves between its two steps
-static int pf_alloc_tracks(usvmpc_handle *h)
-{
-    PfPtrs &F = h->pf;
-    if (!F.trk_pv && (dev_alloc(h, &F.trk_pv, (size_t)h->B * (size_t)(h->K ? h->K : 1) * 4, true) ||
-                      dev_alloc(h, &F.trk_lh, (size_t)h->B * (size_t)(h->K ? h->K : 1), true)))
-        return USVMPC_E_HIP;
-    return 0;
-}
-
-// Vessel encounters: the world list laid out anew - n1_fixed fixed entries, f1 fleet slots behind them (fleet_world.hpp: fleet_relayout, which
-// says what is kept) - through the host: a set-up call, never part of a tick.  fixed: the new fixed entries [B][n1_fixed][3]; null keeps the
-// present ones (n1_fixed is then their count).  Afterwards the list has velocities, whether the world moved before or not.
-static int pf_relayout(usvmpc_handle *h, const double *fixed, int n1_fixed, int f1)
-{
-    PfPtrs &F = h->pf;
-    const int rc = world_relayout(h, &F.world, &h->pf_world_cap, &h->pf_wvel, &h->pf_wvel_cap, h->pf_moving, F.nworld, fleet_slots(h->pf_fleet_S),
-                                  fixed, n1_fixed, f1);
-    if (rc) return rc;
-    if (pf_alloc_tracks(h)) return USVMPC_E_HIP;
-    F.nworld = n1_fixed + f1;
-    return 0;
-}
-
-int usvmpc_pf_world(usvmpc_handle *h, const double *world, int n_world, double max_radius)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = pf_check(h);
-    if (rc) return rc;
-    if (n_world < 0 || n_world > PF_LMAX) { h->err = "pf_world: n_world must lie in 0.." + std::to_string(PF_LMAX); return USVMPC_E_ARG; }
-    if (n_world > 0 && !world) { h->err = "pf_world: null world list"; return USVMPC_E_ARG; }
-    if (!(max_radius == max_radius)) { h->err = "pf_world: max_radius is NaN"; return USVMPC_E_ARG; }
-    if (h->pf_fleet_S) { // (the fixed entries only; the fleet slots stay)
-        if (!fleet_fits(n_world, h->pf_fleet_S)) {
-            h->err = "pf_world: a fleet is on and owns " + std::to_string(fleet_slots(h->pf_fleet_S)) + " entries of the list: n_world must lie in 0.." +
-                     std::to_string(PF_LMAX - fleet_slots(h->pf_fleet_S));
-            return USVMPC_E_ARG;
-        }
-        rc = pf_relayout(h, world, n_world, fleet_slots(h->pf_fleet_S));
-        if (rc) return rc;
-        h->pf_nfixed = n_world;
-        h->pf.max_radius = max_radius;
-        return 0;
-    }
-    rc = pf_alloc(h);
-    if (rc) return rc;
-    PfPtrs &F = h->pf;
-    const size_t need = (size_t)h->B * (size_t)n_world * 3;
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare that reads the old list may be in flight)
-    if (need > h->pf_world_cap) {
-        dev_free(h, const_cast<double *>(F.world), h->pf_world_cap * sizeof(double));
-        F.world = nullptr; h->pf_world_cap = 0;
-        double *d = nullptr;
-        if (dev_alloc(h, &d, need, false)) return USVMPC_E_HIP;
-        F.world = d;
-        h->pf_world_cap = need;
-    }
-    if (need) HIP_TRY(h, hipMemcpyAsync(const_cast<double *>(F.world), world, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const bool same = h->pf_world_set && F.nworld == n_world;
-    F.nworld = n_world;
-    F.max_radius = max_radius;
-    h->pf_world_set = true;
-    if (h->pf_moving && !same) { // (velocities belong to a list: another n_world is at rest until its own are given)
-        h->pf_moving = false;
-        return h->pf_ready ? pf_apply_static(h) : 0;
-    }
-    return 0;
-}
-
-int usvmpc_pf_world_vel(usvmpc_handle *h, const double *vel)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = pf_check(h);
-    if (rc) return rc;
-    if (!vel) { // back to a world at rest
-        if (h->pf_fleet_S) { h->err = "pf_world_vel: a fleet is on and its world moves; switch it off first (usvmpc_pf_fleet with scene_size 0)"; return USVMPC_E_ARG; }
-        h->pf_moving = false;
-        return h->pf_ready ? pf_apply_static(h) : 0;
-    }
-    if (!h->pf_world_set) { h->err = "pf_world_vel: no world list yet (usvmpc_pf_world first)"; return USVMPC_E_ARG; }
-    if (h->opt.tracks_on) { h->err = "pf_world_vel: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
-    PfPtrs &F = h->pf;
-    const int nvel = h->pf_fleet_S ? h->pf_nfixed : F.nworld; // (a fleet's slots have the velocities the gather gave them)
-    const size_t need = (size_t)h->B * (size_t)nvel * 2;
-    for (size_t i = 0; i < need; i++)
-        if (vel[i] - vel[i] != 0.0) { h->err = "pf_world_vel: entry " + std::to_string(i) + " is not finite"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a prepare or a world step that reads the old velocities may be in flight)
-    if (h->pf_fleet_S) { // [B][n_fixed][2] into the head of every instance's [nworld][2]
-        const size_t row = (size_t)F.nworld * 2, head = (size_t)nvel * 2;
-        std::vector<double> v(h->B * row);
-        HIP_TRY(h, hipMemcpyAsync(v.data(), h->pf_wvel, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (size_t b = 0; b < (size_t)h->B; b++) std::copy(vel + b * head, vel + (b + 1) * head, v.begin() + (long)(b * row));
-        HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return 0;
-    }
-    if (need > h->pf_wvel_cap || !h->pf_wvel) { // (an empty list moves too: a non-null pointer is what tells prepare so)
-        dev_free(h, h->pf_wvel, h->pf_wvel_cap * sizeof(double));
-        h->pf_wvel = nullptr; h->pf_wvel_cap = 0;
-        if (dev_alloc(h, &h->pf_wvel, need, false)) return USVMPC_E_HIP;
-        h->pf_wvel_cap = need;
-    }
-    if (pf_alloc_tracks(h)) return USVMPC_E_HIP;
-    if (need) HIP_TRY(h, hipMemcpyAsync(h->pf_wvel, vel, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->pf_moving = true;
-    return h->pf_ready ? pf_apply_static(h) : 0;
-}
-
-int usvmpc_pf_world_step(usvmpc_handle *h, double T)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = pf_check(h);
-    if (rc) return rc;
-    if (!h->pf_moving) { h->err = "pf_world_step: the world is at rest (usvmpc_pf_world_vel first)"; return USVMPC_E_ARG; }
-    if (T - T != 0.0) { h->err = "pf_world_step: T is not finite"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const long n = (long)h->B * h->pf.nworld;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(usv_pf_world_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, const_cast<double *>(h->pf.world),
-                       (const double *)h->pf_wvel, n, T);
-    HIP_TRY(h, hipGetLastError());
-    return 0;
-}
-
-int usvmpc_pf_world_read(usvmpc_handle *h, double *world, double *vel)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = pf_check(h);
-    if (rc) return rc;
-    if (!h->pf_world_set) { h->err = "pf_world_read: no world list yet (usvmpc_pf_world first)"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)h->B * (size_t)h->pf.nworld;
-    if (world && n) HIP_TRY(h, hipMemcpyAsync(world, h->pf.world, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (vel && n && h->pf_moving) HIP_TRY(h, hipMemcpyAsync(vel, h->pf_wvel, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (vel && !h->pf_moving) std::fill(vel, vel + n * 2, 0.0); // (a world at rest)
-    return 0;
+    return apply_static(h);
 }
 
 int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pose)
@@ -4009,7 +3804,8 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     if (rc) return rc;
     if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
     if ((vel_uvr == nullptr) != (pose == nullptr)) { h->err = "pf_prepare: give both vel_uvr and pose, or neither (device-resident)"; return USVMPC_E_ARG; }
-    if (vel_uvr && h->pf_fleet_S) {
+    const WorldPlan &w = h->world;
+    if (vel_uvr && w.fleet_S()) {
         h->err = "pf_prepare: a fleet is on and its scene exists on the device only; prepare device-resident (both NULL)";
         return USVMPC_E_ARG;
     }
@@ -4018,15 +3814,15 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     if (rc) return rc;
     rc = spec_cancel(h); // (a caller write of yref as far as the pipelined lineariser is concerned: pf_guidance.hpp)
     if (rc) return rc;
-    if (h->pf_fleet_S) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_pf_prepare rewrites x0[1..3]
-        const long n = (long)h->B * fleet_slots(h->pf_fleet_S);
-        hipLaunchKernelGGL(usv_pf_fleet_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs.x0, const_cast<double *>(h->pf.world),
-                           h->pf_wvel, h->pf.min_sep, h->pf.sep_tick, (long)h->B, h->pf_fleet_S, h->pf_nfixed, h->pf_fleet_radius, h->pf_tick);
+    if (w.fleet_S()) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_pf_prepare rewrites x0[1..3]
+        const long n = (long)h->B * fleet_slots(w.fleet_S());
+        hipLaunchKernelGGL(usv_pf_fleet_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs.x0, h->wb.list, h->wb.vel,
+                           h->wb.min_sep, h->wb.sep_tick, (long)h->B, w.fleet_S(), w.nfixed(), w.fleet_radius(), h->pf_tick);
         HIP_TRY(h, hipGetLastError());
     }
-    PfPtrs F = h->pf;
+    PfPtrs F = pf_args(h);
     F.margin = h->opt.pf_margin;
-    F.wvel = (h->pf_moving && h->opt.pf_predict) ? h->pf_wvel : nullptr; // (held still inside the horizon: the prepare of a world at rest)
+    F.wvel = w.want_static(WORLD_PF, h->opt.pf_predict != 0) ? nullptr : h->wb.vel; // (held still inside the horizon: the prepare of a world at rest)
     const size_t B = h->B;
     if (vel_uvr) {
         HIP_TRY(h, hipMemcpyAsync(h->pf_vel, vel_uvr, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4051,7 +3847,7 @@ int usvmpc_pf_publish(usvmpc_handle *h, double *thr_port, double *thr_stbd, doub
     if (rc) return rc;
     if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
     HIP_TRY(h, hipSetDevice(h->device));
-    const PfPtrs &F = h->pf;
+    const PfPtrs F = pf_args(h);
     const size_t B = h->B;
     hipLaunchKernelGGL(usv_pf_publish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, F);
     HIP_TRY(h, hipGetLastError());
@@ -4080,58 +3876,6 @@ int usvmpc_pf_state(usvmpc_handle *h, int *wp_index, int *finish_tick, double *m
     if (finish_tick) HIP_TRY(h, hipMemcpyAsync(finish_tick, F.finish_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (min_clearance) HIP_TRY(h, hipMemcpyAsync(min_clearance, F.min_clear, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (yref_writes) HIP_TRY(h, hipMemcpyAsync(yref_writes, F.yref_writes, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-int usvmpc_pf_fleet(usvmpc_handle *h, int scene_size, double radius)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = pf_check(h);
-    if (rc) return rc;
-    if (!h->pf_ready || !h->pf_world_set) {
-        h->err = "pf_fleet: usvmpc_pf_reset and a world list (usvmpc_pf_world; an empty one will do) come first";
-        return USVMPC_E_ARG;
-    }
-    if (scene_size < 0) { h->err = "pf_fleet: scene_size must not be negative"; return USVMPC_E_ARG; }
-    if (!fleet_on(scene_size)) { // off: the list is cut back to the fixed entries, which keep their velocities
-        if (!h->pf_fleet_S) return 0;
-        rc = pf_relayout(h, nullptr, h->pf_nfixed, 0);
-        if (rc) return rc;
-        h->pf_fleet_S = 0;
-        return 0;
-    }
-    const int n_fixed = h->pf_fleet_S ? h->pf_nfixed : h->pf.nworld;
-    if (h->opt.tracks_on) { h->err = "pf_fleet: option \"obstacle_tracks\" is on and the tracks own p; switch it off first"; return USVMPC_E_ARG; }
-    if (!fleet_scene_ok(h->B, scene_size)) {
-        h->err = "pf_fleet: the batch of " + std::to_string(h->B) + " is not a whole number of scenes of " + std::to_string(scene_size);
-        return USVMPC_E_ARG;
-    }
-    if (!fleet_fits(n_fixed, scene_size)) {
-        h->err = "pf_fleet: " + std::to_string(n_fixed) + " fixed entries and " + std::to_string(scene_size - 1) + " fleet entries exceed the " +
-                 std::to_string(PF_LMAX) + " of a world list";
-        return USVMPC_E_ARG;
-    }
-    if (!fleet_radius_ok(radius)) { h->err = "pf_fleet: radius must be finite and not negative"; return USVMPC_E_ARG; }
-    rc = pf_relayout(h, nullptr, n_fixed, scene_size - 1);
-    if (rc) return rc;
-    h->pf_fleet_S = scene_size;
-    h->pf_nfixed = n_fixed;
-    h->pf_fleet_radius = radius;
-    h->pf_moving = true;
-    return pf_apply_static(h);
-}
-
-int usvmpc_pf_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick)
-{
-    if (!h) return USVMPC_E_ARG;
-    int rc = pf_check(h);
-    if (rc) return rc;
-    if (!h->pf_ready) { h->err = "usvmpc_pf_reset must be called first"; return USVMPC_E_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t B = h->B;
-    if (min_separation) HIP_TRY(h, hipMemcpyAsync(min_separation, h->pf.min_sep, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (separation_tick) HIP_TRY(h, hipMemcpyAsync(separation_tick, h->pf.sep_tick, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -4239,7 +3983,7 @@ int usvmpc_cascade_create(usvmpc_handle *guidance, int ratio, double T, int num_
     usvmpc_handle *h = guidance;
     if (h->desc.model != USVMPC_MODEL_GUIDANCE_CA1) { err = "usvmpc_cascade_create: the upper layer must be a usv_model_guidance_ca1 handle"; return USVMPC_E_ARG; }
     if (!h->gd_ready || h->gd.npts < 2) { err = "usvmpc_cascade_create: usvmpc_guidance_reset must be called first"; return USVMPC_E_ARG; }
-    if (!h->gd_world_set) { err = "usvmpc_cascade_create: the guidance handle needs a world list (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
+    if (!h->world.exists()) { err = "usvmpc_cascade_create: the guidance handle needs a world list (usvmpc_guidance_world first; an empty one will do)"; return USVMPC_E_ARG; }
     if (T - T != 0.0 || c - c != 0.0) { err = "usvmpc_cascade_create: T and c must be finite"; return USVMPC_E_ARG; }
     if (ratio < 1 || num_steps < 1 || !(T > 0.0) || instance_offset < 0) { err = "usvmpc_cascade_create: ratio >= 1, num_steps >= 1, T > 0 and instance_offset >= 0 are needed"; return USVMPC_E_ARG; }
     if (fabs((double)ratio * T - h->spec.dt) > 1e-9 * h->spec.dt) {
@@ -4337,7 +4081,7 @@ int usvmpc_cascade_step(usvmpc_cascade *c, double sigma, unsigned long long seed
     CAS_TRY(c, hipGetLastError());
     c->tick++;
     // a guidance period has passed: the guidance layer's moving world follows, as usvmpc_advance would have moved it
-    if (hand_over && h->gd_moving && h->opt.step_on_advance && usvmpc_guidance_world_step(h, (double)c->ratio * c->T)) {
+    if (hand_over && h->world.steps_on_advance(h->opt.step_on_advance != 0) && world_step(h, (double)c->ratio * c->T)) {
         c->err = "cascade_step: " + h->err;
         return USVMPC_E_HIP;
     }

@@ -13,7 +13,66 @@ import numpy as np
 from . import _capi
 
 
-class GuidanceFrontEnd:
+class _ResidentWorld:
+    """What the two front ends share: the world list that lives on the device (csrc/world_plan.hpp holds its rules for both).  A subclass
+    names its C symbols - usvmpc_<_prefix>_world, _world_vel, _world_step, _world_read, _fleet, _fleet_state - and keeps its own set_world,
+    whose arguments differ.  Attributes: s (the solver), B, _lib; _L (fixed entries of the list, once set) and _S (scene size, a fleet on)."""
+    _prefix = None
+
+    def _world_call(self, name, *args):
+        self.s._check(getattr(self._lib, "usvmpc_%s_%s" % (self._prefix, name))(self.s._h, *args))
+
+    def _world_arrays(self, world, vel):
+        """set_world's arrays, checked: (world [B, L, 3], vel [B, L, 2] or None); a fleet's world moves, so vel None is zeros then"""
+        S = getattr(self, "_S", 0)
+        w = _as_world(world, self.B, 64 - (S - 1 if S else 0))
+        v = None if vel is None else _as_world_vel(vel, self.B, w.shape[1])
+        if S and v is None:
+            v = np.zeros((self.B, w.shape[1], 2))
+        return w, v
+
+    def _upload_world(self, w, v, max_radius, *vel_args):
+        self._world_call("world", w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius))
+        self._world_call("world_vel", None if v is None else v.ctypes.data_as(_capi._dp), *vel_args)
+        self._L = w.shape[1]
+
+    def set_fleet(self, scene_size, radius=0.5):
+        """Vessel encounters: the batch is cut into scenes of scene_size = S consecutive instances, and every instance sees the other
+        S - 1 vessels of its scene - position, hull radius `radius`, velocity from the state the plant left in x0 (the guidance model: (u, v)
+        turned by psi) - as moving world entries behind its fixed ones (set_world), refreshed on the device by every device-resident
+        prepare().  B % S == 0; after reset() and set_world() (an empty world will do).  GuidanceFrontEnd: over a world at rest the scene is
+        predicted per stage; a set_world(..., predict=False) AFTER this call holds it still inside the horizon.  scene_size 0 or 1: off, the
+        world list is the fixed entries again."""
+        self._world_call("fleet", int(scene_size), float(radius))
+        self._S = int(scene_size) if int(scene_size) >= 2 else 0
+
+    def fleet_state(self):
+        """dict(min_separation [B] (smallest distance to a vessel of the instance's scene, any tick; 1e300 before the first),
+        separation_tick [B] (the prepare it was met at; -1: none yet))."""
+        ms, st = np.zeros(self.B), np.zeros(self.B, dtype=np.int32)
+        self._world_call("fleet_state", ms.ctypes.data_as(_capi._dp), st.ctypes.data_as(_capi._ip))
+        return dict(min_separation=ms, separation_tick=st)
+
+    def step_world(self, T):
+        """The world moves on by T seconds (enqueued; a moving world only)."""
+        self._world_call("world_step", float(T))
+
+    def world(self):
+        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest.  While a fleet is on L counts the
+        fixed entries and the S - 1 fleet entries behind them."""
+        L = getattr(self, "_L", None)
+        if L is None:
+            raise Exception("world: no world list yet (set_world first)")
+        S = getattr(self, "_S", 0)
+        L += S - 1 if S else 0
+        w, v = np.zeros((self.B, L, 3)), np.zeros((self.B, L, 2))
+        self._world_call("world_read", w.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp))
+        return w, v
+
+
+class GuidanceFrontEnd(_ResidentWorld):
+    _prefix = "guidance"
+
     def __init__(self, solver):
         if solver.ocp.model.name != "usv_model_guidance_ca1":
             raise Exception("the guidance front end belongs to usv_model_guidance_ca1")
@@ -55,46 +114,7 @@ class GuidanceFrontEnd:
         world still inside the horizon (stage 0 only).  None: a world at rest.
         While a fleet is on (set_fleet) these are the FIXED entries, L <= 64 - (S - 1): the fleet's slots stay behind them, and vel None
         gives the fixed entries zero velocities (the scene's world moves)."""
-        S = getattr(self, "_S", 0)
-        w = _as_world(world, self.B, 64 - (S - 1 if S else 0))
-        v = None if vel is None else _as_world_vel(vel, self.B, w.shape[1])
-        if S and v is None:
-            v = np.zeros((self.B, w.shape[1], 2))
-        self.s._check(self._lib.usvmpc_guidance_world(self.s._h, w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius)))
-        self.s._check(self._lib.usvmpc_guidance_world_vel(self.s._h, None if v is None else v.ctypes.data_as(_capi._dp), 1 if predict else 0))
-        self._L = w.shape[1]
-
-    def set_fleet(self, scene_size, radius=0.5):
-        """Vessel encounters: the batch is cut into scenes of scene_size = S consecutive instances, and every instance sees the other
-        S - 1 vessels of its scene - position, hull radius `radius`, velocity (u, v) turned by psi, from the state the plant left in x0 -
-        as moving world entries behind its fixed ones (set_world), refreshed on the device by every device-resident prepare().  B % S == 0;
-        after reset() and set_world() (an empty world will do).  Over a world at rest the scene is predicted per stage; a set_world(...,
-        predict=False) AFTER this call holds it still inside the horizon.  scene_size 0 or 1: off, the world list is the fixed entries again."""
-        self.s._check(self._lib.usvmpc_guidance_fleet(self.s._h, int(scene_size), float(radius)))
-        self._S = int(scene_size) if int(scene_size) >= 2 else 0
-
-    def fleet_state(self):
-        """dict(min_separation [B] (smallest distance to a vessel of the instance's scene, any tick; 1e300 before the first),
-        separation_tick [B] (the prepare it was met at; -1: none yet))."""
-        ms, st = np.zeros(self.B), np.zeros(self.B, dtype=np.int32)
-        self.s._check(self._lib.usvmpc_guidance_fleet_state(self.s._h, ms.ctypes.data_as(_capi._dp), st.ctypes.data_as(_capi._ip)))
-        return dict(min_separation=ms, separation_tick=st)
-
-    def step_world(self, T):
-        """The world moves on by T seconds (enqueued; a moving world only)."""
-        self.s._check(self._lib.usvmpc_guidance_world_step(self.s._h, float(T)))
-
-    def world(self):
-        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest.  While a fleet is on L counts the
-        fixed entries and the S - 1 fleet entries behind them."""
-        L = getattr(self, "_L", None)
-        if L is None:
-            raise Exception("world: no world list yet (set_world first)")
-        S = getattr(self, "_S", 0)
-        L += S - 1 if S else 0
-        w, v = np.zeros((self.B, L, 3)), np.zeros((self.B, L, 2))
-        self.s._check(self._lib.usvmpc_guidance_world_read(self.s._h, w.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp)))
-        return w, v
+        self._upload_world(*self._world_arrays(world, vel), max_radius, 1 if predict else 0)
 
     def prepare(self, vel_uv=None, pose=None, obstacles=None, n_obstacles=None):
         """vel_uv [B,2], pose [B,3] (nedx, nedy, psi), obstacles [B,L,3] body (x, y, R), n_obstacles [B];
@@ -202,7 +222,7 @@ def _as_world_vel(vel, B, L):
     return np.ascontiguousarray(v)
 
 
-class PathFollowingFrontEnd:
+class PathFollowingFrontEnd(_ResidentWorld):
     """Batched counterpart of the reference's path-following ROS node around the solver (class NMPC,
     catkin_ws/src/nmpc_ca/src/nmpc_pf.cpp = nmpc_pf_ca.cpp) for usv_model_pf_ca: waypoint manager, x0 and reference assembly, nearest-K
     obstacle selection, published thrusts.  The arithmetic runs on the device (csrc/pf_guidance.hpp).  Two ways to drive it:
@@ -211,6 +231,8 @@ class PathFollowingFrontEnd:
         device-resident   prepare() -> solve_async -> publish(fetch=False) -> advance / advance_sim
                           the vessel's state is read from the solver's own x0; no host array, no synchronisation
     """
+
+    _prefix = "pf"
 
     def __init__(self, solver):
         if solver.ocp.model.name != "usv_model_pf_ca" or getattr(solver, "generated", False):
@@ -230,47 +252,10 @@ class PathFollowingFrontEnd:
         advance / advance_sim move the world along (option "obstacle_step_on_advance").  None: a world at rest.
         While a fleet is on (set_fleet) these are the FIXED entries, L <= 64 - (S - 1): the fleet's slots stay behind them, and vel None
         gives the fixed entries zero velocities (the scene's world moves)."""
-        S = getattr(self, "_S", 0)
-        w = _as_world(world, self.B, 64 - (S - 1 if S else 0))
-        v = None if vel is None else _as_world_vel(vel, self.B, w.shape[1])
-        if S and v is None:
-            v = np.zeros((self.B, w.shape[1], 2))
+        w, v = self._world_arrays(world, vel)
         if margin is not None:
             self.s.set_option("pf_lh_margin", float(margin))
-        self.s._check(self._lib.usvmpc_pf_world(self.s._h, w.ctypes.data_as(_capi._dp) if w.size else None, w.shape[1], float(max_radius)))
-        self.s._check(self._lib.usvmpc_pf_world_vel(self.s._h, None if v is None else v.ctypes.data_as(_capi._dp)))
-        self._L = w.shape[1]
-
-    def set_fleet(self, scene_size, radius=0.5):
-        """Vessel encounters: the batch is cut into scenes of scene_size = S consecutive instances, and every instance sees the other
-        S - 1 vessels of its scene - position, hull radius `radius`, velocity from the state the plant left in x0 - as moving world
-        entries behind its fixed ones (set_world), refreshed on the device by every device-resident prepare().  B % S == 0; after reset()
-        and set_world() (an empty world will do).  scene_size 0 or 1: off, the world list is the fixed entries again."""
-        self.s._check(self._lib.usvmpc_pf_fleet(self.s._h, int(scene_size), float(radius)))
-        self._S = int(scene_size) if int(scene_size) >= 2 else 0
-
-    def fleet_state(self):
-        """dict(min_separation [B] (smallest distance to a vessel of the instance's scene, any tick; 1e300 before the first),
-        separation_tick [B] (the prepare it was met at; -1: none yet))."""
-        ms, st = np.zeros(self.B), np.zeros(self.B, dtype=np.int32)
-        self.s._check(self._lib.usvmpc_pf_fleet_state(self.s._h, ms.ctypes.data_as(_capi._dp), st.ctypes.data_as(_capi._ip)))
-        return dict(min_separation=ms, separation_tick=st)
-
-    def step_world(self, T):
-        """The world moves on by T seconds (enqueued; a moving world only)."""
-        self.s._check(self._lib.usvmpc_pf_world_step(self.s._h, float(T)))
-
-    def world(self):
-        """(world [B, L, 3], vel [B, L, 2]) as the device holds them; vel is zero for a world at rest.  While a fleet is on L counts the
-        fixed entries and the S - 1 fleet entries behind them."""
-        L = getattr(self, "_L", None)
-        if L is None:
-            raise Exception("world: no world list yet (set_world first)")
-        S = getattr(self, "_S", 0)
-        L += S - 1 if S else 0
-        w, v = np.zeros((self.B, L, 3)), np.zeros((self.B, L, 2))
-        self.s._check(self._lib.usvmpc_pf_world_read(self.s._h, w.ctypes.data_as(_capi._dp), v.ctypes.data_as(_capi._dp)))
-        return w, v
+        self._upload_world(w, v, max_radius)
 
     def prepare(self, vel_uvr=None, pose=None):
         """vel_uvr [B,3] = (u, v, r), pose [B,3] = (nedx, nedy, psi); both None: device-resident (enqueues and returns)."""

@@ -10,6 +10,7 @@ import pytest
 
 from mpc_collisionavoidance_amd import _capi, scenario
 from mpc_collisionavoidance_amd.guidance import PathFollowingFrontEnd
+from tests.world_calls_ref import relayout_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mpc_collisionavoidance_amd", "csrc")
@@ -121,20 +122,6 @@ def test_min_separation_is_symmetric_in_a_scene_of_two():
     x = random_states(8, np.random.default_rng(9))[0]
     sep = scenario.fleet_world(x, 2, 0.5)[2][:, 0]
     assert sep[0::2].tobytes() == sep[1::2].tobytes()
-
-
-def relayout_ref(w0, v0, n0f, f0, fixed, n1f, f1):
-    w1, v1 = np.zeros((n1f + f1, 3)), np.zeros((n1f + f1, 2))
-    w1[:n1f] = fixed if fixed is not None else w0[:n1f]
-    if v0 is not None and n1f == n0f:
-        v1[:n1f] = v0[:n1f]
-    for e in range(f1):
-        if e < f0:
-            w1[n1f + e] = w0[n0f + e]
-            v1[n1f + e] = v0[n0f + e] if v0 is not None else 0.0
-        else:
-            w1[n1f + e] = (1000.0, 1000.0, 0.0)
-    return w1, v1
 
 
 @pytest.mark.parametrize("n0f,f0,moving,has_fixed,n1f,f1", [
