@@ -11,7 +11,7 @@ position, hull radius, velocity (u, v) turned by psi, from the states the plant 
 predicted obstacle set of every stage as it does for any moving world; the lineariser keeps running a tick ahead.  The plant is the
 controller's prediction x_1; with --plant-steps K an RK4 integrator of its own (advance_sim).
 
-    python examples/ca_encounter_sweep.py --scenes 4096 --scene-size 2 --ticks 300 --kind crossing [--plant-steps 10] [--no-predict]
+    python examples/ca_encounter_sweep.py --scenes 4096 --scene-size 2 --ticks 300 --kind crossing [--plant-steps 10] [--no-predict] [--plans]
 """
 import argparse
 import os
@@ -28,7 +28,7 @@ from mpc_collisionavoidance_amd.guidance import GuidanceFrontEnd  # noqa: E402
 RING = 64   # solves whose failure counts the library keeps
 
 
-def run(scenes, S, ticks, kind="crossing", N=None, K=None, seed=0, radius=0.5, plant_steps=None, predict=True, quiet=False):
+def run(scenes, S, ticks, kind="crossing", N=None, K=None, seed=0, radius=0.5, plant_steps=None, predict=True, quiet=False, plans=False):
     cfg = scenario.CA_ENC_OCP
     N, K, dt = N or cfg["N"], K or cfg["K"], cfg["dt"]
     B = scenes * S
@@ -47,7 +47,7 @@ def run(scenes, S, ticks, kind="crossing", N=None, K=None, seed=0, radius=0.5, p
     s.set_all("u", np.zeros((B, N, 1)))
     fe.reset(m["waypoints"], m["pose"][:, 2])
     fe.set_world(m["world"], max_radius=cfg["max_radius"])
-    fe.set_fleet(S, radius)
+    fe.set_fleet(S, radius, plans=plans)      # plans: a scene-mate's slot follows the mate's own solved path (csrc/fleet_plan.hpp)
     if not predict:                                                     # (the fleet is on: these are the fixed entries, and the choice holds)
         fe.set_world(m["world"], max_radius=cfg["max_radius"], predict=False)
     fails = np.zeros(ticks, dtype=int)
@@ -66,10 +66,10 @@ def run(scenes, S, ticks, kind="crossing", N=None, K=None, seed=0, radius=0.5, p
             fails[i + 1 - n:i + 1] = s.fail_counts(n)
     s.sync()
     el = time.perf_counter() - t0
-    st, fl = fe.mission_state(), fe.fleet_state()
+    st, fl, pl = fe.mission_state(), fe.fleet_state(), fe.fleet_plan_state()
     res = dict(ticks_per_s=ticks / el, finish_tick=st["finish_tick"], min_clearance=st["min_clearance"], min_separation=fl["min_separation"],
                separation_tick=fl["separation_tick"], waypoint_index=st["wp_index"], failures_per_tick=fails, final_status=s.get_int("status"),
-               final_pose=s.get("x0", 0)[:, 5:8].copy())
+               final_pose=s.get("x0", 0)[:, 5:8].copy(), plan_fed=pl["plan_fed"], plan_launches=pl["plan_launches"])
     if not quiet:
         fin = st["finish_tick"] >= 0
         ms, mc = res["min_separation"], res["min_clearance"]
@@ -81,6 +81,8 @@ def run(scenes, S, ticks, kind="crossing", N=None, K=None, seed=0, radius=0.5, p
         print("smallest separation between two vessels of a scene: %.4f m (median %.4f m), met at tick %d; hulls of %.2f m touch at %.2f m"
               % (ms.min(), np.median(ms), res["separation_tick"][ms.argmin()], radius, 2 * radius))
         print("minimum clearance to the keep-out circle (R + 0.5 m): worst %.4f m, median %.4f m" % (mc.min(), np.median(mc)))
+        if plans:
+            print("exchanged plans: %d launches of the plan kernel, %d plan-fed (vessel, slot) pairs" % (pl["plan_launches"], pl["plan_fed"]))
         print("failed solves: %d over all ticks (%d ticks with at least one)" % (fails.sum(), (fails > 0).sum()))
     s.close()
     if plant is not None:
@@ -100,6 +102,7 @@ if __name__ == "__main__":
     ap.add_argument("--plant-steps", type=int, default=None,
                     help="integrate the plant in this many RK4 steps per tick (default: the plant is the controller's prediction x_1)")
     ap.add_argument("--no-predict", action="store_true", help="the scene is held still inside the horizon (set_world(..., predict=False))")
+    ap.add_argument("--plans", action="store_true", help="scene-mates are predicted along their own solved paths, not along straight lines")
     a = ap.parse_args()
     run(a.scenes, a.scene_size, a.ticks, kind=a.kind, N=a.horizon, seed=a.seed, radius=a.radius, plant_steps=a.plant_steps,
-        predict=not a.no_predict)
+        predict=not a.no_predict, plans=a.plans)

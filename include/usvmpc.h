@@ -504,6 +504,28 @@ int usvmpc_pf_world_read(usvmpc_handle *h, double *world, double *vel);
  *             -1: none yet).  Either may be NULL. */
 int usvmpc_pf_fleet(usvmpc_handle *h, int scene_size, double radius);
 int usvmpc_pf_fleet_state(usvmpc_handle *h, double *min_separation, int *separation_tick);
+/* EXCHANGED PLANS for both front ends' fleets (the arithmetic: csrc/fleet_plan.hpp; the rule for when a plan is usable: csrc/world_plan.hpp,
+ * PlanState).  Off by default.  A scene-mate is a vessel of this batch, and its own NMPC has just solved where it will go: x[j][1 .. N].  With
+ * plans on a device-resident prepare does all it did - gather, nearest-K choice on current positions, tracks, every stage of p and lh from
+ * pos + (k dt) vel - and ONE more kernel behind it on the handle's stream (usv_pf_fleet_plans / usv_guidance_fleet_plans) rewrites stages
+ * 1 .. N of the slots that hold a scene-mate with a usable plan: with P_k the position pair of x[j][k], q the slot's stage-0 position and
+ * e = q - P_1,   p[k] = P_{k+1} + e  (k = 1 .. N-1),   p[N] = (P_N + (P_N - P_{N-1})) + e;   stage 0 stays q and lh is untouched.
+ *   A plan is used only when the iterate is exactly ONE HAND-OVER OLD: solved (usvmpc_solve*), then handed over once (usvmpc_advance,
+ *             _advance_sim, the cascade's hand-over step), and not since written by the caller (usvmpc_set "x", its device pointer handed
+ *             out), nor the front end reset, nor the fleet switched off, nor plans switched on.  The prepare that uses it uses it up: a second
+ *             prepare without a solve and a hand-over in between is the constant-velocity prepare, as is one after two hand-overs.
+ *             Besides: the instance streams this tick, the mate's mission is not over, and status[j] of the last solve is 0.  Every other
+ *             slot keeps the constant-velocity bits.  While the world is not predicted inside the horizon ("pf_predict" 0, predict 0) the
+ *             kernel is not launched.
+ *   fleet_plans refuses, in this order: another model; (guidance) before usvmpc_guidance_reset; no fleet on (path following: or before
+ *             usvmpc_pf_reset) - "... come first"; N < 2.  A refused call changes nothing.
+ *   fleet_plan_state: source [B][K] of the last prepare - the vessel whose plan fed each slot, -1: none; plan_fed - plan-fed (instance, slot)
+ *             pairs so far, counted on the device; plan_launches - launches of the plan kernel so far.  Any may be NULL.  A handle that never
+ *             switched plans on answers -1, 0, 0. */
+int usvmpc_pf_fleet_plans(usvmpc_handle *h, int on);
+int usvmpc_pf_fleet_plan_state(usvmpc_handle *h, int *source, long long *plan_fed, long long *plan_launches);
+int usvmpc_guidance_fleet_plans(usvmpc_handle *h, int on);
+int usvmpc_guidance_fleet_plan_state(usvmpc_handle *h, int *source, long long *plan_fed, long long *plan_launches);
 /* Profiling aid: stream `nplanes` workspace planes with the solver kernels' access instruction
  * (kernel usv_calib_stream) and report the exact byte counts, to calibrate HBM PMC counters.
  * Overwrites solver scratch; the next usvmpc_solve re-initialises it. */

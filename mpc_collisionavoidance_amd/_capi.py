@@ -70,7 +70,8 @@ EXPORTS = ["usvmpc_model_dims", "usvmpc_default_options", "usvmpc_hpipm_profile"
            "usvmpc_sim_set_stream", "usvmpc_sim_last_error", "usvmpc_advance_sim", "usvmpc_obstacles_step",
            "usvmpc_pf_reset", "usvmpc_pf_world", "usvmpc_pf_prepare", "usvmpc_pf_publish", "usvmpc_pf_state",
            "usvmpc_pf_world_vel", "usvmpc_pf_world_step", "usvmpc_pf_world_read",
-           "usvmpc_pf_fleet", "usvmpc_pf_fleet_state",
+           "usvmpc_pf_fleet", "usvmpc_pf_fleet_state", "usvmpc_pf_fleet_plans", "usvmpc_pf_fleet_plan_state",
+           "usvmpc_guidance_fleet_plans", "usvmpc_guidance_fleet_plan_state",
            "usvmpc_guidance_world", "usvmpc_guidance_world_vel", "usvmpc_guidance_world_step", "usvmpc_guidance_world_read",
            "usvmpc_guidance_mission_state", "usvmpc_guidance_fleet", "usvmpc_guidance_fleet_state",
            "usvmpc_log_start", "usvmpc_log_stop", "usvmpc_log_info", "usvmpc_log_read", "usvmpc_log_errors", "usvmpc_log_device_ptr",
@@ -169,6 +170,9 @@ def load(path):
     L.usvmpc_guidance_fleet.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.usvmpc_guidance_fleet_state.argtypes = [C.c_void_p, _dp, _ip]
     L.usvmpc_pf_fleet_state.argtypes = [C.c_void_p, _dp, _ip]
+    for kind in ("pf", "guidance"):
+        getattr(L, "usvmpc_%s_fleet_plans" % kind).argtypes = [C.c_void_p, C.c_int]
+        getattr(L, "usvmpc_%s_fleet_plan_state" % kind).argtypes = [C.c_void_p, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.usvmpc_debug_model_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_obstacle_eval.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.usvmpc_debug_model_eval_from.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]

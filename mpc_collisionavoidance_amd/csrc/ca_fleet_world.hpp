@@ -45,6 +45,7 @@ USV_HD double ca_fleet_separation(const double *xi, const double *xj)
 // this model for the gather written once for both (fleet_world.hpp: PfFleet)
 struct CaFleet {
     static constexpr int NX = CA_FLEET_NX;
+    static constexpr int PX = 5, PY = 6; // the position pair of a state (fleet_plan.hpp)
     static USV_HD void entry(const double *xj, double radius, double *w, double *wv) { ca_fleet_entry(xj, radius, w, wv); }
     static USV_HD double separation(const double *xi, const double *xj) { return ca_fleet_separation(xi, xj); }
 };

@@ -326,6 +326,8 @@ struct CaTickPtrs {
     double *min_clear;   // [B] running minimum of ca_min_clearance
     int *finish_tick;    // [B] tick of the first prepare that found the mission over (-1: none yet)
     int tick;
+    int *chosen;         // [B][K] exchanged plans (fleet_plan.hpp): the list index behind each slot of this tick, -1 for a parked one and for
+                         // every slot of an instance that does not stream; null: plans are off and nothing is recorded
 };
 
 } // namespace usv

@@ -70,6 +70,7 @@ USV_HD double fleet_separation(const double *xi, const double *xj)
 // this model for a gather written once for both front ends' models (usvmpc.hip: fleet_gather_body; ca_fleet_world.hpp: CaFleet)
 struct PfFleet {
     static constexpr int NX = FLEET_NX;
+    static constexpr int PX = 10, PY = 11; // the position pair of a state (fleet_plan.hpp)
     static USV_HD void entry(const double *xj, double radius, double *w, double *wv) { fleet_entry(xj, radius, w, wv); }
     static USV_HD double separation(const double *xi, const double *xj) { return fleet_separation(xi, xj); }
 };

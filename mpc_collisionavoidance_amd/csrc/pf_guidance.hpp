@@ -66,6 +66,8 @@ struct PfPtrs {
     int *active;
     double *min_sep;     // [B] smallest distance to a vessel of the instance's scene (fleet_world.hpp; 1e300 after a reset)
     int *sep_tick;       // [B] the prepare it was met at (-1: none yet)
+    int *chosen;         // [B][K] exchanged plans (fleet_plan.hpp): the list index behind each slot of this prepare, -1 for a parked one and
+                         // for every slot of an instance that does not stream; null: plans are off and nothing is recorded
 };
 
 // velocityCallback :201-203

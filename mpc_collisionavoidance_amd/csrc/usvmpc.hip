@@ -47,6 +47,7 @@
 #include "world_plan.hpp"
 #include "cond_launch.hpp"
 #include "field_plan.hpp"
+#include "fleet_plan.hpp"
 #ifdef USV_GEN_MODEL_HEADER // a model generated from a symbolic definition (codegen.py): struct ModelGen
 #include USV_GEN_MODEL_HEADER
 #endif
@@ -704,7 +705,7 @@ __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int t
             double dmin;
             if (F.wvel) {
                 dmin = pf_select_tracks(F.world + b * 3 * F.nworld, F.wvel + b * 2 * F.nworld, L, K, nedx, nedy, F.max_radius, F.margin, s_d + t,
-                                        PF_GROUP, F.trk_pv + b * 4 * K, F.trk_lh + b * K, nullptr);
+                                        PF_GROUP, F.trk_pv + b * 4 * K, F.trk_lh + b * K, F.chosen ? F.chosen + b * K : nullptr);
                 s_obs[t] = 1;
                 atomicAdd(&s_nobs, 1u);
             } else {
@@ -712,6 +713,8 @@ __global__ void __launch_bounds__(256) usv_pf_prepare(DevPtrs P, PfPtrs F, int t
                                  const_cast<double *>(P.p) + b * (long)(N + 1) * 2 * K, const_cast<double *>(P.lh) + b * (long)N * K, nullptr);
             }
             if (dmin < F.min_clear[b]) F.min_clear[b] = dmin;
+        } else if (F.chosen) { // (exchanged plans: an instance that does not stream has no slot a plan could feed)
+            for (int s = 0; s < K; s++) F.chosen[b * K + s] = -1;
         }
         if (phase == PF_ACTIVE) {
             pf_x0(psi, u, v, r, seg, nedx, nedy, pp, ps, x0);
@@ -918,6 +921,8 @@ __global__ void __launch_bounds__(256) usv_guidance_tick(DevPtrs P, GuidancePtrs
         int k = G.k[b];
         if (k >= G.npts) { // the mission was over before this tick
             if (W.finish_tick[b] < 0) W.finish_tick[b] = W.tick;
+            if (W.chosen) // (exchanged plans: an instance that does not stream has no slot a plan could feed)
+                for (int s = 0; s < K; s++) W.chosen[b * K + s] = -1;
         } else {
             double *x0 = const_cast<double *>(P.x0) + b * CA_NX;
             const double u_cb = ca_fix_u(x0[0]), v_cb = x0[1], nedx = x0[5], nedy = x0[6], psi = x0[7];
@@ -925,7 +930,7 @@ __global__ void __launch_bounds__(256) usv_guidance_tick(DevPtrs P, GuidancePtrs
             const double *w = W.world + b * 3 * W.nworld;
             if (W.wvel) {
                 ca_select_tracks(w, W.wvel + b * 2 * W.nworld, L, K, psi, nedx, nedy, W.max_radius, s_d + t, CA_GROUP, W.trk_pv + b * 4 * K,
-                                 W.trk_lh + b * K, nullptr);
+                                 W.trk_lh + b * K, W.chosen ? W.chosen + b * K : nullptr);
                 s_obs[t] = 1;
                 atomicAdd(&s_nobs, 1u);
             } else {
@@ -991,6 +996,81 @@ __global__ void __launch_bounds__(256) usv_guidance_tick(DevPtrs P, GuidancePtrs
         }
     }
 }
+
+// ---- Exchanged plans (usvmpc_pf_fleet_plans / usvmpc_guidance_fleet_plans; the arithmetic: fleet_plan.hpp).  Enqueued behind a predicted
+// prepare on the same stream when the handle's plan state says the iterate is one hand-over old (world_plan.hpp: plan_usable): the prepare
+// has written every stage of p from the constant-velocity tracks; this kernel rewrites stages 1 .. N of the slots that hold a scene-mate
+// with a usable plan, and nothing else.  A kernel of its own because a mate's finish_tick is written by another workgroup's decide step.
+// One workgroup per 64 consecutive instances, the prepare's groups (PF_GROUP, CA_GROUP):
+// 1. Sources: thread t takes the (instance, slot) pairs t, t + 256, .. of the group's [cnt][K] - the decide step's choice, the mate's
+//    finish_tick and status - into LDS and into `source`; the plan-fed pairs are counted, one atomic per workgroup (as yref_writes).
+// 2. Stream: the group's run of p (cnt * (N + 1) * K pairs) is walked as the prepare's stream step walks it, thread t the t-th pair of
+//    every 4 KiB pass, but ONLY pairs whose slot has a source are stored: 16 bytes each, the others are not touched.
+// The mates' position columns are 16 bytes of every 112- or 64-byte row of x and are read straight from memory, not staged in LDS.  The
+// pairs of one pass that read the same row are neighbours in the pass (the S - 1 mates of a vessel hold it in one stage each, and their
+// instances are adjacent), so the re-reads hit the line the first read brought into the CU's vector cache, and at the worst L2; HBM sees
+// each line once either way.  A scene's columns in LDS would be (64 + 2 (S - 2)) (N + 1) 16 bytes per group - 107 KB at N = 100, one
+// workgroup per CU - bought with a barrier and a second pass over the same lines, to save cache hits.  
+constexpr int PLAN_GROUP = 64;
+static_assert(PLAN_GROUP == PF_GROUP && PLAN_GROUP == CA_GROUP, "the plan kernel owns the prepare's groups");
+
+struct FleetPlanArgs {
+    const double *x;         // [B][N + 1][NX] the iterate
+    const int *status;       // [B] of the last solve
+    const int *finish_tick;  // [B] as this prepare left it
+    const int *chosen;       // [B][K] the decide step's choice
+    const double *trk_pv;    // [B][K][4] the slot tracks
+    double *p;               // [B][N + 1][2K]
+    int *source;             // [B][K] out: the vessel behind each plan-fed slot, -1: none
+    unsigned long long *fed; // [1] plan-fed (instance, slot) pairs so far
+    int B, N, K, S, n_fixed;
+};
+
+template <class Fleet>
+__device__ __forceinline__ void fleet_plan_body(const FleetPlanArgs &A)
+{
+    const int N = A.N, K = A.K;
+    __shared__ int s_src[PLAN_GROUP * KMAX];
+    __shared__ unsigned s_fed;
+    const int t = (int)threadIdx.x;
+    const long b0 = (long)blockIdx.x * PLAN_GROUP;
+    const int cnt = (int)((long)A.B - b0 < (long)PLAN_GROUP ? (long)A.B - b0 : (long)PLAN_GROUP);
+    if (t == 0) s_fed = 0u;
+    __syncthreads();
+    unsigned mine = 0u;
+    for (int e = t; e < cnt * K; e += 256) {
+        const long i = b0 + e / K;
+        long j = fleet_plan_source(i, A.chosen[b0 * K + e], A.n_fixed, A.S, A.finish_tick, A.status);
+        if (j >= (long)A.B) j = -1; // (never: the batch is a whole number of scenes)
+        s_src[e] = (int)j;
+        A.source[b0 * K + e] = (int)j;
+        mine += j >= 0 ? 1u : 0u;
+    }
+    if (mine) atomicAdd(&s_fed, mine);
+    __syncthreads();
+    if (s_fed == 0u) return;
+    if (t == 0) atomicAdd(A.fed, (unsigned long long)s_fed);
+    const double2 *pv = reinterpret_cast<const double2 *>(A.trk_pv) + b0 * 2 * K; // [cnt][K][2]: (X, Y), (vX, vY)
+    double2 *row = reinterpret_cast<double2 *>(A.p) + b0 * (long)(N + 1) * K;
+    const int per = (N + 1) * K, total = cnt * per; // pairs per instance / of the workgroup
+    int inst = 0, rem = t;                          // j = inst * per + rem
+    while (rem >= per) { rem -= per; inst++; }
+    for (int j = t; j < total; j += 256) {
+        const int k = rem / K, slot = rem - k * K;
+        const int src = s_src[inst * K + slot];
+        if (src >= 0 && k >= 1) {
+            const double2 q = pv[(inst * K + slot) * 2];
+            double2 o;
+            fleet_plan_pair<Fleet>(A.x + (long)src * (N + 1) * Fleet::NX, N, k, q.x, q.y, o.x, o.y);
+            row[j] = o;
+        }
+        rem += 256;
+        while (rem >= per) { rem -= per; inst++; }
+    }
+}
+
+__global__ void __launch_bounds__(256) usv_pf_fleet_plans(FleetPlanArgs A) { fleet_plan_body<PfFleet>(A); }
+__global__ void __launch_bounds__(256) usv_guidance_fleet_plans(FleetPlanArgs A) { fleet_plan_body<CaFleet>(A); }
 
 // ---- The two-layer control stack (usvmpc_cascade_*; the arithmetic: cascade.hpp): guidance layer -> low-level NMPC -> vessel.
 constexpr int CAS_GROUP = 64; // instances per workgroup of usv_cascade_refs
@@ -1341,7 +1421,13 @@ struct usvmpc_handle {
         double *trk_pv, *trk_lh; // [B][K][4], [B][K] the slot tracks a predicted prepare leaves between its two steps
         double *min_sep;      // [B] smallest distance to a vessel of the instance's scene (1e300 after a reset)
         int *sep_tick;        // [B] the prepare it was met at (-1: none yet)
+        // exchanged plans (fleet_plan.hpp; usv_pf_fleet_plans / usv_guidance_fleet_plans), made when plans are first switched on
+        int *chosen;          // [B][K] the list index behind each slot, as the last prepare's decide step chose
+        int *source;          // [B][K] the vessel behind each plan-fed slot of the last prepare, -1: none
+        unsigned long long *plan_fed; // [1] plan-fed (instance, slot) pairs so far
     } wb;
+    long long plan_launches;  // launches of the plan kernel so far
+    bool plan_source_clear;   // wb.source is all -1 (no memset is enqueued for a prepare that finds it so)
     int last_wide;            // the last RTI launch ran on the wide kernel
     // hand-over of long runners to a follow-up launch (option "handover_iter")
     int *d_susp_count, *d_susp_list; // [RING] instances each of the last launches handed over / [B] their groups
@@ -1821,6 +1907,7 @@ int copy_field(usvmpc_handle *h, const char *field, int stage, double *host, siz
     }
     // (a lineariser that ran ahead may have read what is being replaced - it reads x, u, yref: the next solve linearises again)
     if (set && (f.row->flags & FF_LIN)) h->sched.caller_wrote();
+    if (set && f.row->id == FLD_X) h->world.plan_lost(); // (exchanged plans: the iterate is the caller's now)
     const CopyDesc span = field_span(f, (size_t)h->B);
     const int slot = f.row->slot;
     if (set ? h->hm.set_served(slot) : h->hm.get_served(slot)) {
@@ -2151,6 +2238,7 @@ int launch_solve(usvmpc_handle *h, const Kernels &k, int phase)
         HIP_TRY(h, hipEventRecord(h->ev_spec, h->aux_stream));
     }
     h->nsolves++;
+    h->world.plan_solved(); // (exchanged plans: the iterate is this solve's)
     h->layout_dirty = false;
     h->last_cond = cond;
     CopyDesc back;
@@ -2628,6 +2716,7 @@ int usvmpc_get_device_ptr(usvmpc_handle *h, const char *field, void **dptr)
         const int rcf = mirror_flush(h);
         if (rcf) return rcf;
         h->hm.handed_out();
+        if (row->id == FLD_X) h->world.plan_lost(); // (exchanged plans: the caller may write the iterate behind the library's back)
         const int rcs = spec_cancel(h); // (and no lineariser runs ahead on arrays the caller may write behind the library's back)
         if (rcs) return rcs;
     }
@@ -3134,6 +3223,7 @@ int usvmpc_advance(usvmpc_handle *h, double sigma, unsigned long long seed)
     hipLaunchKernelGGL(usv_advance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ptrs, h->nx, sigma, seed, h->opt.noise_mask,
                        h->opt.instance_offset);
     HIP_TRY(h, hipGetLastError());
+    h->world.plan_handed_over();
     if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, h->spec.dt); // (the world moves with the vehicle: one shooting interval)
     if (h->world.steps_on_advance(h->opt.step_on_advance != 0)) return world_step(h, h->spec.dt); // (the front end's world likewise)
     return 0;
@@ -3197,6 +3287,7 @@ int usvmpc_advance_sim(usvmpc_handle *h, const usvmpc_sim *plant, double sigma, 
     default: h->err = "advance_sim: no plant kernel for this model in this library"; return USVMPC_E_ARG;
     }
     HIP_TRY(h, hipGetLastError());
+    h->world.plan_handed_over();
     if (h->opt.tracks_on && h->opt.step_on_advance) return tracks_step(h, plant->T); // (the world moves by the plant's period)
     if (h->world.steps_on_advance(h->opt.step_on_advance != 0)) return world_step(h, plant->T);
     return 0;
@@ -3346,6 +3437,7 @@ static int apply_static(usvmpc_handle *h)
 }
 
 static int pf_alloc(usvmpc_handle *h);
+static size_t slots_k(const usvmpc_handle *h) { return (size_t)h->B * (size_t)h->K; } // (instance, slot) pairs
 
 // a world buffer (the list, or the velocities) of `need` doubles in place of the present one, which is released first; the plan hears of both
 static int world_buffer(usvmpc_handle *h, double **buf, size_t need, bool vel)
@@ -3380,6 +3472,14 @@ static int carry_world(usvmpc_handle *h, const WorldAct &a, const double *in, do
         if (dev_alloc(h, &D.min_sep, B, true) || dev_alloc(h, &D.sep_tick, B, true)) return USVMPC_E_HIP;
         hipLaunchKernelGGL(usv_guidance_none_yet, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, D.min_sep, D.sep_tick, (int)B);
         HIP_TRY(h, hipGetLastError());
+    }
+    if (a.make_plans && !D.chosen) {
+        if (dev_alloc(h, &D.chosen, slots, true) || dev_alloc(h, &D.source, slots, true) || dev_alloc(h, &D.plan_fed, 1, true)) return USVMPC_E_HIP;
+        HIP_TRY(h, hipMemsetAsync(D.chosen, 0xff, slots * sizeof(int), h->stream)); // (-1)
+        HIP_TRY(h, hipMemsetAsync(D.source, 0xff, slots * sizeof(int), h->stream));
+        HIP_TRY(h, hipMemsetAsync(D.plan_fed, 0, sizeof(unsigned long long), h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->plan_source_clear = true;
     }
     switch (a.what) {
     case WORLD_UPLOAD_LIST:
@@ -3432,6 +3532,18 @@ static int carry_world(usvmpc_handle *h, const WorldAct &a, const double *in, do
         if (vel && n && a.vel_on_device) HIP_TRY(h, hipMemcpyAsync(vel, D.vel, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (vel && !a.vel_on_device) std::fill(vel, vel + n * 2, 0.0); // (a world at rest)
+        return 0;
+    }
+    case WORLD_PLAN_STATE: { // out2: {int *source, long long *fed}
+        void **o = (void **)out2;
+        if (a.host_answer) {
+            if (o[0]) std::fill((int *)o[0], (int *)o[0] + slots_k(h), -1);
+            if (o[1]) *(long long *)o[1] = 0;
+            return 0;
+        }
+        if (o[0] && slots_k(h)) HIP_TRY(h, hipMemcpyAsync(o[0], D.source, slots_k(h) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (o[1]) HIP_TRY(h, hipMemcpyAsync(o[1], D.plan_fed, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
         return 0;
     }
     case WORLD_FLEET_STATE:
@@ -3519,6 +3631,56 @@ int usvmpc_pf_fleet_state(usvmpc_handle *h, double *min_separation, int *separat
     return h ? world_call(h, h->world.fleet_state(world_facts(h, WORLD_PF)), nullptr, 0.0, min_separation, separation_tick) : USVMPC_E_ARG;
 }
 
+int usvmpc_guidance_fleet_plans(usvmpc_handle *h, int on)
+{
+    return h ? world_call(h, h->world.plans(world_facts(h, WORLD_GUIDANCE), on, h->N)) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_fleet_plans(usvmpc_handle *h, int on)
+{
+    return h ? world_call(h, h->world.plans(world_facts(h, WORLD_PF), on, h->N)) : USVMPC_E_ARG;
+}
+
+static int fleet_plan_state(usvmpc_handle *h, const WorldKind &k, int *source, long long *plan_fed, long long *plan_launches)
+{
+    void *out[2] = {source, plan_fed};
+    const int rc = world_call(h, h->world.fleet_plan_state(world_facts(h, k)), nullptr, 0.0, nullptr, out);
+    if (rc == 0 && plan_launches) *plan_launches = h->plan_launches;
+    return rc;
+}
+
+int usvmpc_guidance_fleet_plan_state(usvmpc_handle *h, int *source, long long *plan_fed, long long *plan_launches)
+{
+    return h ? fleet_plan_state(h, WORLD_GUIDANCE, source, plan_fed, plan_launches) : USVMPC_E_ARG;
+}
+
+int usvmpc_pf_fleet_plan_state(usvmpc_handle *h, int *source, long long *plan_fed, long long *plan_launches)
+{
+    return h ? fleet_plan_state(h, WORLD_PF, source, plan_fed, plan_launches) : USVMPC_E_ARG;
+}
+
+// a predicted prepare's last step while plans are on (world_plan.hpp: records_choice): the plan kernel behind the prepare when the iterate
+// is one hand-over old, else the sources say "none".  Same stream, no wait.
+static int fleet_plans_follow(usvmpc_handle *h, const WorldKind &k, void (*kernel)(FleetPlanArgs), const int *finish_tick)
+{
+    usvmpc_handle::WorldBufs &D = h->wb;
+    const WorldPlan &w = h->world;
+    if (!D.source || h->K == 0) return 0; // (plans were never on)
+    if (!w.plan_usable(k, h->opt.pf_predict != 0)) { // the sources of the LAST prepare: none, plans on or off
+        if (!h->plan_source_clear) HIP_TRY(h, hipMemsetAsync(D.source, 0xff, slots_k(h) * sizeof(int), h->stream)); // (-1)
+        h->plan_source_clear = true;
+        return 0;
+    }
+    h->plan_source_clear = false;
+    FleetPlanArgs A = {h->ptrs.x, h->ptrs.status, finish_tick, D.chosen, D.trk_pv, const_cast<double *>(h->ptrs.p), D.source, D.plan_fed,
+                       h->B, h->N, h->K, w.fleet_S(), w.nfixed()};
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((h->B + PLAN_GROUP - 1) / PLAN_GROUP)), dim3(256), 0, h->stream, A);
+    HIP_TRY(h, hipGetLastError());
+    h->plan_launches++;
+    h->world.plan_used();
+    return 0;
+}
+
 // ---- guidance front end (M1 only): see ca_guidance.hpp (the arithmetic), guidance.hpp (the host-fed kernels), usv_guidance_tick above
 
 static int guidance_alloc(usvmpc_handle *h, int npts)
@@ -3578,6 +3740,7 @@ int usvmpc_guidance_reset(usvmpc_handle *h, const double *waypoints, int npts, c
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->gd_tick = 0;
+    h->world.plan_lost();
     return apply_static(h);
 }
 
@@ -3637,6 +3800,7 @@ static int guidance_tick(usvmpc_handle *h)
     W.trk_pv = D.trk_pv; W.trk_lh = D.trk_lh;
     W.wvel = w.want_static(WORLD_GUIDANCE, false) ? nullptr : D.vel; // (held still inside the horizon: the tick of a world at rest)
     W.tick = h->gd_tick;
+    W.chosen = w.records_choice(WORLD_GUIDANCE, false) ? D.chosen : nullptr;
     const size_t B = h->B;
     if (w.fleet_S()) { // the scene's other vessels, as the plant left them, into the fleet slots - before usv_guidance_tick rewrites x0
         const long n = (long)B * fleet_slots(w.fleet_S());
@@ -3647,7 +3811,7 @@ static int guidance_tick(usvmpc_handle *h)
     hipLaunchKernelGGL(usv_guidance_tick, dim3((unsigned)((B + CA_GROUP - 1) / CA_GROUP)), dim3(256), 0, h->stream, h->ptrs, h->gd, W);
     HIP_TRY(h, hipGetLastError());
     h->gd_tick++;
-    return 0;
+    return fleet_plans_follow(h, WORLD_GUIDANCE, usv_guidance_fleet_plans, W.finish_tick);
 }
 
 int usvmpc_guidance_sense(usvmpc_handle *h, const double *pose, const double *world, int n_world, double max_radius,
@@ -3766,6 +3930,7 @@ static PfPtrs pf_args(const usvmpc_handle *h)
     F.world = h->wb.list; F.nworld = h->world.nworld(); F.max_radius = h->world.max_radius();
     F.trk_pv = h->wb.trk_pv; F.trk_lh = h->wb.trk_lh;
     F.min_sep = h->wb.min_sep; F.sep_tick = h->wb.sep_tick;
+    F.chosen = nullptr; // (usvmpc_pf_prepare says otherwise while plans are on)
     return F;
 }
 
@@ -3794,6 +3959,7 @@ int usvmpc_pf_reset(usvmpc_handle *h, const double *waypoints, int npts)
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->pf_ready = true; h->pf_stale = true; h->pf_tick = 0;
+    h->world.plan_lost();
     return apply_static(h);
 }
 
@@ -3823,6 +3989,7 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     PfPtrs F = pf_args(h);
     F.margin = h->opt.pf_margin;
     F.wvel = w.want_static(WORLD_PF, h->opt.pf_predict != 0) ? nullptr : h->wb.vel; // (held still inside the horizon: the prepare of a world at rest)
+    F.chosen = w.records_choice(WORLD_PF, h->opt.pf_predict != 0) ? h->wb.chosen : nullptr;
     const size_t B = h->B;
     if (vel_uvr) {
         HIP_TRY(h, hipMemcpyAsync(h->pf_vel, vel_uvr, B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -3836,7 +4003,7 @@ int usvmpc_pf_prepare(usvmpc_handle *h, const double *vel_uvr, const double *pos
     h->pf_stale = false;
     h->pf_tick++;
     if (vel_uvr) HIP_TRY(h, hipStreamSynchronize(h->stream)); // (the copies read caller memory: it must be reusable when this call returns)
-    return 0;
+    return fleet_plans_follow(h, WORLD_PF, usv_pf_fleet_plans, F.finish_tick);
 }
 
 int usvmpc_pf_publish(usvmpc_handle *h, double *thr_port, double *thr_stbd, double *Tx, double *Tz, float *e_u, float *e_ye, double *speed,
@@ -4080,6 +4247,7 @@ int usvmpc_cascade_step(usvmpc_cascade *c, double sigma, unsigned long long seed
                        h->B, c->T, c->num_steps, c->c, sigma, seed, c->offset, hand_over ? 1 : 0);
     CAS_TRY(c, hipGetLastError());
     c->tick++;
+    if (hand_over) h->world.plan_handed_over();
     // a guidance period has passed: the guidance layer's moving world follows, as usvmpc_advance would have moved it
     if (hand_over && h->world.steps_on_advance(h->opt.step_on_advance != 0) && world_step(h, (double)c->ratio * c->T)) {
         c->err = "cascade_step: " + h->err;

@@ -71,6 +71,16 @@ inline size_t first_nonfinite(const double *a, size_t n)
     return n;
 }
 
+// Exchanged plans (fleet_plan.hpp): whether the iterate x of the handle may stand for where each vessel will go.  A mate's x[j][1] must be
+// the mate's position NOW, which holds for an iterate that was solved and then handed over exactly once.  The plan hears of every event
+// through a method below (no caller assigns the state); only a prepare that finds PLAN_SHIFTED launches the plan kernel, and that prepare
+// uses the plan up - a second prepare without a hand-over is today's prepare.
+//   PLAN_NONE     no usable plan       a front-end reset, a caller write of x (usvmpc_set, or a device pointer handed out), fleet with scene
+//                                      size 0, switching plans on, a second hand-over with no solve in between, the prepare that used it
+//   PLAN_SOLVED   solved, not shifted  a solve
+//   PLAN_SHIFTED  one hand-over old    a hand-over (usvmpc_advance, _advance_sim, the cascade's step) from PLAN_SOLVED
+enum PlanState { PLAN_NONE = 0, PLAN_SOLVED, PLAN_SHIFTED };
+
 // the list as it stands
 struct WorldState {
     bool set = false;          // a list has been given (an empty one counts)
@@ -85,6 +95,9 @@ struct WorldState {
     bool has_vel = false;      // the velocity buffer exists
     bool tracks = false;       // the slot tracks exist
     bool sep = false;          // the separation buffers were made by a fleet call (WorldKind::sep_with_front_end: unused)
+    bool plans = false;        // scene-mates' planned paths feed the fleet's slots (fleet_plan.hpp), when a plan is usable
+    bool plan_bufs = false;    // the plan buffers (the decide step's choice, the sources, the counter) exist
+    int plan = PLAN_NONE;      // PlanState: how old the iterate x is
 };
 
 enum WorldDo {
@@ -98,6 +111,8 @@ enum WorldDo {
     WORLD_STEP,        // one step over B n entries
     WORLD_READ,        // copy out B n entries; velocities from the device when `vel_on_device`, else zeros
     WORLD_FLEET_STATE, // copy out the separations; `host_answer`: no buffer yet, 1e300 / -1 from the host
+    WORLD_PLANS,       // exchanged plans switched; the plan buffers first when `make_plans`
+    WORLD_PLAN_STATE,  // copy out the sources and the counter; `host_answer`: no buffer yet, -1 / 0 from the host
 };
 
 // A judged call: refused (the message, word for word; nothing else is meaningful then) or what the carrier does, and the state that stands
@@ -114,6 +129,7 @@ struct WorldAct {
     bool make_front_end = false; // the front end's own buffers first (a world call ahead of the reset)
     bool make_tracks = false;    // the slot tracks first
     bool make_sep = false;       // the separation buffers first, filled with 1e300 / -1
+    bool make_plans = false;     // the plan buffers first: sources -1, counter 0
     bool apply_static = false;   // afterwards the carrier asks for "static_obstacles" as want_static() says
     WorldState next;
 };
@@ -133,9 +149,20 @@ public:
     size_t list_cap() const { return s.list_cap; }
     size_t vel_cap() const { return s.vel_cap; }
 
+    bool plans_on() const { return s.plans; }
+    int plan_state() const { return s.plan; }
+
     // the horizon sees the velocities (only asked of a moving world)
     bool predicted(const WorldKind &k, bool pf_predict) const { return k.stores_predict ? s.predict : pf_predict; }
     bool want_static(const WorldKind &k, bool pf_predict) const { return !(s.moving && predicted(k, pf_predict)); }
+    // a prepare: its decide step records the choice (plans on over a fleet that is predicted) .. and the plan kernel follows it
+    bool records_choice(const WorldKind &k, bool pf_predict) const { return s.plans && s.fleet_S != 0 && !want_static(k, pf_predict); }
+    bool plan_usable(const WorldKind &k, bool pf_predict) const { return records_choice(k, pf_predict) && s.plan == PLAN_SHIFTED; }
+    // what happens to the iterate x (PlanState above)
+    void plan_solved() { s.plan = PLAN_SOLVED; }
+    void plan_handed_over() { s.plan = s.plan == PLAN_SOLVED ? PLAN_SHIFTED : PLAN_NONE; }
+    void plan_lost() { s.plan = PLAN_NONE; } // (a front-end reset, a caller write of x)
+    void plan_used() { s.plan = PLAN_NONE; } // (the prepare that launched the plan kernel)
     // usvmpc_advance / _advance_sim / the cascade's hand-over move the world on
     bool steps_on_advance(bool step_on_advance) const { return s.moving && step_on_advance; }
 
@@ -252,6 +279,7 @@ public:
             return refuse(who + ": " + k.reset_call + " and a world list (" + k.world_call + "; an empty one will do) come first");
         if (scene_size < 0) return refuse(who + ": scene_size must not be negative");
         if (!fleet_on(scene_size)) { // off: the list is cut back to the fixed entries, which keep their velocities
+            a.next.plan = PLAN_NONE;
             if (!s.fleet_S) return a;
             relayout(a, f, s.nfixed, 0, false);
             a.next.fleet_S = 0;
@@ -284,6 +312,38 @@ public:
         if (!a.refused.empty()) return a;
         a.what = WORLD_FLEET_STATE;
         a.host_answer = !k.sep_with_front_end && !s.sep; // no fleet yet: as after a reset
+        return a;
+    }
+
+    // exchanged plans on or off (N: the handle's horizon)
+    WorldAct plans(const WorldFacts &f, int on, int N) const
+    {
+        const WorldKind &k = *f.kind;
+        const std::string who = std::string(k.prefix) + "fleet_plans";
+        WorldAct a = begin(f, who, k.reset_for_all);
+        if (!a.refused.empty()) return a;
+        if (k.reset_for_all) {
+            if (!s.fleet_S) return refuse(who + ": a world list and a fleet (" + k.fleet_call + ") come first");
+        } else if (!f.ready || !s.fleet_S)
+            return refuse(who + ": " + k.reset_call + ", a world list and a fleet (" + k.fleet_call + ") come first");
+        if (N < 2) return refuse(who + ": the horizon has N = " + std::to_string(N) + "; a scene-mate's plan needs N >= 2");
+        a.what = WORLD_PLANS;
+        a.make_plans = on != 0 && !s.plan_bufs;
+        a.next.plans = on != 0;
+        if (on) { // (whatever the iterate was: the first plan used is one solved and handed over with plans on)
+            a.next.plan_bufs = true;
+            a.next.plan = PLAN_NONE;
+        }
+        return a;
+    }
+
+    WorldAct fleet_plan_state(const WorldFacts &f) const
+    {
+        const WorldKind &k = *f.kind;
+        WorldAct a = begin(f, std::string(k.prefix) + "fleet_plan_state", true);
+        if (!a.refused.empty()) return a;
+        a.what = WORLD_PLAN_STATE;
+        a.host_answer = !s.plan_bufs; // plans were never on
         return a;
     }
 

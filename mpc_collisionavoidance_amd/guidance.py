@@ -36,15 +36,31 @@ class _ResidentWorld:
         self._world_call("world_vel", None if v is None else v.ctypes.data_as(_capi._dp), *vel_args)
         self._L = w.shape[1]
 
-    def set_fleet(self, scene_size, radius=0.5):
+    def set_fleet(self, scene_size, radius=0.5, plans=False):
         """Vessel encounters: the batch is cut into scenes of scene_size = S consecutive instances, and every instance sees the other
         S - 1 vessels of its scene - position, hull radius `radius`, velocity from the state the plant left in x0 (the guidance model: (u, v)
         turned by psi) - as moving world entries behind its fixed ones (set_world), refreshed on the device by every device-resident
         prepare().  B % S == 0; after reset() and set_world() (an empty world will do).  GuidanceFrontEnd: over a world at rest the scene is
         predicted per stage; a set_world(..., predict=False) AFTER this call holds it still inside the horizon.  scene_size 0 or 1: off, the
-        world list is the fixed entries again."""
+        world list is the fixed entries again.
+        plans=True (exchanged plans, csrc/fleet_plan.hpp; N >= 2): a scene-mate's slot follows the path the mate's own NMPC has just
+        solved, x[j][1 .. N] moved by what the plant did to the mate since, instead of the straight line pos + (k dt) vel - whenever the
+        iterate is exactly one hand-over old (solve -> advance / advance_sim -> prepare), the mate's mission is not over and its last solve
+        succeeded; every other slot, and every prepare in any other state, keeps the constant-velocity stages.  fleet_plan_state() tells which
+        slots were fed."""
         self._world_call("fleet", int(scene_size), float(radius))
         self._S = int(scene_size) if int(scene_size) >= 2 else 0
+        if self._S and (plans or getattr(self, "_plans", False)):
+            self._world_call("fleet_plans", 1 if plans else 0)
+            self._plans = bool(plans)
+
+    def fleet_plan_state(self):
+        """dict(source [B, K] (the vessel whose plan fed each slot at the last prepare; -1: none - the slot kept its constant-velocity stages),
+        plan_fed (plan-fed (instance, slot) pairs so far, counted on the device), plan_launches (launches of the plan kernel so far))."""
+        src = np.full((self.B, self.s.K), -1, dtype=np.int32)
+        fed, launches = C.c_longlong(0), C.c_longlong(0)
+        self._world_call("fleet_plan_state", src.ctypes.data_as(_capi._ip), C.byref(fed), C.byref(launches))
+        return dict(source=src, plan_fed=int(fed.value), plan_launches=int(launches.value))
 
     def fleet_state(self):
         """dict(min_separation [B] (smallest distance to a vessel of the instance's scene, any tick; 1e300 before the first),

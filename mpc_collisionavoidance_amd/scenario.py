@@ -484,6 +484,46 @@ def ca_fleet_world(x0, S, radius=0.5):
     return entries, vel, np.sqrt(dx * dx + dy * dy)
 
 
+# ---- exchanged plans for both front ends' fleets (csrc/fleet_plan.hpp): a scene-mate's slot follows the mate's own planned path
+FLEET_PLAN_POS = {"usv_model_pf_ca": (10, 11), "usv_model_guidance_ca1": (5, 6)}   # the position pair of a state
+
+
+def fleet_plan_stages(p, x, chosen, S, n_fixed, status, finish_tick, pos=(10, 11), q=None):
+    """The numpy restatement of the device's plan kernel (usv_pf_fleet_plans / usv_guidance_fleet_plans).  p [B,N+1,2K]: the stages as the
+    constant-velocity prepare left them; x [B,N+1,nx]: the iterate, one hand-over old; chosen [B,K]: the list index behind each slot
+    (-1: parked; every slot of an instance that does not stream this tick); status [B] of the last solve; finish_tick [B] as this prepare
+    left it (>= 0: the mission is over); pos: the model's position states (FLEET_PLAN_POS); q [B,K,2]: the slots' stage-0 positions
+    (default: stage 0 of p).  -> (p [B,N+1,2K], source [B,K]: the vessel behind each plan-fed slot, -1: none).
+    Slot s of instance i with c = chosen[i,s] >= n_fixed has the source j = fleet_vessels(B, S)[i, c - n_fixed], used when finish_tick[j] < 0
+    and status[j] == 0.  With P_k = x[j,k,pos] and e = q - P_1: stage k = 1 .. N-1 becomes P_{k+1} + e, stage N becomes
+    (P_N + (P_N - P_{N-1})) + e; stage 0 and every other slot keep their bits.  Sums and differences only, each rounded on its own: the
+    device's bits."""
+    p, x, chosen = np.array(p, dtype=float), np.asarray(x, dtype=float), np.asarray(chosen, dtype=int)
+    status, finish_tick = np.asarray(status, dtype=int), np.asarray(finish_tick, dtype=int)
+    B, K = chosen.shape
+    N = p.shape[1] - 1
+    if N < 2:
+        raise ValueError("fleet_plan_stages: a plan needs N >= 2")
+    if S < 2 or B % S:
+        raise ValueError("fleet_plan_stages: %d instances are not a whole number of scenes of %d (S >= 2)" % (B, S))
+    mates = fleet_vessels(B, S)
+    e_idx = chosen - n_fixed
+    has = (chosen >= n_fixed) & (e_idx < S - 1)
+    j = np.where(has, mates[np.arange(B)[:, None], np.clip(e_idx, 0, S - 2)], -1)
+    ok = has & (finish_tick[np.clip(j, 0, B - 1)] < 0) & (status[np.clip(j, 0, B - 1)] == 0)
+    source = np.where(ok, j, -1)
+    bb, ss = np.nonzero(ok)
+    if bb.size == 0:
+        return p, source
+    P = x[source[bb, ss]][:, :, list(pos)]                              # [n, N+1, 2]
+    slots = p.reshape(B, N + 1, K, 2)
+    q0 = slots[bb, 0, ss] if q is None else np.asarray(q, dtype=float).reshape(B, K, 2)[bb, ss]
+    e = q0 - P[:, 1]
+    slots[bb[:, None], np.arange(1, N)[None, :], ss[:, None]] = P[:, 2:N + 1] + e[:, None]
+    slots[bb, N, ss] = (P[:, N] + (P[:, N] - P[:, N - 1])) + e
+    return slots.reshape(B, N + 1, 2 * K), source
+
+
 # Encounter geometry, settled with tools/guidance_encounter_oracle.py (profiles/guidance_encounter_oracle.txt) under this model's SOFT
 # obstacle rows, whose keep-out distance between two hulls of radius 0.5 is 0.5 + 0.5 = 1.0 m:
 CA_ENC_LANE = 2.0            # m between neighbouring lanes, +- CA_ENC_LANE_JITTER per vessel

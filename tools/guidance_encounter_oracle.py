@@ -10,6 +10,11 @@ Prints finish ticks, separations, clearances and failure counts per kind.  It is
 were settled (--lane / --cross-offset / --lateral override scenario.CA_ENC_LANE / CA_ENC_CROSS_OFFSET / CA_ENC_HEAD_ON_LATERAL).
 
     python tools/guidance_encounter_oracle.py --scenes 32 --scene-size 2 --ticks 400 --write
+
+--plans: exchanged plans (csrc/fleet_plan.hpp) behind their numpy restatement scenario.fleet_plan_stages - from tick 1 on, a slot that holds a
+scene-mate whose mission is not over and whose last solve succeeded follows the mate's own solved path x[j][1 .. N] instead of the straight
+line.  Every kind is run twice, constant velocity and plans, and --write writes both to profiles/guidance_encounter_plans_oracle.txt
+(tests/test_gpu_guidance_fleet_plans.py copies the plans' figures).
 """
 import argparse
 import os
@@ -25,7 +30,7 @@ from oracle import binding as oracle  # noqa: E402
 MODEL_GUIDANCE_CA1 = 1
 
 
-def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=None, K=None, quiet=False, out=None):
+def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=None, K=None, quiet=False, out=None, plans=False):
     cfg = scenario.CA_ENC_OCP
     N, K, dt, max_radius = N or cfg["N"], K or cfg["K"], cfg["dt"], cfg["max_radius"]
     m = scenario.make_ca_encounters(scenes, S, seed, kind)
@@ -47,6 +52,7 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
     min_clear, finish = np.full(B, 1e300), np.full(B, -1)
     status = np.zeros(B, dtype=np.int32)
     kdt = (np.arange(N + 1, dtype=float) * dt)[:, None, None]
+    plan_fed = 0
     for t in range(ticks):
         ent, vel, sep = scenario.ca_fleet_world(X, S, radius)
         for e in range(S - 1):
@@ -56,6 +62,7 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
         x0 = X.copy()
         ak = np.zeros(B)
         active = np.zeros(B, dtype=int)
+        chosen = np.full((B, K), -1)                           # the world index behind each slot; -1: parked, or the instance does not stream
         for b in range(B):
             if k[b] >= npts:                                   # over before this tick: x0, p and lh are kept
                 if finish[b] < 0:
@@ -72,6 +79,7 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
             if predict:
                 _, _, ch = oracle.guidance_obstacles(K, pose[2], pose[0], pose[1], body)
                 v = np.array([wvel[b, vis[c]] if c >= 0 else (0.0, 0.0) for c in ch]).reshape(K, 2)
+                chosen[b] = [vis[c] if c >= 0 else -1 for c in ch]
                 p[b] = (r["p_obs"].reshape(K, 2)[None] + kdt * v[None]).reshape(N + 1, 2 * K)
             else:
                 p[b] = r["p_obs"][None]
@@ -81,6 +89,9 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
                 x0[b], pp[b], ak[b] = r["x0"], r["past_psied"], r["ak"]
             else:
                 finish[b] = t
+        if plans and predict and t >= 1:     # the iterate is exactly one hand-over old: solved last tick, handed over once
+            p, src = scenario.fleet_plan_stages(p, x, chosen, S, fixed.shape[1], status, finish, pos=scenario.FLEET_PLAN_POS["usv_model_guidance_ca1"])
+            plan_fed += int((src >= 0).sum())
         status, its = oracle.rti_batch(spec, x, u, x0, yref, yref_e, p, lh, threads=threads)
         fails[t] = int((status != 0).sum())
         for b in np.nonzero(active)[0]:
@@ -88,11 +99,12 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
         X[:] = x[:, 1]                   # the hand-over: the plant is the controller's prediction, no trajectory shift
         fixed[:, :, :2] = fixed[:, :, :2] + dt * fvel
     res = dict(finish_tick=finish, min_clearance=min_clear, min_separation=min_sep, separation_tick=sep_tick, failures_per_tick=fails,
-               final_status=status, waypoint_index=k.copy())
+               final_status=status, waypoint_index=k.copy(), plan_fed=plan_fed)
     if not quiet:
         fin = finish >= 0
-        lines = ["kind %s: %d scenes of %d, seeds %d .. %d, %d ticks, N %d, K %d, %s" % (
-                     kind, scenes, S, seed, seed + scenes - 1, ticks, N, K, "predicted per stage" if predict else "held still inside the horizon"),
+        lines = ["kind %s: %d scenes of %d, seeds %d .. %d, %d ticks, N %d, K %d, %s%s" % (
+                     kind, scenes, S, seed, seed + scenes - 1, ticks, N, K, "predicted per stage" if predict else "held still inside the horizon",
+                     ", scene-mates along their PLANS (%d plan-fed slots)" % plan_fed if plans else ", scene-mates at constant velocity"),
                  "  constants: lane %.3g +- %.3g, stagger %.3g, crossing offset %.3g, head-on lateral offset %.3g" % (
                      scenario.CA_ENC_LANE, scenario.CA_ENC_LANE_JITTER, scenario.CA_ENC_STAGGER, scenario.CA_ENC_CROSS_OFFSET,
                      scenario.CA_ENC_HEAD_ON_LATERAL),
@@ -127,7 +139,9 @@ if __name__ == "__main__":
     ap.add_argument("--lane", type=float, default=None)
     ap.add_argument("--cross-offset", type=float, default=None)
     ap.add_argument("--lateral", type=float, default=None)
-    ap.add_argument("--write", action="store_true", help="also write profiles/guidance_encounter_oracle.txt")
+    ap.add_argument("--plans", action="store_true", help="every kind twice: scene-mates at constant velocity, then along their own solved paths")
+    ap.add_argument("--write", action="store_true",
+                    help="also write profiles/guidance_encounter_oracle.txt (--plans: profiles/guidance_encounter_plans_oracle.txt)")
     a = ap.parse_args()
     if a.lane is not None:
         scenario.CA_ENC_LANE = a.lane
@@ -136,10 +150,13 @@ if __name__ == "__main__":
     if a.lateral is not None:
         scenario.CA_ENC_HEAD_ON_LATERAL = a.lateral
     text = ["# tools/guidance_encounter_oracle.py --scenes %d --scene-size %d --ticks %d --seed %d%s" % (
-        a.scenes, a.scene_size, a.ticks, a.seed, " --no-predict" if a.no_predict else ""),
-        "# the CPU oracle behind its own node arithmetic and the numpy gather: the yardstick of tests/test_gpu_guidance_fleet.py"]
+        a.scenes, a.scene_size, a.ticks, a.seed, (" --no-predict" if a.no_predict else "") + (" --plans" if a.plans else "")),
+        "# the CPU oracle behind its own node arithmetic and the numpy gather: the yardstick of tests/test_gpu_guidance_fleet%s.py" % (
+            "_plans" if a.plans else "")]
     for kind in a.kinds.split(","):
         run(a.scenes, a.scene_size, a.ticks, kind, seed=a.seed, predict=not a.no_predict, threads=a.threads, N=a.horizon, out=text)
+        if a.plans:
+            run(a.scenes, a.scene_size, a.ticks, kind, seed=a.seed, predict=not a.no_predict, threads=a.threads, N=a.horizon, out=text, plans=True)
     if a.write:
-        with open(os.path.join(ROOT, "profiles", "guidance_encounter_oracle.txt"), "w") as f:
+        with open(os.path.join(ROOT, "profiles", "guidance_encounter_plans_oracle.txt" if a.plans else "guidance_encounter_oracle.txt"), "w") as f:
             f.write("\n".join(text) + "\n")

@@ -13,7 +13,9 @@ scene starts 2 a metres to the side), the world of every resident mode moves, an
 on - prepare() gathers the scene-mates on the device ahead of usv_guidance_tick -, and `fleethost` is the loop a handle without the fleet
 needs for the same scenes: synchronise, read x0 and the world back, rebuild the S - 1 trailing entries and velocities in numpy
 (scenario.ca_fleet_world), upload, then the same four calls.  tick_net_of_qp_ms_median is the tick without the QP launch.  The JSON lines
-also go to --out (default with --fleet: profiles/guidance_fleet_probe.txt).
+also go to --out (default with --fleet: profiles/guidance_fleet_probe.txt).  --plans switches exchanged plans on in mode `fleet`
+(set_fleet(plans=True): one more kernel behind the tick, csrc/fleet_plan.hpp); the mode `planhost` is the loop a handle without them needs:
+synchronise, read x, status and the mission state back, prepare, read p back, rebuild it in numpy (scenario.fleet_plan_stages), upload it.
 
 Per run one JSON line: the median tick (a host clock around the loop's body, ending in a synchronisation for the resident modes), and for the
 resident modes the HIP-event time of the prepare's kernel (usv_guidance_tick: events on the solver's stream either side of it), the bytes a
@@ -52,7 +54,7 @@ def missions(B, L, seed):
                 world=world, world_vel=wvel)
 
 
-def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5):
+def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5, plans=False):
     import torch
     from mpc_collisionavoidance_amd import BatchOcpSolver, scenario, usv_models
     from mpc_collisionavoidance_amd.guidance import GuidanceFrontEnd
@@ -63,8 +65,8 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5):
     world, pose, vel = m["world"], m["pose"], m["vel"]
     fe.reset(m["waypoints"], pose[:, 2])
     times, tick_ms = [], []
-    out = dict(mode=mode, batch=B, N=N, K=K, L=L, ticks=ticks, warmup=warmup, fleet=fleet)
-    if mode in ("fleet", "fleethost") and fleet < 2:
+    out = dict(mode=mode, batch=B, N=N, K=K, L=L, ticks=ticks, warmup=warmup, fleet=fleet, plans=bool(plans and mode == "fleet"))
+    if mode in ("fleet", "fleethost", "planhost") and fleet < 2:
         raise SystemExit("modes fleet and fleethost need --fleet S with S >= 2")
     if mode == "hostfed":
         min_clear = np.full(B, np.inf)
@@ -89,9 +91,11 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5):
             fe.set_world(np.concatenate([world, np.tile([1000.0, 1000.0, 0.0], (B, fleet - 1, 1))], axis=1), max_radius=100.0,
                          vel=np.concatenate([m["world_vel"], np.zeros((B, fleet - 1, 2))], axis=1))
         else:
-            fe.set_world(world, max_radius=100.0, vel=m["world_vel"] if mode in ("moving", "held", "fleet") or fleet else None,
+            fe.set_world(world, max_radius=100.0, vel=m["world_vel"] if mode in ("moving", "held", "fleet", "planhost") or fleet else None,
                          predict=mode != "held")
-        if mode == "fleet":
+        if mode == "fleet" and plans:
+            fe.set_fleet(fleet, radius, plans=True)
+        elif mode in ("fleet", "planhost"):
             fe.set_fleet(fleet, radius)
         s.sync()
         for t in range(warmup + ticks):
@@ -101,7 +105,15 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5):
                 w, v = fe.world()
                 w[:, L:], v[:, L:], _ = scenario.ca_fleet_world(xr, fleet, radius)
                 fe.set_world(w, max_radius=100.0, vel=v)
+            if mode == "planhost":          # what a handle without exchanged plans needs: x, status and the mission state back, p back and up
+                xs, status, before = s.get_all("x"), s.get_int("status"), fe.mission_state()["finish_tick"]
             fe.prepare()
+            if mode == "planhost" and t >= 1:
+                p, fin = s.get_all("p"), fe.mission_state()["finish_tick"]
+                w = fe.world()[0]
+                hit = np.abs(p[:, 0].reshape(B, K, 1, 2) - w[:, None, :, :2]).max(axis=3) <= 1e-4
+                chosen = np.where(hit.any(axis=2) & (before < 0)[:, None], hit.argmax(axis=2), -1)
+                s.set_all("p", scenario.fleet_plan_stages(p, xs, chosen, fleet, L, status, fin, pos=scenario.FLEET_PLAN_POS["usv_model_guidance_ca1"])[0])
             s.solve_async()
             fe.publish(fetch=False)
             s.advance(0.0, t)
@@ -113,7 +125,7 @@ def run(mode, B, ticks, warmup, N=100, K=8, L=5, seed=0, fleet=0, radius=0.5):
         # caller's stream no longer pipelines its lineariser (usvmpc_set_stream)
         stream = torch.cuda.Stream()
         s.set_stream(stream.cuda_stream)
-        for t in range(0 if mode == "fleethost" else warmup + ticks):   # (fleethost: the kernels are those of `moving`)
+        for t in range(0 if mode in ("fleethost", "planhost") else warmup + ticks):   # (fleethost: the kernels are those of `moving`)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             fe.prepare()
@@ -149,6 +161,7 @@ if __name__ == "__main__":
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--modes", default="hostfed,resident,moving")
     ap.add_argument("--fleet", type=int, default=0, help="scenes of this many vessels (modes fleet, fleethost); the world of every resident mode moves")
+    ap.add_argument("--plans", action="store_true", help="mode fleet: exchanged plans on (set_fleet(plans=True)); the mode planhost is the host loop they replace")
     ap.add_argument("--entries", type=int, default=5, help="world entries per instance (with --fleet: the fixed ones)")
     ap.add_argument("--root", default=HERE, help="the checkout whose package is imported (default: this one)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well (the record: profiles/guidance_mission_probe.txt)")
@@ -159,11 +172,11 @@ if __name__ == "__main__":
         a.out = os.path.join(HERE, "profiles", "guidance_fleet_probe.txt")
     if a.fleet:
         with open(a.out, "a") as f:
-            f.write("# tools/guidance_mission_probe.py --batch %d --fleet %d --entries %d --modes %s --ticks %d --warmup %d --runs %d\n" % (
-                a.batch, a.fleet, a.entries, a.modes, a.ticks, a.warmup, a.runs))
+            f.write("# tools/guidance_mission_probe.py --batch %d --fleet %d --entries %d --modes %s --ticks %d --warmup %d --runs %d%s\n" % (
+                a.batch, a.fleet, a.entries, a.modes, a.ticks, a.warmup, a.runs, " --plans" if a.plans else ""))
     for r in range(a.runs):
         for mode in a.modes.split(","):
-            line = run(mode, a.batch, a.ticks, a.warmup, L=a.entries, fleet=a.fleet)
+            line = run(mode, a.batch, a.ticks, a.warmup, L=a.entries, fleet=a.fleet, plans=a.plans)
             line["run"] = r
             line["root"] = "this tree" if os.path.abspath(a.root) == HERE else "another checkout"
             print(json.dumps(line), flush=True)

@@ -9,6 +9,11 @@ Prints finish ticks, separations, clearances and failure counts per kind.  It is
 (--lane / --cross-offset / --lateral override scenario.PF_ENC_LANE / PF_ENC_CROSS_OFFSET / PF_ENC_HEAD_ON_LATERAL).
 
     python tools/pf_encounter_oracle.py --scenes 32 --scene-size 2 --ticks 400 --write
+
+--plans: exchanged plans (csrc/fleet_plan.hpp) behind their numpy restatement scenario.fleet_plan_stages - from tick 1 on, a slot that holds a
+scene-mate whose mission is not over and whose last solve succeeded follows the mate's own solved path x[j][1 .. N] instead of the straight
+line.  Every kind is run twice, constant velocity and plans, and --write writes both to profiles/pf_encounter_plans_oracle.txt
+(tests/test_gpu_pf_fleet_plans.py copies the plans' figures).
 """
 import argparse
 import os
@@ -25,7 +30,7 @@ from tests import pf_frontend_ref as R  # noqa: E402
 MODEL_PF_CA = 2
 
 
-def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=None, K=None, quiet=False, out=None):
+def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=None, K=None, quiet=False, out=None, plans=False):
     cfg = scenario.PF_MISSION_OCP
     N, K, dt = N or cfg["N"], K or cfg["K"], cfg["dt"]
     m = scenario.make_pf_encounters(scenes, S, seed, kind)
@@ -43,6 +48,7 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
     fails = np.zeros(ticks, dtype=int)
     min_sep, sep_tick = np.full(B, 1e300), np.full(B, -1)
     status = np.zeros(B, dtype=np.int32)
+    plan_fed = 0
     for t in range(ticks):
         ent, vel, sep = scenario.fleet_world(fe.x0, S, radius)
         for e in range(S - 1):
@@ -56,6 +62,10 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
             pp, ll = scenario.predict_world(world, wvel, fe.chosen, N, dt, margin=cfg["margin"])
         else:
             pp, ll = np.tile(fe.p0[:, None], (1, N + 1, 1)), np.tile(fe.lh0[:, None], (1, N, 1))
+        if plans and predict and t >= 1:     # the iterate is exactly one hand-over old: solved last tick, handed over once
+            chosen = np.where(live[:, None], fe.chosen, -1)
+            pp, src = scenario.fleet_plan_stages(pp, x, chosen, S, fixed.shape[1], status, fe.finish_tick, pos=scenario.FLEET_PLAN_POS["usv_model_pf_ca"])
+            plan_fed += int((src >= 0).sum())
         p[live], lh[live] = pp[live], ll[live]
         status, its = oracle.rti_batch(spec, x, u, fe.x0, fe.yref, fe.yref_e, p, lh, threads=threads)
         fails[t] = int((status != 0).sum())
@@ -63,12 +73,14 @@ def run(scenes, S, ticks, kind, seed=0, radius=0.5, predict=True, threads=16, N=
         fe.x0[:] = x[:, 1]               # the hand-over: the plant is the controller's prediction, no trajectory shift
         fixed[:, :, :2] = fixed[:, :, :2] + dt * fvel
     res = dict(finish_tick=fe.finish_tick.copy(), min_clearance=fe.min_clearance.copy(), min_separation=min_sep, separation_tick=sep_tick,
-               failures_per_tick=fails, final_status=status, waypoint_index=fe.k.copy())
+               failures_per_tick=fails, final_status=status, waypoint_index=fe.k.copy(), plan_fed=plan_fed)
     if not quiet:
         ft, mc = res["finish_tick"], res["min_clearance"]
         fin = ft >= 0
-        lines = ["kind %s: %d scenes of %d, seeds %d .. %d, %d ticks, %s" % (kind, scenes, S, seed, seed + scenes - 1, ticks,
-                                                                          "predicted per stage" if predict else "held still inside the horizon"),
+        lines = ["kind %s: %d scenes of %d, seeds %d .. %d, %d ticks, %s%s" % (kind, scenes, S, seed, seed + scenes - 1, ticks,
+                                                                            "predicted per stage" if predict else "held still inside the horizon",
+                                                                            ", scene-mates along their PLANS (%d plan-fed slots)" % plan_fed if plans
+                                                                            else ", scene-mates at constant velocity"),
                  "  constants: lane %.3g +- %.3g, stagger %.3g, crossing offset %.3g, head-on lateral offset %.3g" % (
                      scenario.PF_ENC_LANE, scenario.PF_ENC_LANE_JITTER, scenario.PF_ENC_STAGGER, scenario.PF_ENC_CROSS_OFFSET,
                      scenario.PF_ENC_HEAD_ON_LATERAL),
@@ -97,7 +109,8 @@ if __name__ == "__main__":
     ap.add_argument("--lane", type=float, default=None)
     ap.add_argument("--cross-offset", type=float, default=None)
     ap.add_argument("--lateral", type=float, default=None)
-    ap.add_argument("--write", action="store_true", help="also write profiles/pf_encounter_oracle.txt")
+    ap.add_argument("--plans", action="store_true", help="every kind twice: scene-mates at constant velocity, then along their own solved paths")
+    ap.add_argument("--write", action="store_true", help="also write profiles/pf_encounter_oracle.txt (--plans: profiles/pf_encounter_plans_oracle.txt)")
     a = ap.parse_args()
     if a.lane is not None:
         scenario.PF_ENC_LANE = a.lane
@@ -106,10 +119,12 @@ if __name__ == "__main__":
     if a.lateral is not None:
         scenario.PF_ENC_HEAD_ON_LATERAL = a.lateral
     text = ["# tools/pf_encounter_oracle.py --scenes %d --scene-size %d --ticks %d --seed %d%s" % (
-        a.scenes, a.scene_size, a.ticks, a.seed, " --no-predict" if a.no_predict else ""),
-        "# the CPU oracle behind the numpy front end and the numpy gather: the yardstick of tests/test_gpu_pf_fleet.py"]
+        a.scenes, a.scene_size, a.ticks, a.seed, (" --no-predict" if a.no_predict else "") + (" --plans" if a.plans else "")),
+        "# the CPU oracle behind the numpy front end and the numpy gather: the yardstick of tests/test_gpu_pf_fleet%s.py" % ("_plans" if a.plans else "")]
     for kind in a.kinds.split(","):
         run(a.scenes, a.scene_size, a.ticks, kind, seed=a.seed, predict=not a.no_predict, threads=a.threads, out=text)
+        if a.plans:
+            run(a.scenes, a.scene_size, a.ticks, kind, seed=a.seed, predict=not a.no_predict, threads=a.threads, out=text, plans=True)
     if a.write:
-        with open(os.path.join(ROOT, "profiles", "pf_encounter_oracle.txt"), "w") as f:
+        with open(os.path.join(ROOT, "profiles", "pf_encounter_plans_oracle.txt" if a.plans else "pf_encounter_oracle.txt"), "w") as f:
             f.write("\n".join(text) + "\n")

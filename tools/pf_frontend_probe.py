@@ -17,7 +17,10 @@ vessel's route, start and four fixed obstacles are moved 4 a metres east for ves
 the world of every mode moves, and two more modes exist: `fleet` is `resident` with the fleet on - prepare() gathers the scene-mates on the
 device ahead of its own kernel -, and `fleethost` is the loop a handle without the fleet needs for the same scenes: synchronise, read x0 and
 the world back, rebuild the S - 1 trailing entries and velocities in numpy (scenario.fleet_world), upload, then the same four calls.  The
-JSON lines also go to --out (default profiles/pf_fleet_probe.txt).
+JSON lines also go to --out (default profiles/pf_fleet_probe.txt).  --plans switches exchanged plans on in mode `fleet` (set_fleet(plans=True):
+one more kernel behind the prepare, csrc/fleet_plan.hpp), and the mode `planhost` is the loop a handle without them needs: synchronise, read
+x, status and the front-end state back, prepare, read p back, rebuild it in numpy (scenario.fleet_plan_stages), upload [B][N+1][2K].  --root
+imports the package of another checkout (one whose library has no plans runs `fleet` without the switch).
 
 Median over --ticks timed ticks after --warmup warm-up ticks (a host clock around the tick and a final sync), `--runs` alternating runs, one
 JSON line each, with the lineariser's and the QP launch's kernel times of the same ticks (HIP events) and the bytes a full yref rewrite
@@ -37,7 +40,9 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1]) if "--root" in sys.argv[:-1] else HERE   # (ahead of the imports below)
+sys.path.insert(0, ROOT)
 import torch  # noqa: F401,E402  (before the solver library: one HIP runtime for both)
 from mpc_collisionavoidance_amd import BatchOcpSolver, scenario, usv_models  # noqa: E402
 from mpc_collisionavoidance_amd.guidance import PathFollowingFrontEnd  # noqa: E402
@@ -56,7 +61,7 @@ def fleet_missions(m, S):
     return out
 
 
-def run(mode, B, ticks, warmup, seed=0, moving=False, fleet=0, radius=0.5):
+def run(mode, B, ticks, warmup, seed=0, moving=False, fleet=0, radius=0.5, plans=False):
     cfg = scenario.PF_MISSION_OCP
     N, K, dt = cfg["N"], cfg["K"], cfg["dt"]
     if (B, seed, fleet) not in _missions:
@@ -73,10 +78,12 @@ def run(mode, B, ticks, warmup, seed=0, moving=False, fleet=0, radius=0.5):
     fe.reset(m["waypoints"])
     if mode == "held":
         s.set_option("pf_predict", 0)
-    moves = mode == "held" or mode in ("fleet", "fleethost") or (moving and mode in ("resident", "hostfed"))
+    moves = mode == "held" or mode in ("fleet", "fleethost", "planhost") or (moving and mode in ("resident", "hostfed"))
     fe.set_world(m["world"], max_radius=cfg["max_radius"], margin=cfg["margin"], vel=m["world_vel"] if moves else None)
     n_fixed = m["world"].shape[1]
-    if mode == "fleet":
+    if mode == "fleet" and plans:
+        fe.set_fleet(fleet, radius, plans=True)
+    elif mode in ("fleet", "planhost"):
         fe.set_fleet(fleet, radius)
     elif mode == "fleethost":             # the same list, the trailing S - 1 entries the host's to fill
         far = np.tile([1000.0, 1000.0, 0.0], (B, fleet - 1, 1))
@@ -96,6 +103,16 @@ def run(mode, B, ticks, warmup, seed=0, moving=False, fleet=0, radius=0.5):
             w[:, n_fixed:], v[:, n_fixed:], _ = scenario.fleet_world(x0, fleet, radius)
             fe.set_world(w, max_radius=cfg["max_radius"], vel=v)
             fe.prepare()
+        elif mode == "planhost":
+            x, status = s.get_all("x"), s.get_int("status")          # (synchronises)
+            fe.prepare()
+            if t >= 1:
+                p, fin = s.get_all("p"), fe.state()["finish_tick"]
+                w = fe.world()[0]
+                slots = p[:, 0].reshape(B, K, 2)
+                hit = (slots[:, :, None, :] == w[:, None, :, :2]).all(axis=3)
+                chosen = np.where(hit.any(axis=2) & (fin < 0)[:, None], hit.argmax(axis=2), -1)
+                s.set_all("p", scenario.fleet_plan_stages(p, x, chosen, fleet, n_fixed, status, fin)[0])
         elif mode == "hostfed":
             x0 = s.get("x0", 0)
             fe.prepare(x0[:, 3:6], x0[:, [10, 11, 0]])
@@ -110,7 +127,8 @@ def run(mode, B, ticks, warmup, seed=0, moving=False, fleet=0, radius=0.5):
     used, discarded = s.pipeline_stats()
     st = fe.state()
     out = dict(mode=mode, batch=B, N=N, K=K, ticks=ticks, warmup=warmup, tick_ms_median=statistics.median(timed), tick_ms_min=min(timed),
-               tick_ms_max=max(timed), tick_net_of_qp_ms_median=statistics.median(timed) - float(np.median(qp)), fleet=fleet,
+               tick_ms_max=max(timed), tick_net_of_qp_ms_median=statistics.median(timed) - float(np.median(qp)), fleet=fleet, plans=bool(plans and mode == "fleet"),
+               root="this tree" if ROOT == HERE else "another checkout",
                linearize_ms_median=float(np.median(lin)), qp_ms_median=float(np.median(qp)),
                pipelined_linearisations_used=int(used), yref_writes=st["yref_writes"], yref_full_rewrite_bytes=B * (N * 16 + 14) * 8,
                failed_last_tick=int(s.fail_counts(1)[0]), moving=bool(moves),
@@ -129,17 +147,18 @@ if __name__ == "__main__":
     ap.add_argument("--moving", action="store_true", help="the world of the front-end modes moves (every stage of p / lh per tick)")
     ap.add_argument("--fleet", type=int, default=0, help="scenes of this many vessels (modes fleet, fleethost); the world of every mode moves")
     ap.add_argument("--out", default=None, help="with --fleet: where the JSON lines are also written (default profiles/pf_fleet_probe.txt)")
+    ap.add_argument("--plans", action="store_true", help="mode fleet: exchanged plans on (set_fleet(plans=True))")
+    ap.add_argument("--root", default=HERE, help="the checkout whose package is imported (default: this one)")
     a = ap.parse_args()
     lines = []
     for r in range(a.runs):
         for mode in a.modes.split(","):
-            line = run(mode, a.batch, a.ticks, a.warmup, moving=a.moving or a.fleet > 0, fleet=a.fleet)
+            line = run(mode, a.batch, a.ticks, a.warmup, moving=a.moving or a.fleet > 0, fleet=a.fleet, plans=a.plans)
             line["run"] = r
             lines.append(json.dumps(line))
             print(lines[-1], flush=True)
     if a.fleet:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        with open(a.out or os.path.join(root, "profiles", "pf_fleet_probe.txt"), "a") as f:
-            f.write("# tools/pf_frontend_probe.py --batch %d --fleet %d --modes %s --ticks %d --warmup %d --runs %d\n" % (
-                a.batch, a.fleet, a.modes, a.ticks, a.warmup, a.runs))
+        with open(a.out or os.path.join(HERE, "profiles", "pf_fleet_probe.txt"), "a") as f:
+            f.write("# tools/pf_frontend_probe.py --batch %d --fleet %d --modes %s --ticks %d --warmup %d --runs %d%s\n" % (
+                a.batch, a.fleet, a.modes, a.ticks, a.warmup, a.runs, " --plans" if a.plans else ""))
             f.write("\n".join(lines) + "\n")
